@@ -69,6 +69,9 @@ def parse_args():
   ap.add_argument('--cpu_batch', type=int, default=32, help='batch of the CPU baseline sample (SURVEY 8d: 32)')
   ap.add_argument('--cpu_steps', type=int, default=5, help='timed CPU steps after the warm-up (SURVEY 8d: >= 5)')
   ap.add_argument('--cpu_budget_s', type=float, default=200.0, help='wall-clock bound of the CPU baseline sample')
+  ap.add_argument('--dump-outputs', dest='dump_outputs', default=None, metavar='DIR',
+                  help='after the timed region, write what the last timed step computed to DIR/<name>.npy (float32 / float64): '
+                       'the values train_step returned and the parameters it updated (a fixed, seeded sample of the larger ones)')
   args = ap.parse_args()
   cfg = CONFIGS[args.config]
   for k in ('batch', 'resnet_size', 'image_size', 'act_bits', 'weight_bits', 'roofline_kernel'):
@@ -294,6 +297,65 @@ def launch_probe(torch, n=1000):
   return {'host_us_per_launch': (p1 - p0) * 1e6 / n, 'us_per_dispatch': (p2 - p0) * 1e6 / n}
 
 
+# The most train_step calls main() makes between the warm-up and the timed region, outside the launch-by-launch backlog: the
+# host-share sample (2), the recording (<= 8), the step-mode calibration (19), the host-bound probe (2) and its profiled step (1).
+# How many of them run depends on what the process measures; with --dump-outputs, untimed steps up to this count (+ K) make the
+# learner's state at the timed region a function of the arguments alone.
+MAX_UNTIMED_STEPS = 34
+DUMP_SAMPLE = 1 << 22                     # elements: a larger output is dumped as this many seeded picks (16 MiB in float32)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def collect_outputs(torch, out, learner):
+  """{name: host array} of what one step gave its caller: the values train_step returned ('out.<key>': losses, metrics, learning
+  rate; nested keys joined with '.') and the parameter buffers it updated ('params.weights', 'params.others').  Called right
+  after the step, before anything else runs."""
+  import numpy as np
+  arrays = {}
+
+  def add(name, v):
+    if isinstance(v, dict):
+      for k, x in v.items():
+        add('%s.%s' % (name, k), x)
+    elif isinstance(v, (list, tuple)):
+      for i, x in enumerate(v):
+        add('%s.%d' % (name, i), x)
+    elif torch.is_tensor(v):
+      t = v.detach()
+      t = t.double() if t.dtype == torch.float64 or not t.is_floating_point() else t.float()
+      arrays[name] = t.cpu().numpy()
+    elif isinstance(v, (bool, int, float, np.number)):
+      arrays[name] = np.asarray(v, dtype=np.float64)
+  add('out', out)
+  store = learner.graph.store
+  for name, buf, n in (('params.weights', store.w_master, store.w_size), ('params.others', store.o_master, store.o_size)):
+    if n:
+      arrays[name] = buf[:n].detach().float().cpu().numpy()
+  return arrays
+
+
+def dump_outputs(arrays, out_dir):
+  """Write `arrays` as out_dir/<name>.npy.  An array of more than DUMP_SAMPLE elements is written as a sample: the elements at
+  DUMP_SAMPLE indices drawn with a seed fixed by the array's size, in ascending order (the same picks in every run).
+  Returns {name: [shape written, shape computed]}."""
+  import numpy as np
+  os.makedirs(out_dir, exist_ok=True)
+  index = {}
+  total = 0
+  for name in sorted(arrays):
+    a = np.ascontiguousarray(arrays[name])
+    full = list(a.shape)
+    if a.size > DUMP_SAMPLE:
+      pick = np.sort(np.random.RandomState(a.size % (1 << 31)).randint(0, a.size, DUMP_SAMPLE))
+      a = a.reshape(-1)[pick]
+    total += a.nbytes
+    if total > DUMP_LIMIT_BYTES:
+      raise RuntimeError('--dump-outputs: more than %d bytes' % DUMP_LIMIT_BYTES)
+    np.save(os.path.join(out_dir, name + '.npy'), a)
+    index[name] = [list(a.shape), full]
+  return index
+
+
 def main():
   args = parse_args()
   import torch
@@ -326,7 +388,12 @@ def main():
   def barrier():
     if world > 1:
       dist.barrier()
-  learner, train_step = build_learner(args, FLAGS, tmp, rank, world, barrier)
+  learner, learner_step = build_learner(args, FLAGS, tmp, rank, world, barrier)
+  n_calls = [0]
+
+  def train_step():
+    n_calls[0] += 1
+    return learner_step()
   cfg = CONFIGS[args.config]
   if os.environ.get('PF_BENCH_MAIN_PRIORITY', '0') == '1':
     # experiment: the student's queue at high priority (the teacher's and the backward-filter queue stay at normal priority)
@@ -469,14 +536,22 @@ def main():
     if os.path.isdir(out_dir):
       with open(os.path.join(out_dir, 'bench_host_bound_profile.txt'), 'w') as f:
         f.write(text)
-  if sg is None and world == 1:
+  backlog = args.steps if sg is None and world == 1 else 0
+  if args.dump_outputs:
+    # Untimed steps up to a fixed count: the timed steps start from the same learner state in every run with these arguments,
+    # whichever step mode the calibration chose and whether the self-diagnosis ran, so that the outputs of two builds can be compared
+    if n_calls[0] > args.warmup + MAX_UNTIMED_STEPS:
+      raise RuntimeError('bench.py: %d steps before the timed region, MAX_UNTIMED_STEPS is out of date' % n_calls[0])
+    while n_calls[0] < args.warmup + MAX_UNTIMED_STEPS + args.steps - backlog:
+      train_step()
+  if backlog:
     # Launch-by-launch steps: the host runs ahead of the GPU (6 vs 11 ms per step on MobileNet, 11 vs 22 on ResNet-50), and the blocks
     # handed between the streams (record_stream: freed when the reader's event has passed) stay out of the pool for as long as the launch
     # queue is deep -- the caching allocator grows while the backlog builds up, one hipMalloc of 40-90 ms at a time (seen as
     # host stalls of that size and as `segments_allocated` moving INSIDE the timed region of round 6's first launch-by-launch lines:
     # 16.2 instead of 11.2 ms per step on MobileNet).  So the backlog is built up once, untimed: as many back-to-back steps as the timed
     # region has.
-    for _ in range(args.steps):
+    for _ in range(backlog):
       train_step()
     sync()
   n_event = args.steps if sg is None else max(0, min(args.event_steps, args.steps))
@@ -496,12 +571,15 @@ def main():
     if sg is not None and i == args.steps - n_event:
       sg.suspend()
       profiling.unpause()
-    train_step()
+    out = train_step()
     marks.append(time.perf_counter())
     if sg is not None and i >= args.steps - n_event:
       rec_marks.append(profiling.count(args.roofline_kernel))
   sync()
   dt = time.perf_counter() - t0
+  dumped = None
+  if args.dump_outputs and rank == 0:
+    dumped = dump_outputs(collect_outputs(torch, out, learner), args.dump_outputs)
   host_ms = (marks[-1] - t0) * 1e3 / max(1, args.steps)        # host-side submission time per step (GPU-bound when << ms_per_step)
   host_steps = sorted((b - a) * 1e3 for a, b in zip([t0] + marks[:-1], marks))
   probe_after = launch_probe(torch)
@@ -629,7 +707,9 @@ def main():
                    # graph.WrwSide (round 6): the backward-filter launches of a pass on a second stream, one join before the optimiser
                    'backward_filter_queue': ('second stream' if getattr(learner.graph.store, 'wrw_side', None) is not None else 'one queue'),
                    'host_share_of_two_launch_by_launch_steps': auto_share},
-        'roofline': roofline, 'cpu_baseline': cpu_baseline, 'multi_gpu': multi_gpu}
+        'roofline': roofline, 'cpu_baseline': cpu_baseline, 'multi_gpu': multi_gpu,
+        # --dump-outputs: {name: [shape written, shape computed]} of the last timed step's outputs
+        'dumped_outputs': dumped}
     print(json.dumps(line))
   if world > 1:
     dist.barrier()

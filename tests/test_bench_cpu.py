@@ -83,3 +83,79 @@ def test_bench_flag_setup_in_a_fresh_interpreter(config, tmp_path):
           % (config, root, str(tmp_path)))
   out = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, timeout=300)
   assert out.returncode == 0 and 'OK ModelHelper' in out.stdout, out.stderr[-2000:]
+
+
+def _emulated_bench(monkeypatch, tmp_path, argv):
+  """bench.main() on the emulated kernels of tests/fake_hip.py (as above); returns the number of train_step calls."""
+  import pocketflow_amd.graph as G
+  import pocketflow_amd.learners.channel_pruning.learner as CP
+  import pocketflow_amd.plan as P
+  import pocketflow_amd.losses as L
+  import pocketflow_amd.optim as Opt
+  import pocketflow_amd.profiling as PR
+  import pocketflow_amd.learners.abstract_learner as AL
+  import pocketflow_amd.learners.nonuniform_quantization.utils as NU
+  import pocketflow_amd.learners.weight_sparsification.learner as WS
+  import pocketflow_amd.learners.layerwise as LW
+  import bench
+  fake = FakeHipFull()
+  for mod in (G, P, L, Opt, WS, NU, LW, CP):
+    monkeypatch.setattr(mod, 'hip', fake)
+  monkeypatch.setattr(AL, 'require_gpu', lambda: torch.device('cpu'))
+  monkeypatch.setattr(torch.cuda, 'synchronize', lambda *a, **k: None)
+  monkeypatch.setattr(bench, 'launch_probe', lambda torch, n=1000: {'host_us_per_launch': 1.0, 'us_per_dispatch': 1.0})
+  monkeypatch.setattr(bench, 'memory_snapshot', lambda torch: {'reserved_gb': 0.0, 'segments_allocated': 0})
+  monkeypatch.setattr(PR, 'enable', lambda name: None)
+  monkeypatch.setattr(PR, 'summary', lambda name, lo=0, hi=None, side=None: (72, 7.2, 72 * 3.0e8))
+  monkeypatch.setenv('TMPDIR', str(tmp_path))
+  calls = [0]
+  build = bench.build_learner
+
+  def counting_build(*a, **k):
+    learner, step = build(*a, **k)
+
+    def counted():
+      calls[0] += 1
+      return step()
+    return learner, counted
+  monkeypatch.setattr(bench, 'build_learner', counting_build)
+  monkeypatch.setattr(sys, 'argv', ['bench.py'] + argv)
+  from pocketflow_amd.flags import FLAGS
+  try:
+    bench.main()
+  finally:
+    FLAGS.reset()
+  return calls[0]
+
+
+def test_bench_dump_outputs_do_not_depend_on_the_untimed_steps(monkeypatch, capsys, tmp_path):
+  """--dump-outputs DIR writes the last timed step's outputs as float32 / float64 .npy files (64 MiB at most), and the learner
+  state the timed steps start from does not depend on how many untimed steps the step-mode decision took: a run that tries to
+  record the step (--step_graph default: two sampled steps and the recording attempt) dumps the same arrays as one that runs
+  launch by launch from the start (--step_graph 0).  --steps sets the number of timed steps."""
+  import numpy as np
+  import bench
+  base = ['--config', 'c1', '--batch', '2', '--dtype', 'float32', '--no_cpu_baseline', '--warmup', '1',
+          '--unshared_steps', '0']
+  monkeypatch.setattr(bench, 'MAX_UNTIMED_STEPS', 12)     # (enough for the emulated runs, where no recording succeeds)
+  runs = []
+  for steps, mode in ((2, []), (2, ['--step_graph', '0']), (3, ['--step_graph', '0'])):
+    d = tmp_path / ('dump_%d_%d' % (steps, len(mode)))
+    n = _emulated_bench(monkeypatch, tmp_path, base + mode + ['--steps', str(steps), '--dump-outputs', str(d)])
+    out, err = capsys.readouterr()
+    line = json.loads([ln for ln in out.splitlines() if ln.startswith('{')][-1])
+    assert line['steps'] == steps and line['ms_per_step'] > 0
+    assert ('step graph not recorded' in err) == (not mode)
+    assert n == 1 + bench.MAX_UNTIMED_STEPS + 2 * steps, n      # warm-up and untimed steps up to the fixed count, K-step backlog, K timed
+    files = sorted(p.name for p in d.iterdir())
+    assert files == sorted(name + '.npy' for name in line['dumped_outputs'])
+    arrays = {f[:-4]: np.load(str(d / f)) for f in files}
+    assert {'out.1', 'out.2.accuracy', 'params.weights', 'params.others'} <= set(arrays), sorted(arrays)   # (lr, loss, metrics)
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    runs.append(arrays)
+  assert runs[0].keys() == runs[1].keys()
+  for name in runs[0]:
+    assert np.array_equal(runs[0][name], runs[1][name]), name
+  # one more timed step: the outputs are those of a later step
+  assert not np.array_equal(runs[1]['params.weights'], runs[2]['params.weights'])
