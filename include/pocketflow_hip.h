@@ -435,6 +435,29 @@ int pf_prox_groups(int64_t rows, int I);
 int pf_prox_norms(const float* w, const void* g, int g_dtype, float lr, int64_t rows, int I, float* partial, float* norms, void* stream);
 int pf_prox_apply(float* w, const void* g, int g_dtype, float lr, int64_t rows, int I, const float* norms, const float* thr, void* stream);
 
+/* ---- channel selection of the 'chn-pruned-rmt' learner (pf_cpr.hip; reference learners/channel_pruning_rmt/learner.py) -------------
+ * pf_cpr_gather: rows row0 + crop * B + b of P[rows][kh*kw][C] (input patches of x, zeros outside the image) and Y[rows][Co] (output
+ *   vectors of y) at the drawn output positions pos[crops][2] = (oh, ow); x [B][H][W][C] and y [B][OH][OW][Co] NHWC, float32 / bf16.
+ * pf_cpr_gram: over the secondary sample idx[n] of those rows, X[i*Co + o][c] = sum_k P[idx[i]][k][c] * W[o][k][c] (W: KRSC float32),
+ *   X^T X and X^T y in float64, divided by ||X^T X||_F and written as float32 xtx[C][C], xty[C]; ws: pf_cpr_gram_ws(C) doubles.
+ * pf_cpr_ista: `iters` ISTA iterations from m0 with threshold gamma * lr; the result in mask[C], its non-zero count in nnz[0];
+ *   m_ws: 2 * C floats.
+ * pf_cpr_lstsq_step: one Adam step on W[K][Co] (HWIO kernel matrix, K = kh*kw*C) for the kept rows kidx[Kp] (pos[K]: position in kidx
+ *   or -1); R: N x Co residual workspace; part: pf_cpr_lstsq_splits(N, Kp, Co) * Kp * Co floats.  pf_cpr_lstsq_resid: R alone. */
+int pf_cpr_gather(const void* x, int x_dtype, const void* y, int y_dtype, const int* pos, int crops, int B, int H, int W, int C, int OH, int OW,
+                  int Co, int kh, int kw, int stride, int pad_t, int pad_l, float* P, float* Y, int64_t row0, void* stream);
+int64_t pf_cpr_gram_ws(int C);
+int pf_cpr_gram(const float* P, const float* Y, const int* idx, int64_t n, int kk, int C, int Co, const float* w, double* ws, int64_t ws_elems,
+                float* xtx, float* xty, void* stream);
+int pf_cpr_ista(const float* A, const float* b, const float* m0, float* m_ws, float* mask, int C, float gamma, float lr, int iters, int* nnz,
+                void* stream);
+int pf_cpr_lstsq_splits(int64_t N, int Kp, int Co);
+int pf_cpr_lstsq_step(const float* P, int K, const int* kidx, const int* pos, int Kp, const float* Y, float* R, int64_t N, int Co, float* W,
+                      float* m, float* v, float* part, float wd, float lr_t, float beta1, float beta2, float c1, float c2, float eps,
+                      void* stream);
+int pf_cpr_lstsq_resid(const float* P, int K, const int* kidx, int Kp, const float* W, const float* Y, float* R, int64_t N, int Co,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,7 @@ SYMBOLS = [
     'pf_conv_stem3_supported', 'pf_conv_stem3_fwd', 'pf_conv_stem3_wrw_slabs', 'pf_conv_stem3_wrw',
     'pf_conv1x1_fwd_affine', 'pf_conv2d_fwd_affine', 'pf_conv2d_bwd_data_strided_stats_groups',
     'pf_conv2d_bwd_data_strided_bnstats',
+    'pf_cpr_gather', 'pf_cpr_gram_ws', 'pf_cpr_gram', 'pf_cpr_ista', 'pf_cpr_lstsq_splits', 'pf_cpr_lstsq_step', 'pf_cpr_lstsq_resid',
 ]
 
 
@@ -76,6 +77,7 @@ def _load() -> ctypes.CDLL:
     fn = getattr(lib, name)            # AttributeError here = header/library mismatch
     if name not in ('pf_error_string',):
       fn.restype = c_int
+  lib.pf_cpr_gram_ws.restype = c_int64
   return lib
 
 
@@ -286,6 +288,112 @@ def prox_apply(w, g, lr: float, rows: int, I: int, norms, thr) -> None:
   _dev(w)
   _check(_lib.pf_prox_apply(_ptr(w), _ptr(g), c_int(dtype_code(g)), c_float(lr), c_int64(rows), c_int(I), _ptr(norms), _ptr(thr),
                             _stream()), 'pf_prox_apply')
+
+
+# ------------------------------------------------------------------------------------------------
+# channel selection of the 'chn-pruned-rmt' learner (pf_cpr.hip)
+# ------------------------------------------------------------------------------------------------
+
+def _f32_dev(*ts) -> None:
+  for t in ts:
+    _dev(t)
+    if t.dtype != torch.float32 or not t.is_contiguous():
+      raise TypeError('pf_cpr: contiguous float32 tensors expected (got %s)' % t.dtype)
+
+
+def _i32_dev(*ts) -> None:
+  for t in ts:
+    _dev(t)
+    if t.dtype != torch.int32 or not t.is_contiguous():
+      raise TypeError('pf_cpr: contiguous int32 tensors expected (got %s)' % t.dtype)
+
+
+def cpr_gather(x, y, pos, kh: int, kw: int, stride: int, pad_t: int, pad_l: int, P, Y, row0: int) -> None:
+  """Rows row0 + crop * B + b of P [rows][kh*kw][C] / Y [rows][Co] (float32) from the NHWC-stored taps x [B, C, H, W] and
+  y [B, Co, OH, OW] (float32 / bf16, channels-last) at the output positions pos [crops][2] (int32 (oh, ow))."""
+  _dev(x)
+  _dev(y)
+  _i32_dev(pos)
+  _f32_dev(P, Y)
+  B, C, H, W = x.shape
+  By, Co, OH, OW = y.shape
+  crops = pos.shape[0]
+  if By != B or not x.is_contiguous(memory_format=torch.channels_last) or not y.is_contiguous(memory_format=torch.channels_last):
+    raise TypeError('cpr_gather: channels-last taps of one batch expected')
+  if pos.numel() != 2 * crops or int(pos[:, 0].min()) < 0 or int(pos[:, 0].max()) >= OH or int(pos[:, 1].min()) < 0 or int(pos[:, 1].max()) >= OW:
+    raise ValueError('cpr_gather: positions outside the %d x %d output' % (OH, OW))
+  rows = row0 + crops * B
+  if P.numel() < rows * kh * kw * C or Y.numel() < rows * Co:
+    raise ValueError('cpr_gather: P / Y hold fewer than %d rows' % rows)
+  _check(_lib.pf_cpr_gather(_ptr(x), c_int(dtype_code(x)), _ptr(y), c_int(dtype_code(y)), _ptr(pos), c_int(crops), c_int(B), c_int(H), c_int(W),
+                            c_int(C), c_int(OH), c_int(OW), c_int(Co), c_int(kh), c_int(kw), c_int(stride), c_int(pad_t), c_int(pad_l), _ptr(P),
+                            _ptr(Y), c_int64(row0), _stream()), 'pf_cpr_gather')
+
+
+def cpr_gram_ws(C: int) -> int:
+  return int(_lib.pf_cpr_gram_ws(c_int(C)))
+
+
+def cpr_gram(P, Y, idx, kk: int, C: int, Co: int, w_krsc, ws, xtx, xty) -> None:
+  """xtx [C][C], xty [C] (float32) = X^T X / ||X^T X||_F, X^T y / ||X^T X||_F, accumulated in float64, X over the rows idx (int32) of
+  P [rows][kk][C] with the KRSC float32 kernel w_krsc [Co][kk][C]; ws: float64 workspace of cpr_gram_ws(C) elements."""
+  _f32_dev(P, Y, w_krsc, xtx, xty)
+  _i32_dev(idx)
+  _dev(ws)
+  rows = P.numel() // (kk * C)
+  if ws.dtype != torch.float64 or ws.numel() < cpr_gram_ws(C) or w_krsc.numel() != Co * kk * C or xtx.numel() < C * C or xty.numel() < C:
+    raise ValueError('cpr_gram: buffer sizes')
+  if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= rows or Y.numel() < rows * Co):
+    raise ValueError('cpr_gram: row indices outside the %d sampled rows' % rows)
+  _check(_lib.pf_cpr_gram(_ptr(P), _ptr(Y), _ptr(idx), c_int64(idx.numel()), c_int(kk), c_int(C), c_int(Co), _ptr(w_krsc), _ptr(ws),
+                          c_int64(ws.numel()), _ptr(xtx), _ptr(xty), _stream()), 'pf_cpr_gram')
+
+
+def cpr_ista(A, b, m0, m_ws, mask, gamma: float, lr: float, iters: int, nnz) -> None:
+  """mask = `iters` ISTA iterations from m0 (threshold float32(gamma) * float32(lr)); nnz[0] (int32) = its non-zero count."""
+  C = b.numel()
+  _f32_dev(A, b, m0, m_ws, mask)
+  _i32_dev(nnz)
+  if A.numel() != C * C or m0.numel() != C or m_ws.numel() < 2 * C or mask.numel() != C:
+    raise ValueError('cpr_ista: buffer sizes')
+  _check(_lib.pf_cpr_ista(_ptr(A), _ptr(b), _ptr(m0), _ptr(m_ws), _ptr(mask), c_int(C), c_float(gamma), c_float(lr), c_int(iters), _ptr(nnz),
+                          _stream()), 'pf_cpr_ista')
+
+
+def cpr_lstsq_splits(N: int, Kp: int, Co: int) -> int:
+  return int(_lib.pf_cpr_lstsq_splits(c_int64(N), c_int(Kp), c_int(Co)))
+
+
+def _lstsq_check(P, kidx, Y, R, W, N, Co):
+  _f32_dev(P, Y, R, W)
+  _i32_dev(kidx)
+  K = W.numel() // Co
+  if P.numel() < N * K or Y.numel() < N * Co or R.numel() < N * Co or W.numel() != K * Co:
+    raise ValueError('cpr_lstsq: buffer sizes')
+  if kidx.numel() and (int(kidx.min()) < 0 or int(kidx.max()) >= K):
+    raise ValueError('cpr_lstsq: kept rows outside the kernel')
+  return K
+
+
+def cpr_lstsq_step(P, kidx, pos, Y, R, W, m, v, part, N: int, Co: int, wd: float, lr_t: float, beta1: float, beta2: float, c1: float,
+                   c2: float, eps: float) -> None:
+  """One Adam step of the reference's meta least-squares problem on W [K][Co] over X = P[:N][:, kidx] (see pf_cpr.hip)."""
+  K = _lstsq_check(P, kidx, Y, R, W, N, Co)
+  _f32_dev(m, v, part)
+  _i32_dev(pos)
+  Kp = kidx.numel()
+  if pos.numel() != K or m.numel() != K * Co or v.numel() != K * Co or part.numel() < cpr_lstsq_splits(N, Kp, Co) * Kp * Co:
+    raise ValueError('cpr_lstsq_step: buffer sizes')
+  _check(_lib.pf_cpr_lstsq_step(_ptr(P), c_int(K), _ptr(kidx), _ptr(pos), c_int(Kp), _ptr(Y), _ptr(R), c_int64(N), c_int(Co), _ptr(W), _ptr(m),
+                                _ptr(v), _ptr(part), c_float(wd), c_float(lr_t), c_float(beta1), c_float(beta2), c_float(c1), c_float(c2),
+                                c_float(eps), _stream()), 'pf_cpr_lstsq_step')
+
+
+def cpr_lstsq_resid(P, kidx, W, Y, R, N: int, Co: int) -> None:
+  """R = P[:N][:, kidx] W[kidx] - Y."""
+  K = _lstsq_check(P, kidx, Y, R, W, N, Co)
+  _check(_lib.pf_cpr_lstsq_resid(_ptr(P), c_int(K), _ptr(kidx), c_int(kidx.numel()), _ptr(W), _ptr(Y), _ptr(R), c_int64(N), c_int(Co),
+                                 _stream()), 'pf_cpr_lstsq_resid')
 
 
 # ------------------------------------------------------------------------------------------------
