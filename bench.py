@@ -3,6 +3,7 @@
 distillation (BASELINE.json configs[2]) on N MI355X GPUs of one node, synthetic 224x224x3 batches.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -10,6 +11,11 @@ A "step" is one full pass of the hot path over one batch per GPU: teacher forwar
 of all 54 kernels, student forward (BN+ReLU+activation fake-quant applied inside the 1x1 convolutions), CE + coupled L2 +
 distillation loss, backward with straight-through estimators, [RCCL all-reduce], fused Adam.
 Rank 0 prints ONE JSON line (contract in the task description).
+
+A plain run does what the headline figure needs: set-up, warm-up (with the step-mode calibration), the K timed steps,
+--dump-outputs and the JSON line.  --full adds what is measured or checked besides it, outside the timed region: the
+host-share sample, the launch probes, the allocator snapshots and the host-bound self-diagnosis, roofline.hbm_region.unshared
+(extra steps), the CPU baseline (tens of seconds on the host) and, with N > 1, the data-parallel invariants (`multi_gpu`).
 """
 import argparse
 import json
@@ -51,7 +57,10 @@ def parse_args():
   ap.add_argument('--roofline_kernel', default=None,
                   help='profiling region whose launches are timed with HIP events: conv1x1_fwd | conv1x1_wrw | '
                        'conv1x1_bwd_data | conv2d_fwd | bn_bwd_apply | bn_bwd_stats | bn_act_quant_apply | bn_stats')
-  ap.add_argument('--no_cpu_baseline', action='store_true')
+  ap.add_argument('--full', action='store_true',
+                  help='also measure and check what the headline figure does not need (see the module docstring); '
+                       'a plain run leaves those keys of the JSON line null')
+  ap.add_argument('--no_cpu_baseline', action='store_true', help='with --full: leave the CPU baseline out')
   ap.add_argument('--step_graph', type=int, default=None,
                   help='1 (default): the steady-state step is recorded in a hipGraph during the warm-up and replayed '
                        '(pocketflow_amd/step_graph.py; N > 1: two graphs around the gradient-exchange calls); 0: every step is issued launch by launch.  The throughput of a '
@@ -59,14 +68,14 @@ def parse_args():
                        'cannot slow a recorded step down; a replayed graph cannot carry timing events on ROCm, so the last --event_steps '
                        'steps are issued launch by launch for the roofline figure')
   ap.add_argument('--unshared_steps', type=int, default=2,
-                  help='extra launch-by-launch steps OUTSIDE the timed region with the teacher branch serialised with the student step: '
-                       'the roofline region with the chip to itself (roofline.unshared); 0 = skip')
+                  help='with --full: extra launch-by-launch steps OUTSIDE the timed region with the teacher branch serialised with the '
+                       'student step: the roofline region with the chip to itself (roofline.unshared); 0 = skip')
   ap.add_argument('--event_steps', type=int, default=3,
                   help='with --step_graph 1: this many of the K timed steps run launch by launch, their roofline-region launches '
                        'bracketed by HIP events (a replayed graph cannot carry timing events)')
   ap.add_argument('--no_reexec', action='store_true', help=argparse.SUPPRESS)       # accepted, ignored (older scripts)
   ap.add_argument('--no_prewarm', action='store_true', help=argparse.SUPPRESS)      # accepted, ignored (older scripts)
-  ap.add_argument('--cpu_batch', type=int, default=32, help='batch of the CPU baseline sample (SURVEY 8d: 32)')
+  ap.add_argument('--cpu_batch', type=int, default=32, help='batch of the CPU baseline sample (--full; SURVEY 8d: 32)')
   ap.add_argument('--cpu_steps', type=int, default=5, help='timed CPU steps after the warm-up (SURVEY 8d: >= 5)')
   ap.add_argument('--cpu_budget_s', type=float, default=200.0, help='wall-clock bound of the CPU baseline sample')
   ap.add_argument('--dump-outputs', dest='dump_outputs', default=None, metavar='DIR',
@@ -298,9 +307,9 @@ def launch_probe(torch, n=1000):
 
 
 # The most train_step calls main() makes between the warm-up and the timed region, outside the launch-by-launch backlog: the
-# host-share sample (2), the recording (<= 8), the step-mode calibration (19), the host-bound probe (2) and its profiled step (1).
-# How many of them run depends on what the process measures; with --dump-outputs, untimed steps up to this count (+ K) make the
-# learner's state at the timed region a function of the arguments alone.
+# host-share sample (2, --full), the recording (<= 8), the step-mode calibration (19), the host-bound probe (2, --full) and its
+# profiled step (1, --full).  How many of them run depends on what the process measures; with --dump-outputs, untimed steps up to
+# this count (+ K) make the learner's state at the timed region a function of the arguments alone, with or without --full.
 MAX_UNTIMED_STEPS = 34
 DUMP_SAMPLE = 1 << 22                     # elements: a larger output is dumped as this many seeded picks (16 MiB in float32)
 DUMP_LIMIT_BYTES = 64 << 20
@@ -424,15 +433,16 @@ def main():
   # submits a step in ~11 ms); the two-graph recorded step has only ever run over gloo on a shared GPU.  PF_STEP_GRAPH_DIST=1 opts in
   # (kept only where its replays are not slower, decided by all ranks together, below).
   if args.step_graph is None and (world == 1 or os.environ.get('PF_STEP_GRAPH_DIST', '0') == '1'):
-    # default: the step is recorded; how host-bound it is launch by launch (the host's share of two untimed steps from an empty launch
-    # queue) is measured first and reported in the line (config.host_share_of_two_launch_by_launch_steps)
-    torch.cuda.synchronize()
-    a0 = time.perf_counter()
-    train_step()
-    train_step()
-    a1 = time.perf_counter()
-    torch.cuda.synchronize()
-    auto_share = (a1 - a0) / max(time.perf_counter() - a0, 1e-9)
+    # default: the step is recorded; with --full, how host-bound it is launch by launch (the host's share of two untimed steps from an
+    # empty launch queue) is measured first and reported in the line (config.host_share_of_two_launch_by_launch_steps)
+    if args.full:
+      torch.cuda.synchronize()
+      a0 = time.perf_counter()
+      train_step()
+      train_step()
+      a1 = time.perf_counter()
+      torch.cuda.synchronize()
+      auto_share = (a1 - a0) / max(time.perf_counter() - a0, 1e-9)
     FLAGS.enbl_step_graph = True          # (the measured host share is reported; the recording is the default)
   if FLAGS.enbl_step_graph:
     # N > 1: every rank records its own two graphs around the gradient-exchange calls (step_graph.CudaBackend.cut).  Every
@@ -501,41 +511,38 @@ def main():
         recorded_choice['replayed_steps'] = sg.n_replays
         FLAGS.enbl_step_graph = False
         sg = None
-  # Self-diagnosis of a host-bound process.  Seven bench processes of round 2 ran at 150 ms instead of
+  # Self-diagnosis of a host-bound process, --full.  Seven bench processes of round 2 ran at 150 ms instead of
   # 29 ms per step with the same kernels: the caching allocator was going to the driver for every tensor (torch.empty at
   # 185 us) because a reference cycle in the layer executor kept each step's activations alive until Python's cyclic
   # collector happened to run.  The cycle is gone (graph._BnLazy) and tests/ hold that property; what stays here is cheap
   # and outside the timed region: an empty-launch probe, the host's share of two untimed steps from an empty queue (0.45
   # for this workload, 1.0 when host-bound), the allocator's counters -- all part of the JSON line -- and, if the process
   # IS host-bound, one more untimed step under cProfile on stderr.
-  torch.cuda.synchronize()
-  probe_warm = launch_probe(torch)
-  h0 = time.perf_counter()
-  train_step()
-  train_step()
-  h1 = time.perf_counter()
-  torch.cuda.synchronize()
-  h2 = time.perf_counter()
-  probe_warm['host_share_of_two_steps'] = (h1 - h0) / max(h2 - h0, 1e-9)
-  mem_warm = memory_snapshot(torch)
-  if world == 1 and (probe_warm['us_per_dispatch'] > 40.0 or probe_warm['host_share_of_two_steps'] > 0.9):   # (an extra step on one rank only would dead-lock the all-reduce)
-    import cProfile
-    import io
-    import pstats
-    prof = cProfile.Profile()
-    prof.enable()
-    train_step()
-    prof.disable()
+  probe_warm = mem_warm = None
+  if args.full:
     torch.cuda.synchronize()
-    buf = io.StringIO()
-    pstats.Stats(prof, stream=buf).sort_stats('tottime').print_stats(14)
-    text = 'bench.py: host-bound process (probe %r)\nmemory before the profiled step %r\nmemory after it %r\n%s' % (
-        probe_warm, mem_warm, memory_snapshot(torch), buf.getvalue())
-    sys.stderr.write(text)
-    out_dir = os.path.join(ROOT, 'gpurun_out')
-    if os.path.isdir(out_dir):
-      with open(os.path.join(out_dir, 'bench_host_bound_profile.txt'), 'w') as f:
-        f.write(text)
+    probe_warm = launch_probe(torch)
+    h0 = time.perf_counter()
+    train_step()
+    train_step()
+    h1 = time.perf_counter()
+    torch.cuda.synchronize()
+    h2 = time.perf_counter()
+    probe_warm['host_share_of_two_steps'] = (h1 - h0) / max(h2 - h0, 1e-9)
+    mem_warm = memory_snapshot(torch)
+    if world == 1 and (probe_warm['us_per_dispatch'] > 40.0 or probe_warm['host_share_of_two_steps'] > 0.9):   # (an extra step on one rank only would dead-lock the all-reduce)
+      import cProfile
+      import io
+      import pstats
+      prof = cProfile.Profile()
+      prof.enable()
+      train_step()
+      prof.disable()
+      torch.cuda.synchronize()
+      buf = io.StringIO()
+      pstats.Stats(prof, stream=buf).sort_stats('tottime').print_stats(14)
+      sys.stderr.write('bench.py: host-bound process (probe %r)\nmemory before the profiled step %r\nmemory after it %r\n%s' % (
+          probe_warm, mem_warm, memory_snapshot(torch), buf.getvalue()))
   backlog = args.steps if sg is None and world == 1 else 0
   if args.dump_outputs:
     # Untimed steps up to a fixed count: the timed steps start from the same learner state in every run with these arguments,
@@ -582,8 +589,8 @@ def main():
     dumped = dump_outputs(collect_outputs(torch, out, learner), args.dump_outputs)
   host_ms = (marks[-1] - t0) * 1e3 / max(1, args.steps)        # host-side submission time per step (GPU-bound when << ms_per_step)
   host_steps = sorted((b - a) * 1e3 for a, b in zip([t0] + marks[:-1], marks))
-  probe_after = launch_probe(torch)
-  mem_after = memory_snapshot(torch)
+  probe_after = launch_probe(torch) if args.full else None
+  mem_after = memory_snapshot(torch) if args.full else None
   if os.environ.get('PF_BENCH_TRACE_STEPS') and rank == 0:    # host-side submission time of every step (diagnostics)
     sys.stderr.write('host ms/step: %s | tail sync %.1f ms\n' % (
         ' '.join('%.1f' % ((b - a) * 1e3) for a, b in zip([t0] + marks[:-1], marks)), (t0 + dt - marks[-1]) * 1e3))
@@ -592,6 +599,7 @@ def main():
     t = torch.tensor([dt], dtype=torch.float64, device='cuda')
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
+  if world > 1 and args.full:
     # data-parallel invariants, outside the timed region: after the broadcast and K all-reduced updates every rank must
     # hold bit-identical parameters (deterministic kernels + one summed gradient); how much of the exchange was launched
     # from inside backward; bytes on the links per step (utils/multi_gpu_wrapper.py:83-98 of the reference = Horovod)
@@ -616,14 +624,14 @@ def main():
   n_s, ms_s, work_s = profiling.summary(args.roofline_kernel, side=True)
   by_stream = {'main_stream': {'launches': n_m, 'avg_launch_ms': (ms_m / n_m) if n_m else None},
                'teacher_stream': {'launches': n_s, 'avg_launch_ms': (ms_s / n_s) if n_s else None}}
-  # The same region with the chip to itself (`roofline.unshared`, outside the timed region): two more launch-by-launch steps in which the
+  # The same region with the chip to itself (`roofline.unshared`, --full, outside the timed region): two more launch-by-launch steps in which the
   # teacher branch is SERIALISED with the student's step (TeacherAhead.serialise: the side stream waits for the main stream before the
   # teacher is issued, the next step waits for the teacher as always) -- every launch of the region then runs alone, which is the figure
   # that is comparable round over round (round 3's bench had no teacher beside the region) and that measures the kernels rather than
   # the overlap.  `frac` above stays the shared figure: it is what a rocprofv3 trace of this command shows.
   unshared = None
   ahead_h = getattr(learner, '_teacher_ahead', None)
-  if world == 1 and n_launch and ahead_h is not None and not getattr(ahead_h, 'handover_only', False) and args.unshared_steps > 0:
+  if args.full and world == 1 and n_launch and ahead_h is not None and not getattr(ahead_h, 'handover_only', False) and args.unshared_steps > 0:
     sync()
     ahead_h.serialise = True
     train_step()                                       # (its teacher logits were issued un-serialised by the last timed step)
@@ -668,9 +676,9 @@ def main():
                 'achieved': mfma_ach / 1e12, 'peak': MFMA_BF16_PEAK / 1e12, 'unit': 'TFLOP/s', 'frac': mfma_ach / MFMA_BF16_PEAK,
                 'traffic': None, 'step_mfma_frac': mfma_ach / MFMA_BF16_PEAK, 'hbm_region': hbm_region}
     cpu_baseline = None
-    if world == 1 and not args.no_cpu_baseline and cfg['learner'] == 'uniform':   # the oracle timer restates the UQ step
+    if args.full and world == 1 and not args.no_cpu_baseline and cfg['learner'] == 'uniform':   # the oracle timer restates the UQ step
       # the reference path restated on the host cores (oracle/learner_oracle.py), in a child process with a
-      # hard wall-clock limit so that the default run always finishes within minutes
+      # hard wall-clock limit so that a --full run always finishes within minutes
       import subprocess
       code = ('import json, sys; sys.path.insert(0, %r); from oracle.learner_oracle import time_cpu_baseline; '
               'print("CPU_BASELINE " + json.dumps(time_cpu_baseline(%d, %d, %d, %d, %d, %d, budget_s=%f)))'
@@ -692,8 +700,8 @@ def main():
         'value_per_gpu': per_gpu, 'host_submit_ms_per_step': host_ms,
         'host_submit_ms_min_median_max': [host_steps[0], host_steps[len(host_steps) // 2], host_steps[-1]],
         'host_submit_ms_steps': [round((b - a) * 1e3, 2) for a, b in zip([t0] + marks[:-1], marks)],
-        'launch_probe': {'after_warmup': probe_warm, 'after_timed_region': probe_after, 'extra_untimed_steps': 2},
-        'memory': {'after_warmup': mem_warm, 'after_timed_region': mem_after},
+        'launch_probe': ({'after_warmup': probe_warm, 'after_timed_region': probe_after, 'extra_untimed_steps': 2} if args.full else None),
+        'memory': ({'after_warmup': mem_warm, 'after_timed_region': mem_after} if args.full else None),
         'config': {'workload': cfg['workload'].format(**vars(args)), 'name': args.config,
                    'global_batch': args.batch * world, 'parallelism': 'dp%d' % world,
                    # learners/teacher_ahead.py (the default since round 4): the teacher's forward over batch k+1 on a second stream;

@@ -1,6 +1,6 @@
 """bench.py's control flow end to end WITHOUT a GPU: the HIP entry points are replaced by the float32 emulations of
 tests/fake_hip.py and the few torch.cuda calls bench.py makes are stubbed, so that every line of `main()` runs -- argument
-handling, learner construction, warm-up, the self-diagnosis (here forced into its host-bound branch), the timed region and
+handling, learner construction, warm-up, the self-diagnosis of --full (here forced into its host-bound branch), the timed region and
 the JSON line with every key of the driver's contract.  (What it measures is meaningless; the GPU runs measure.)"""
 import json
 import sys
@@ -39,7 +39,7 @@ def test_bench_main_runs_end_to_end_on_emulated_kernels(monkeypatch, capsys, tmp
   monkeypatch.setattr(PR, 'summary', lambda name, lo=0, hi=None, side=None: (72, 7.2, 72 * 3.0e8))
   monkeypatch.setenv('TMPDIR', str(tmp_path))
   monkeypatch.setattr(sys, 'argv', ['bench.py', '--config', config, '--steps', '1', '--warmup', '1', '--batch', '2',
-                                    '--image_size', '32', '--dtype', 'float32', '--no_cpu_baseline'] + extra)
+                                    '--image_size', '32', '--dtype', 'float32', '--full', '--no_cpu_baseline'] + extra)
   from pocketflow_amd.flags import FLAGS
   try:
     bench.main()
@@ -130,22 +130,22 @@ def _emulated_bench(monkeypatch, tmp_path, argv):
 
 def test_bench_dump_outputs_do_not_depend_on_the_untimed_steps(monkeypatch, capsys, tmp_path):
   """--dump-outputs DIR writes the last timed step's outputs as float32 / float64 .npy files (64 MiB at most), and the learner
-  state the timed steps start from does not depend on how many untimed steps the step-mode decision took: a run that tries to
-  record the step (--step_graph default: two sampled steps and the recording attempt) dumps the same arrays as one that runs
-  launch by launch from the start (--step_graph 0).  --steps sets the number of timed steps."""
+  state the timed steps start from does not depend on how many untimed steps the step-mode decision and --full took: a --full
+  run that tries to record the step (--step_graph default: two sampled steps, the recording attempt, the self-diagnosis) dumps the
+  same arrays as a plain one that runs launch by launch from the start (--step_graph 0).  --steps sets the number of timed steps."""
   import numpy as np
   import bench
   base = ['--config', 'c1', '--batch', '2', '--dtype', 'float32', '--no_cpu_baseline', '--warmup', '1',
           '--unshared_steps', '0']
   monkeypatch.setattr(bench, 'MAX_UNTIMED_STEPS', 12)     # (enough for the emulated runs, where no recording succeeds)
   runs = []
-  for steps, mode in ((2, []), (2, ['--step_graph', '0']), (3, ['--step_graph', '0'])):
+  for steps, mode in ((2, ['--full']), (2, ['--step_graph', '0']), (3, ['--step_graph', '0'])):
     d = tmp_path / ('dump_%d_%d' % (steps, len(mode)))
     n = _emulated_bench(monkeypatch, tmp_path, base + mode + ['--steps', str(steps), '--dump-outputs', str(d)])
     out, err = capsys.readouterr()
     line = json.loads([ln for ln in out.splitlines() if ln.startswith('{')][-1])
     assert line['steps'] == steps and line['ms_per_step'] > 0
-    assert ('step graph not recorded' in err) == (not mode)
+    assert ('step graph not recorded' in err) == ('--step_graph' not in mode)
     assert n == 1 + bench.MAX_UNTIMED_STEPS + 2 * steps, n      # warm-up and untimed steps up to the fixed count, K-step backlog, K timed
     files = sorted(p.name for p in d.iterdir())
     assert files == sorted(name + '.npy' for name in line['dumped_outputs'])
@@ -159,3 +159,38 @@ def test_bench_dump_outputs_do_not_depend_on_the_untimed_steps(monkeypatch, caps
     assert np.array_equal(runs[0][name], runs[1][name]), name
   # one more timed step: the outputs are those of a later step
   assert not np.array_equal(runs[1]['params.weights'], runs[2]['params.weights'])
+
+
+@pytest.mark.parametrize('full', [False, True])
+def test_bench_plain_run_does_only_what_the_headline_needs(monkeypatch, capsys, tmp_path, full):
+  """A plain run makes the warm-up, backlog and timed steps and nothing else: no host-share sample, no self-diagnosis, no
+  roofline.unshared steps, no launch probes, no CPU baseline.  --full runs all of them (the CPU baseline's child process is
+  stood in for)."""
+  import subprocess
+  import bench
+  started = []
+
+  def fake_run(cmd, **kw):
+    started.append(cmd)
+    return subprocess.CompletedProcess(cmd, 0, stdout='CPU_BASELINE {"value": 1.5}\n', stderr='')
+  monkeypatch.setattr(subprocess, 'run', fake_run)
+  monkeypatch.setenv('PF_TEACHER_AHEAD', 'inline')           # (the teacher helper the roofline.unshared steps need)
+  argv = ['--config', 'c2', '--resnet_size', '18', '--batch', '2', '--image_size', '32', '--dtype', 'float32',
+          '--warmup', '1', '--steps', '2'] + (['--full'] if full else [])
+  n = _emulated_bench(monkeypatch, tmp_path, argv)
+  out, err = capsys.readouterr()
+  line = json.loads([ln for ln in out.splitlines() if ln.startswith('{')][-1])
+  assert line['steps'] == 2 and line['ms_per_step'] > 0 and line['value'] > 0
+  unshared = line['roofline']['hbm_region']['unshared']
+  share = line['config']['host_share_of_two_launch_by_launch_steps']
+  if not full:
+    assert n == 1 + 2 * 2, n                                  # warm-up, K-step backlog (no step is recorded here), K timed
+    assert started == [] and line['cpu_baseline'] is None and unshared is None and share is None
+    assert line['launch_probe'] is None and line['memory'] is None and 'host-bound process' not in err
+    return
+  profiled = 1 if 'host-bound process' in err else 0
+  assert n == 1 + 2 + 2 + profiled + 2 * 2 + 1 + 2, n        # + host-share sample, self-diagnosis, hand-over and roofline.unshared
+  assert share is not None
+  assert len(started) == 1 and 'time_cpu_baseline' in started[0][-1] and line['cpu_baseline'] == {'value': 1.5}
+  assert unshared['steps'] == 2 and line['launch_probe']['after_timed_region'] is not None
+  assert line['memory']['after_warmup'] is not None

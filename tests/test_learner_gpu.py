@@ -197,7 +197,7 @@ def test_bench_two_ranks_share_one_gpu(tmp_path, recorded):
     env.pop('PF_STEP_GRAPH_DIST', None)
   cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr',
          '127.0.0.1', '--master-port', '29533' if recorded else '29535', os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '4',
-         '--event_steps', '2', '--warmup', '1', '--batch', '8', '--image_size', '64', '--no_cpu_baseline']
+         '--event_steps', '2', '--warmup', '1', '--batch', '8', '--image_size', '64', '--full', '--no_cpu_baseline']
   out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
   assert out.returncode == 0, out.stderr[-3000:]
   line = [l for l in out.stdout.splitlines() if l.startswith('{')][-1]
@@ -234,7 +234,7 @@ def test_bench_two_gpus_over_rccl(tmp_path):
   env.pop('PF_SINGLE_DEVICE', None)
   cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr',
          '127.0.0.1', '--master-port', '29541', os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3',
-         '--warmup', '1', '--batch', '16', '--image_size', '64', '--no_cpu_baseline']
+         '--warmup', '1', '--batch', '16', '--image_size', '64', '--full', '--no_cpu_baseline']
   out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
   assert out.returncode == 0, out.stderr[-3000:]
   rec = json.loads([l for l in out.stdout.splitlines() if l.startswith('{')][-1])
