@@ -415,6 +415,20 @@ int pf_convg_wrw_splits(int imgs, int C, int N, int R, int S, int Ho, int Wo);
 int pf_convg_wrw(const void* dy, const void* x, void* dw, int dtype, int dw_dtype, float* slab, int imgs, int H, int W, int C, int N,
                  int R, int S, int stride, int pad_h, int pad_w, int Ho, int Wo, void* stream);
 
+/* ---- channel-gather convolution: the forward pass of a physically shrunk channel-pruned layer (pf_conv_gather.hip) ----------------
+ * replaces tf.gather(input, nnz, axis=channel) + the smaller convolution of the reference's exported models
+ * (tools/conversion/export_chn_pruned_tflite_model.py:236-276); inference only.
+ *   Y[img][ho][wo][n] = sum_{r,s} sum_{j < Ck} X[img][ho*stride + r - pad_h][wo*stride + s - pad_w][gather[j]] * w[n][r][s][j]
+ * x: NHWC with all C channels; w: KRSC cut along C to [N][R][S][Ck]; gather: int32[Ck], strictly ascending, values in [0, C)
+ * (validated by the caller once, when the model is loaded; an out-of-range entry is skipped, never dereferenced); float32 or bf16
+ * storage (dtype), float32 accumulation, bf16 on the matrix cores; pad_h / pad_w are symmetric pads (positions outside the image
+ * read 0).  Optional epilogue, in this order: + bias[N] (float32), + res[imgs][Ho][Wo][N] (storage type, added before the one
+ * rounding), act(scale_shift[n] * y + scale_shift[N + n]) (a folded inference-mode BatchNorm; `act` is ignored without scale_shift);
+ * all three act on the float32 accumulator, the result is rounded to the storage type once.  C <= 8192.  Deterministic: no atomics, fixed summation order. */
+int pf_conv_gather_fwd(const void* x, const void* w, const int32_t* gather, const float* bias, const void* res,
+                       const float* scale_shift, int act, void* y, int dtype, int imgs, int H, int W, int C, int Ck, int N, int R,
+                       int S, int stride, int pad_h, int pad_w, int Ho, int Wo, void* stream);
+
 /* ---- R x S convolutions with few input channels (ResNet-20 @ CIFAR-10: resnet_model.py:156-199 with 16 / 32 filters) --------------
  * bf16, C % 8 == 0.  pf_im2col gathers Xcol[imgs*Ho*Wo][R*S*C] (taps outside the image: zeros) so that the convolution and its two
  * gradients are 1x1 products on pf_conv1x1_fwd / pf_conv1x1_wrw over Xcol and the [N][R*S*C] view of the KRSC kernel; pf_col2im is

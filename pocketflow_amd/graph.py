@@ -40,6 +40,7 @@ import torch
 import torch.nn.functional as F
 
 from pocketflow_amd import hip
+from pocketflow_amd.hip import check_gather
 from pocketflow_amd.plan import WeightDesc
 from pocketflow_amd.profiling import region
 
@@ -70,6 +71,11 @@ class Variable:
   tensor: Optional[torch.Tensor] = field(default=None, repr=False)  # forward view (leaf; compute copy for 'W')
   store: Optional[object] = field(default=None, repr=False)   # owning VarStore
   master: Optional[torch.Tensor] = field(default=None, repr=False)  # fp32 master view
+  # a physically shrunk Conv2D kernel (Graph.apply_gathers): ref_shape[2] is the number of KEPT input channels, `cin_full` the layer's
+  # input channels, `gather_host` the kept channel indices (int32, strictly ascending), `gather` the same vector on the device
+  cin_full: int = 0
+  gather_host: Optional[np.ndarray] = field(default=None, repr=False)
+  gather: Optional[torch.Tensor] = field(default=None, repr=False)
 
   @property
   def storage_shape(self) -> Tuple[int, ...]:
@@ -372,6 +378,8 @@ class Graph:
     self.tap_dense = False                     # also record Dense layers (input, MatMul output before the bias)
     self.tap_stop = None                       # layer after whose tap the forward pass is abandoned (TapStop)
     self._names: Dict[str, int] = {}
+    self.reinflated: List[str] = []            # shrunk kernels a loader scattered back to full shape (gather_pays)
+    self.kernel_params = self.kernel_params_kept = self.nb_gathered = 0   # set by inference.load_shrunk
 
   # -- naming like tf.layers (conv2d, conv2d_1, ...) ---------------------------------------------
   def unique_name(self, base: str) -> str:
@@ -403,8 +411,40 @@ class Graph:
     self.activation_ops.append(op)
     return op
 
+  def apply_gathers(self, gathers: Dict[str, np.ndarray], values: Optional[Dict[str, np.ndarray]] = None) -> None:
+    """Turn the named Conv2D kernels of a constructed, not yet finalised INFERENCE graph into physically shrunk ones: the artefact of
+    tools/conversion/export_chn_pruned_model.py stores such a kernel as [kh, kw, len(gather), cout] plus the int32 vector of the kept
+    input channels.  The variable's stored shape changes from cin to len(gather), the layer's cin is kept for checks, and the vector
+    goes to the device once (finalize); Conv2D then runs on hip.conv_gather_fwd.  `values`: the kernels that will be loaded, to
+    check their shapes here, where the message can name the variable.  Every rejection is a ValueError that names the variable."""
+    if self.store.finalized:
+      raise RuntimeError('apply_gathers: the graph is already finalised')
+    for name, vec in gathers.items():
+      var = self.store.by_name.get(name)
+      if var is None:
+        raise ValueError('%s: gather for a variable this graph does not have' % name)
+      if var.kind != 'conv':
+        raise ValueError('%s: a gather applies to Conv2D kernels only, this is a %s variable' % (name, var.kind))
+      if var.gather_host is not None:
+        raise ValueError('%s: the kernel already has a gather' % name)
+      kh, kw, cin, cout = var.ref_shape
+      g = check_gather(vec, cin, int(np.asarray(vec).size), what=name)
+      if cin > GATHER_MAX_CIN:
+        raise ValueError('%s: %d input channels, the gather kernel takes at most %d' % (name, cin, GATHER_MAX_CIN))
+      shape = (kh, kw, int(g.size), cout)
+      if values is not None and name in values and tuple(np.shape(values[name])) != shape:
+        raise ValueError('%s: kernel of shape %s does not match its gather of %d kept channels (expected %s)'
+                         % (name, tuple(np.shape(values[name])), g.size, shape))
+      full_init = var.init
+      var.cin_full, var.gather_host, var.ref_shape, var.numel = cin, g, shape, int(np.prod(shape))
+      if full_init is not None:
+        var.init = lambda rng, _f=full_init, _g=g: np.ascontiguousarray(_f(rng)[:, :, _g, :])
+
   def finalize(self, separate_compute: bool = False, seed: int = 42, requires_grad: bool = True) -> None:
     self.store.finalize(self.device, self.compute_dtype, separate_compute, seed, requires_grad)
+    for v in self.store.vars:
+      if v.gather_host is not None and v.gather is None:
+        v.gather = torch.from_numpy(v.gather_host).to(self.device)
     n_act = max(len(self.activation_ops), 1)
     self.act_slots = torch.empty((n_act, 2), dtype=torch.int32, device=self.device)
 
@@ -1406,6 +1446,21 @@ def constant_init(ref_shape, value: float):
   return lambda rng: np.full(ref_shape, value, dtype=np.float32)
 
 
+GATHER_MAX_CIN = 8192             # pf_conv_gather.hip keeps an int16 inverse channel map in LDS
+
+
+def gather_pays(k: int, cin: int, kept: int, cout: int, dtype) -> bool:
+  """Should a loader keep a shrunk k x k convolution with `kept` of `cin` input channels on pf_conv_gather.hip (True), or re-inflate
+  it -- scatter the kept slices back into a zero kernel of full shape -- so that it runs on the dense inference kernels (False)?
+
+  profiles/gather_conv_layers.txt (every ResNet-50 and MobileNet-v1 convolution shape at B = 256, bf16, 0.5 and 0.75 of the channels
+  kept): the gather kernel loses on EVERY layer, dense / gather 0.17 - 0.46 (all convolutions of one ResNet-50 pass: 3.7 ms dense
+  against 14.4 / 16.6 ms gathered; MobileNet 0.80 against 1.9 / 2.2 ms); the one row near 1 is MobileNet's 1 x 1-pixel logits layer
+  (61 us either way).  float32 has not been timed.  So no layer class pays today and every shrunk layer is re-inflated: a shrunk
+  file then runs exactly as fast as the full-shape checkpoint.  (inference.load_shrunk(reinflate='none') still runs the kernel.)"""
+  return False
+
+
 class Conv2D:
   """tf.layers.conv2d / slim.conv2d: NHWC, kernel HWIO (stored KRSC), padding 'SAME' | 'VALID'."""
 
@@ -1430,6 +1485,8 @@ class Conv2D:
       out_bn = None
     if self.graph.taps is not None:
       return _tapped(self, materialize(x), residual)
+    if self.kernel.gather_host is not None:      # a physically shrunk layer (Graph.apply_gathers): inference on pf_conv_gather.hip
+      return self._call_gathered(x, residual, out_bn)
     if fused_conv1x1_ok(x, self):
       lazy = x if isinstance(x, LazyAct) else None
       if lazy is not None:
@@ -1511,6 +1568,46 @@ class Conv2D:
     else:
       y = F.conv2d(x, w, b, stride=self.stride, padding=pad)
     return y if residual is None else y + residual
+
+  def _call_gathered(self, x, residual, out_bn) -> torch.Tensor:
+    """The shrunk layer: reduction over the kept input channels only (hip.conv_gather_fwd), with the epilogues the dense inference
+    kernels have (bias, residual, the consumer's folded inference-mode BN + activation).  Training a shrunk model is out of scope."""
+    var = self.kernel
+    w = var.tensor
+    x = materialize(x)
+    if torch.is_grad_enabled() and (w.requires_grad or x.requires_grad):
+      raise RuntimeError('%s: a shrunk (channel-gathered) convolution runs in inference only: call it under torch.no_grad() '
+                         'on a graph finalised with requires_grad=False' % var.name)
+    if x.dim() != 4 or x.shape[1] != var.cin_full:
+      raise ValueError('%s: input of shape %s, the layer has %d input channels' % (var.name, tuple(x.shape), var.cin_full))
+    sym = (0, 0)                                 # 'VALID', and 'SAME' with a 1x1 kernel
+    if isinstance(self.padding, int):
+      sym = (self.padding, self.padding)
+    elif self.padding == 'SAME' and self.k > 1:
+      ph = _same_pads(x.shape[2], self.k, self.stride)
+      pw = _same_pads(x.shape[3], self.k, self.stride)
+      if ph[0] == ph[1] and pw[0] == pw[1]:
+        sym = (ph[0], pw[0])
+      else:
+        x = F.pad(x, (pw[0], pw[1], ph[0], ph[1]))
+    x = _nhwc(x)
+    B, C, H, Wd = x.shape
+    N = w.shape[0]
+    Ho = (H + 2 * sym[0] - self.k) // self.stride + 1
+    Wo = (Wd + 2 * sym[1] - self.k) // self.stride + 1
+    wk = w.detach().permute(0, 2, 3, 1)
+    if not wk.is_contiguous() or wk.dtype != x.dtype:
+      wk = wk.contiguous().to(x.dtype)
+    y = torch.empty((B, N, Ho, Wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    bias = None if self.bias is None else self.bias.tensor.detach().float().contiguous()
+    res = None if residual is None else _nhwc(residual).to(x.dtype)
+    ss = out_bn._eval_scale_shift(y) if out_bn is not None else None
+    with region('conv_gather_fwd', float((x.numel() + y.numel() * (2 if res is not None else 1)) * x.element_size())):
+      hip.conv_gather_fwd(x, wk, var.gather, y, B, H, Wd, C, N, self.k, self.k, self.stride, sym[0], sym[1], Ho, Wo,
+                          bias=bias, residual=res, scale_shift=ss, act=out_bn.act if out_bn is not None else None)
+    if out_bn is not None:
+      y._pf_bn_done = out_bn
+    return y
 
   def plain(self, x: torch.Tensor) -> torch.Tensor:
     """The convolution alone on a materialised tensor (tracing / channel pruning)."""

@@ -53,6 +53,7 @@ SYMBOLS = [
     'pf_conv1x1_fwd_affine', 'pf_conv2d_fwd_affine', 'pf_conv2d_bwd_data_strided_stats_groups',
     'pf_conv2d_bwd_data_strided_bnstats',
     'pf_cpr_gather', 'pf_cpr_gram_ws', 'pf_cpr_gram', 'pf_cpr_ista', 'pf_cpr_lstsq_splits', 'pf_cpr_lstsq_step', 'pf_cpr_lstsq_resid',
+    'pf_conv_gather_fwd',
 ]
 
 
@@ -654,6 +655,42 @@ def convg_fwd(X, Wk, bias, Y, B: int, H: int, Wd: int, C: int, N: int, R: int, S
   _check(_lib.pf_convg_fwd(_ptr(X), _ptr(Wk), _ptr(bias), _ptr(Y), c_int(dtype_code(X)), c_int(B), c_int(H), c_int(Wd), c_int(C),
                            c_int(N), c_int(R), c_int(S), c_int(stride), c_int(pad_h), c_int(pad_w), c_int(Ho), c_int(Wo), _ptr(slab),
                            c_int64(slab.numel() if slab is not None else 0), _stream()), 'pf_convg_fwd')
+
+
+def check_gather(gather, C: int, Ck: int, what: str = 'gather') -> np.ndarray:
+  """The host-side validation of a gather vector, done ONCE when a shrunk model is loaded (the kernel trusts it): int32[Ck],
+  strictly ascending, every value in [0, C).  Returns the vector as a contiguous int32 array."""
+  g = np.asarray(gather)
+  if g.ndim != 1 or g.size != Ck or not np.issubdtype(g.dtype, np.integer):
+    raise ValueError('%s: expected an integer vector of %d kept channels, got shape %s dtype %s' % (what, Ck, g.shape, g.dtype))
+  g = g.astype(np.int64)
+  if g.size == 0 or g[0] < 0 or g[-1] >= C or np.any(np.diff(g) <= 0):
+    raise ValueError('%s: kept channels must be strictly ascending and lie in [0, %d)' % (what, C))
+  return np.ascontiguousarray(g.astype(np.int32))
+
+
+def conv_gather_fwd(X, Wk, gather, Y, B: int, H: int, Wd: int, C: int, N: int, R: int, S: int, stride: int, pad_h: int, pad_w: int,
+                    Ho: int, Wo: int, bias=None, residual=None, scale_shift=None, act=None) -> None:
+  """Y[B][Ho][Wo][N] = conv(X[B][H][Wd][C][..., gather], Wk[N][R][S][Ck]) (+ bias) (+ residual), then act(scale * y + shift) when
+  scale_shift ([2][N] float32) is given.  `gather`: int32 device vector that passed check_gather() when the model was loaded."""
+  _dev(X)
+  Ck = int(gather.numel())
+  if Wk.dtype != X.dtype or Y.dtype != X.dtype or (residual is not None and residual.dtype != X.dtype):
+    raise TypeError('conv_gather_fwd: X / Wk / Y / residual share one dtype')
+  if gather.dtype != torch.int32 or (bias is not None and bias.dtype != torch.float32) or (
+      scale_shift is not None and scale_shift.dtype != torch.float32):
+    raise TypeError('conv_gather_fwd: gather is int32, bias and scale_shift are float32')
+  if X.numel() != B * H * Wd * C or Wk.numel() != N * R * S * Ck or Y.numel() != B * Ho * Wo * N or not 1 <= Ck <= C or (
+      residual is not None and residual.numel() != Y.numel()) or (bias is not None and bias.numel() != N) or (
+      scale_shift is not None and scale_shift.numel() != 2 * N):
+    raise ValueError('conv_gather_fwd: operand sizes do not match B=%d H=%d W=%d C=%d Ck=%d N=%d R=%d S=%d Ho=%d Wo=%d'
+                     % (B, H, Wd, C, Ck, N, R, S, Ho, Wo))
+  if (Ho - 1) * stride + R - 2 * pad_h > H or (Wo - 1) * stride + S - 2 * pad_w > Wd:
+    raise ValueError('conv_gather_fwd: the output extends beyond the symmetrically padded input')
+  _check(_lib.pf_conv_gather_fwd(_ptr(X), _ptr(Wk), _ptr(gather), _ptr(bias), _ptr(residual), _ptr(scale_shift),
+                                 c_int(ACT_CODES[act]), _ptr(Y), c_int(dtype_code(X)), c_int(B), c_int(H), c_int(Wd), c_int(C),
+                                 c_int(Ck), c_int(N), c_int(R), c_int(S), c_int(stride), c_int(pad_h), c_int(pad_w), c_int(Ho),
+                                 c_int(Wo), _stream()), 'pf_conv_gather_fwd')
 
 
 def convg_bwd_data(dY, Wk, dX, B: int, H: int, Wd: int, C: int, N: int, R: int, S: int, stride: int, pad_h: int, pad_w: int,

@@ -1,0 +1,96 @@
+"""Measure the inference time of a model on the device (reference tools/benchmark/calc_inference_time.py, which times *.pb /
+*.tflite files): here the model is a `model_shrunk.npz` written by tools/conversion/export_chn_pruned_model.py or a checkpoint
+directory, loaded with pocketflow_amd.inference.load_shrunk.
+
+    python -m pocketflow_amd.tools.conversion.export_chn_pruned_model --model_dir ./models --enbl_fake_prune --fake_prune_ratio 0.5
+    python -m pocketflow_amd.tools.benchmark.calc_inference_time --net resnet_at_ilsvrc12 --resnet_size 50 --batch_size 256 \\
+        --compute_dtype bfloat16 --model_file ./models/model_shrunk.npz                      # shrunk layers on the gather kernel
+    python -m pocketflow_amd.tools.benchmark.calc_inference_time ... --model_file ./models/model_shrunk.npz --reinflate all
+                                                           # the same weights in full shape (zero channels): the baseline
+
+Flags: `--model_file`, `--nb_repts_warmup` (100), `--nb_repts` (100) as in the reference; `--net` names the ModelHelper module under
+pocketflow_amd.nets, whose own flags (`--resnet_size`, `--mobilenet_depth_mult`, `--nb_classes`, `--image_size` ...) and
+`--compute_dtype` apply.  `--batch_size` is the datasets' flag of that name (the reference tool's own `batch_size` defaults to 1;
+here the default is the dataset's training batch, 128 for CIFAR-10 and 64 for ILSVRC-12), because one registry holds both.
+`--reinflate auto|none|all`: see load_shrunk.  The input is a batch of zeros, like the reference's; it is put on the device and
+converted once, outside the timed window.  The window is a host clock around `nb_repts` forward passes that ends in a device
+synchronise.  Prints ms per batch and per image; `--json` prints one JSON line with those, the number of gathered layers and the
+kept share of convolution-kernel parameters.
+"""
+from __future__ import annotations
+
+import importlib
+import json
+import logging
+import sys
+from timeit import default_timer as timer
+
+import numpy as np
+import torch
+
+from pocketflow_amd.flags import FLAGS, flags
+
+flags.DEFINE_string('model_file', None, 'model file path: a model_shrunk.npz or a checkpoint directory')
+flags.DEFINE_integer('nb_repts_warmup', 100, '# of repeated runs for warm-up')
+flags.DEFINE_integer('nb_repts', 100, '# of repeated runs for elapsed time measurement')
+flags.DEFINE_string('net', 'resnet_at_ilsvrc12', 'ModelHelper module under pocketflow_amd.nets')
+flags.DEFINE_string('reinflate', 'auto', "'auto': re-inflate the layers graph.gather_pays rejects | 'none' | 'all' (full-shape baseline)")
+flags.DEFINE_boolean('json', False, 'print one JSON result line')
+
+log = logging.getLogger('pocketflow_amd')
+
+
+def _net_of(argv) -> str:
+  """The value of --net, read before parsing: the net's module defines flags the parser must know."""
+  for i, a in enumerate(argv):
+    if a.startswith('--net='):
+      return a.split('=', 1)[1]
+    if a == '--net' and i + 1 < len(argv):
+      return argv[i + 1]
+  return 'resnet_at_ilsvrc12'
+
+
+def measure(forward_eval, graph, x, nb_warmup: int, nb_repts: int) -> float:
+  """Seconds per forward pass: host clock around nb_repts passes, closed by a device synchronise."""
+  sync = (lambda: torch.cuda.synchronize()) if x.is_cuda else (lambda: None)
+  with torch.no_grad(), graph.as_default():
+    for _ in range(nb_warmup):
+      forward_eval(x)
+    sync()
+    beg = timer()
+    for _ in range(nb_repts):
+      forward_eval(x)
+    sync()
+    return (timer() - beg) / max(nb_repts, 1)
+
+
+def main(argv=None) -> int:
+  argv = list(sys.argv[1:] if argv is None else argv)
+  from pocketflow_amd.learners import abstract_learner as AL
+  from pocketflow_amd.graph import to_device_images
+  from pocketflow_amd.inference import load_shrunk
+  mod = importlib.import_module('pocketflow_amd.nets.' + _net_of(argv))
+  FLAGS.parse(argv)
+  logging.basicConfig(level=logging.INFO)
+  if FLAGS.model_file is None:
+    raise ValueError('<FLAGS.model_file> must not be None')
+  device = AL.require_gpu()
+  mh = mod.ModelHelper()
+  graph, _ = load_shrunk(mh, FLAGS.model_file, device, AL.compute_dtype(), reinflate=FLAGS.reinflate)
+  batch = int(mh.dataset_train.batch_size)
+  x = to_device_images(np.zeros((batch,) + tuple(mh.dataset_train.image_shape), dtype=np.float32), graph)
+  sec = measure(mh.forward_eval, graph, x, FLAGS.nb_repts_warmup, FLAGS.nb_repts)
+  rslt = {'model_file': FLAGS.model_file, 'net': FLAGS.net, 'compute_dtype': FLAGS.compute_dtype, 'batch_size': batch,
+          'nb_repts_warmup': FLAGS.nb_repts_warmup, 'nb_repts': FLAGS.nb_repts, 'reinflate': FLAGS.reinflate,
+          'ms_per_batch': sec * 1e3, 'ms_per_image': sec * 1e3 / batch, 'nb_gathered_layers': graph.nb_gathered,
+          'nb_reinflated_layers': len(graph.reinflated),
+          'kernel_params_kept_share': graph.kernel_params_kept / max(graph.kernel_params, 1)}
+  print('time consumption of %s: %.3f ms per batch of %d, %.4f ms per image (%d gathered layers, %d re-inflated)'
+        % (FLAGS.model_file, rslt['ms_per_batch'], batch, rslt['ms_per_image'], graph.nb_gathered, len(graph.reinflated)))
+  if FLAGS.json:
+    print(json.dumps(rslt))
+  return 0
+
+
+if __name__ == '__main__':
+  sys.exit(main())
