@@ -852,6 +852,57 @@ def _bn_backward(dq, x, scale_shift, mean_invstd, act, graph, rows, C, addend=No
   return (dx, None, None) if direct else (dx, dgamma, dbeta)
 
 
+def _filter_grad(graph, w, w_var, keep, name, nbytes, launch):
+  """The filter gradient of the convolution kernel `w` (logical [N][C][R][S] over KRSC memory; depthwise [C][1][k][k]), computed by
+  `launch(target, scratch)`: `target` is the gradient in STORAGE layout ([N][R][S][C]), `scratch(n)` the float32 split workspace of
+  the queue the launch runs on.  The target is the leaf's gradient view inside the flat gradient buffer where there is one: written
+  directly (each kernel is used once per step; the optimiser zeroes the buffer), no accumulation kernel.  Autograd then sees no
+  gradient for this leaf (None is returned), so it is reported here, on the launch's queue.  Any other `w` -- no gradient yet, or one
+  that is not laid out in storage order -- gets a fresh tensor, returned in the logical layout for autograd to accumulate.  (`w.grad`
+  always has the shape and dtype of `w`, torch refuses any other: what decides is the layout.)  `keep`: every tensor the launch
+  reads, referenced until the side queue is joined (WrwSide)."""
+  gw = getattr(w, 'grad', None)
+  direct = gw is not None and gw.shape == w.shape and gw.dtype == w.dtype and gw.permute(0, 2, 3, 1).is_contiguous()
+  target = (gw.permute(0, 2, 3, 1) if direct
+            else torch.empty((w.shape[0], w.shape[2], w.shape[3], w.shape[1]), dtype=w.dtype, device=w.device))
+  with _wrw_queue(graph, direct, *keep) as scratch, region(name, nbytes):
+    launch(target, scratch)
+    if direct:
+      graph.store.notify_grad(w_var)
+  return None if direct else target.permute(0, 3, 1, 2)
+
+
+def _bwd_data_weight(graph, w_var, w):
+  """The kernel in backward-data layout, W'[c][R-1-r][S-1-s][n] = W[n][r][s][c]: a view of the store's transposed buffer (one launch
+  for all kernels of the step) when `w` is that variable's tensor, else a copy made here."""
+  if USE_SEG_TRANSPOSE and w_var is not None and w_var.store is graph.store and w_var.tensor is w:
+    return graph.store.transposed(w_var)
+  return w.detach().permute(0, 2, 3, 1).flip(1, 2).permute(3, 1, 2, 0).contiguous()
+
+
+def _krsc(w, dtype):
+  """The kernel `w` (logical [N][C][R][S]) as a contiguous [N][R][S][C] tensor of `dtype`: a view where it is stored that way."""
+  wk = w.detach().permute(0, 2, 3, 1)
+  if not wk.is_contiguous() or wk.dtype != dtype:
+    wk = wk.contiguous().to(dtype)
+  return wk
+
+
+def _out_size(size: int, k: int, stride: int, pad_total: int) -> int:
+  """Output pixels along one axis of a k-wide window moved by `stride` over `size` pixels padded by `pad_total` (both ends together)."""
+  return (size + pad_total - k) // stride + 1
+
+
+def _apply_with_stats(fn, *args):
+  """`fn.apply(*args, box)` for the convolutions whose forward kernel leaves the BN statistics of its output: apply() wraps the
+  result in a new tensor object, so forward hands `_pf_stats` over in `box` and it is put back on the tensor here."""
+  box = []
+  y = fn.apply(*args, box)
+  if box[0] is not None:
+    y._pf_stats = box[0]
+  return y
+
+
 def _conv1x1_geom(x_shape, stride):
   """(M, geom) of a 1x1 convolution over a logical-NCHW / physical-NHWC input."""
   n, _, h, w = x_shape
@@ -892,7 +943,7 @@ class _FusedConv1x1(torch.autograd.Function):
   """y = conv1x1(Q(x), W) [+ residual], Q = the producer BN's normalise/act/fake-quant (prologue)."""
 
   @staticmethod
-  def forward(ctx, x, w, residual, lazy, want_stats, stride, graph, box, w_var=None):
+  def forward(ctx, x, w, residual, lazy, want_stats, stride, graph, w_var, box):
     w2d = w.detach().permute(0, 2, 3, 1).reshape(w.shape[0], w.shape[1])      # [N][K] (KRSC, R=S=1)
     res = _nhwc(residual) if residual is not None else None
     y = _run_conv1x1(x, w2d, lazy, res, want_stats, stride)
@@ -916,27 +967,15 @@ class _FusedConv1x1(torch.autograd.Function):
     dx = dw = None
     if ctx.needs_input_grad[1]:
       S = hip.conv1x1_wrw_splits(M, N, K)
-      # the kernel's gradient view inside the flat gradient buffer ([N][1][1][K] memory = [N][K]): written
-      # directly (each kernel is used once per step; the optimiser zeroes the buffer), no accumulation kernel
-      gw = getattr(ctx.w_leaf, 'grad', None)
-      direct = (gw is not None and gw.dtype == w2d.dtype and gw.shape == ctx.w_leaf.shape
-                and gw.permute(0, 2, 3, 1).is_contiguous())
-      dw2d = gw.permute(0, 2, 3, 1).view(N, K) if direct else torch.empty((N, K), dtype=w2d.dtype, device=x.device)
+
+      def wrw(dwk, scratch):                     # dwk: [N][1][1][K] memory = [N][K]
+        hip.conv1x1_wrw(dy, x, dwk.view(N, K), scratch((S + 32) * N * K), M, N, K, scale_shift=ss, act=act,
+                        slot=lazy.slot if quant else None, bits=lazy.bits if quant else 8, geom=geom)
       # (everything the launch reads stays referenced until the join: the producer BN's constants belong to ITS autograd node, which
       # runs -- and frees them -- on the main stream right after this function returns)
-      with _wrw_queue(graph, direct, dy, x, w2d, ss, lazy) as scratch, region('conv1x1_wrw', float((M * K + M * N) * 2)):
-        ws = scratch((S + 32) * N * K)
-        hip.conv1x1_wrw(dy, x, dw2d, ws, M, N, K, scale_shift=ss, act=act, slot=lazy.slot if quant else None,
-                        bits=lazy.bits if quant else 8, geom=geom)
-        if direct:
-          graph.store.notify_grad(ctx.w_var)     # autograd sees no gradient for this leaf: report it ourselves (on the launch's queue)
-      dw = None if direct else dw2d.view(N, 1, 1, K).permute(0, 3, 1, 2)       # logical OIHW over KRSC memory
+      dw = _filter_grad(graph, ctx.w_leaf, ctx.w_var, (dy, x, w2d, ss, lazy), 'conv1x1_wrw', float((M * K + M * N) * 2), wrw)
     if ctx.needs_input_grad[0]:
-      wv = getattr(ctx, 'w_var', None)
-      if USE_SEG_TRANSPOSE and wv is not None and wv.store is graph.store and wv.tensor is ctx.w_leaf:
-        wt = graph.store.transposed(wv).view(K, N)                             # [K][N], one launch for all kernels
-      else:
-        wt = w2d.t().contiguous()
+      wt = _bwd_data_weight(graph, ctx.w_var, ctx.w_leaf).view(K, N)           # [K][N]
       if geom is None:
         dx = torch.empty_like(x)
       else:
@@ -997,8 +1036,7 @@ def _run_conv2d(x, w_krsc, stride, pad, want_stats, out_bn=None):
   """x: logical NCHW / physical NHWC bf16, w_krsc: contiguous [N][R][S][C] bf16."""
   B, C, H, W = x.shape
   N, R, S, _ = w_krsc.shape
-  Ho = (H + 2 * pad[0] - R) // stride + 1
-  Wo = (W + 2 * pad[1] - S) // stride + 1
+  Ho, Wo = _out_size(H, R, stride, 2 * pad[0]), _out_size(W, S, stride, 2 * pad[1])
   y = torch.empty((B, N, Ho, Wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
   M = B * Ho * Wo
   if out_bn is not None:                         # the consumer's inference-mode BN + activation in the epilogue (pf_conv2d_fwd_affine)
@@ -1026,7 +1064,7 @@ class _Conv2dIgemm(torch.autograd.Function):
   switches' other side and geometries outside the kernels' limits (channel counts, 31-bit offsets)."""
 
   @staticmethod
-  def forward(ctx, x, w, stride, pad, want_stats, graph, box, bn_box, w_var=None):
+  def forward(ctx, x, w, stride, pad, want_stats, graph, bn_box, w_var, box):
     ctx.w_var = w_var
     w_krsc = w.detach().permute(0, 2, 3, 1)              # physical layout of the kernel: contiguous [N][R][S][C]
     y = _run_conv2d(x, w_krsc, stride, pad, want_stats)
@@ -1041,93 +1079,62 @@ class _Conv2dIgemm(torch.autograd.Function):
     stride, pad, graph, bn_box = ctx.meta
     dy = _nhwc(dy)
     dx = dw = None
+    N, C, R, S = w.shape
+    B, _, H, W = x.shape
+    Ho, Wo = dy.shape[2], dy.shape[3]
     if ctx.needs_input_grad[1]:
-      N_, C_, R_, S_ = w.shape
-      B_, _, H_, W_ = x.shape
-      Ho_, Wo_ = dy.shape[2], dy.shape[3]
-      M_ = B_ * Ho_ * Wo_
       # C = 64: the [64 x 64] tile per tap is too small to feed the matrix cores (measured 256 vs 168 us against MIOpen on
       # the 56x56 layer, tools/gpu/wrw_bench.py); from C = 128 up the shared-tile kernel is on par or ahead
-      splits = hip.conv2d_wrw_splits(M_, N_, C_, R_ * S_) if (OWN_CONV2D_WRW and C_ >= OWN_CONV2D_WRW_MIN_C) else 0
-      with region('conv2d_wrw', float((x.numel() + dy.numel()) * 2)):
-        if splits > 0:
-          # the kernel's gradient view inside the flat gradient buffer (KRSC memory): written directly, like the 1x1 path
-          gw = getattr(w, 'grad', None)
-          direct = (gw is not None and gw.shape == w.shape and gw.permute(0, 2, 3, 1).is_contiguous()
-                    and gw.dtype in (torch.float32, torch.bfloat16))
-          dwk = gw.permute(0, 2, 3, 1) if direct else torch.empty((N_, R_, S_, C_), dtype=w.dtype, device=x.device)
-          with _wrw_queue(graph, direct, dy, x) as scratch:
-            ws = scratch((splits + 32) * N_ * R_ * S_ * C_)
-            hip.conv2d_wrw(dy, x, dwk, ws, B_, H_, W_, C_, N_, R_, S_, stride, pad[0], pad[1], Ho_, Wo_)
-            if direct:
-              graph.store.notify_grad(ctx.w_var)
-          if not direct:
-            dw = dwk.permute(0, 3, 1, 2)
-        elif OWN_CONV2D_WRW and OWN_CONV_GENERIC and x.is_cuda and dy.dtype == x.dtype and w.dtype == x.dtype:
-          # fewer than 2 048 output pixels (the 64 x 64 test networks): too few steps for the pixel-split MFMA kernels -- the general
-          # kernel (round 6; MIOpen until then: VERDICT r5 weak #1 "those parity lines partly measure the library")
-          gs = hip.convg_wrw_splits(B_, C_, N_, R_, S_, Ho_, Wo_)
-          dwk = torch.empty((N_, R_, S_, C_), dtype=w.dtype, device=x.device)
-          hip.convg_wrw(dy, x, dwk, graph.scratch(gs * N_ * R_ * S_ * C_), B_, H_, W_, C_, N_, R_, S_, stride, pad[0], pad[1], Ho_, Wo_)
-          dw = dwk.permute(0, 3, 1, 2)
-        else:
+      splits = hip.conv2d_wrw_splits(B * Ho * Wo, N, C, R * S) if (OWN_CONV2D_WRW and C >= OWN_CONV2D_WRW_MIN_C) else 0
+      nbytes = float((x.numel() + dy.numel()) * 2)
+      if splits > 0:
+        def wrw(dwk, scratch):
+          hip.conv2d_wrw(dy, x, dwk, scratch((splits + 32) * N * R * S * C), B, H, W, C, N, R, S, stride, pad[0], pad[1], Ho, Wo)
+        dw = _filter_grad(graph, w, ctx.w_var, (dy, x), 'conv2d_wrw', nbytes, wrw)
+      elif OWN_CONV2D_WRW and OWN_CONV_GENERIC and x.is_cuda and dy.dtype == x.dtype and w.dtype == x.dtype:
+        # fewer than 2 048 output pixels (the 64 x 64 test networks): too few steps for the pixel-split MFMA kernels -- the general
+        # kernel (round 6; MIOpen until then: VERDICT r5 weak #1 "those parity lines partly measure the library")
+        gs = hip.convg_wrw_splits(B, C, N, R, S, Ho, Wo)
+        dwk = torch.empty((N, R, S, C), dtype=w.dtype, device=x.device)
+        with region('conv2d_wrw', nbytes):
+          hip.convg_wrw(dy, x, dwk, graph.scratch(gs * N * R * S * C), B, H, W, C, N, R, S, stride, pad[0], pad[1], Ho, Wo)
+        dw = dwk.permute(0, 3, 1, 2)
+      else:
+        with region('conv2d_wrw', nbytes):
           dw = torch.ops.aten.convolution_backward(dy, x, w.detach(), None, [stride, stride], list(pad), [1, 1], False,
                                                    [0, 0], 1, [False, True, False])[1]
     if ctx.needs_input_grad[0]:
-      N, C, R, S = w.shape
       # backward-data = the same kernel with the roles of C and N swapped: its contraction runs over N in steps of 64
-      if stride == 1 and N % 64 == 0 and C % 8 == 0 and igemm_limits_ok(dy.numel(), w.numel(), R * S):
-        B, _, H, W = x.shape
-        wv = ctx.w_var
-        if USE_SEG_TRANSPOSE and wv is not None and wv.store is graph.store and wv.tensor is w:
-          wb = graph.store.transposed(wv)                                                 # [C][R][S][N]
-        else:
-          wb = w.detach().permute(0, 2, 3, 1).flip(1, 2).permute(3, 1, 2, 0).contiguous()
+      mfma = N % 64 == 0 and C % 8 == 0 and igemm_limits_ok(dy.numel(), w.numel(), R * S)
+      # strided backward-data by output-parity classes on the implicit-GEMM kernel (pf_conv2d_bwd_data_strided; MIOpen until round 4)
+      by_classes = (OWN_CONV2D_BWD_STRIDED and stride > 1 and H % stride == 0 and W % stride == 0 and R >= stride and S >= stride
+                    and dy.dtype == torch.bfloat16)
+      if mfma and (stride == 1 or by_classes):
+        wb = _bwd_data_weight(graph, ctx.w_var, w)                                        # [C][R][S][N], flipped
         dx = torch.empty_like(x)
-        M = B * H * W
+        # the BN-backward sums of x's producer BN from this launch's epilogue (stride 1: bn2 of a block; by classes: bn2 in front of a
+        # stage's strided 3x3, round 6)
         fuse = (FUSE_BN_BWD_STATS and bn_box is not None and bn_box.get('n_consumers') == 1
                 and bn_box.get('act') in ('Relu', 'Relu6') and bn_box['x'].shape == x.shape)
         with region('conv2d_bwd_data', float((dy.numel() + x.numel() * (2 if fuse else 1)) * 2)):
+          bn = {}
           if fuse:
-            G = hip.conv2d_stats_groups(M, C, geom=(B, H, W, N, C, R, S, 1, R - 1 - pad[0], S - 1 - pad[1], H, W))
+            G = (hip.conv2d_stats_groups(B * H * W, C, geom=(B, H, W, N, C, R, S, 1, R - 1 - pad[0], S - 1 - pad[1], H, W))
+                 if stride == 1 else hip.conv2d_bwd_data_strided_stats_groups(B, H, W, C, stride))
             partial = torch.empty((G, 2, C), dtype=torch.float32, device=x.device)
-            hip.conv2d_fwd(dy, wb, dx, B, H, W, N, C, R, S, 1, R - 1 - pad[0], S - 1 - pad[1], H, W, partial=partial,
-                           bn_x=bn_box['x'], bn_scale_shift=bn_box['scale_shift'], bn_mean_invstd=bn_box['mean_invstd'],
-                           bn_act=bn_box['act'])
-            bn_box['bwd_stats'] = (partial, G, dx.data_ptr())
+            bn = dict(partial=partial, bn_x=bn_box['x'], bn_scale_shift=bn_box['scale_shift'], bn_mean_invstd=bn_box['mean_invstd'],
+                      bn_act=bn_box['act'])
+          if stride == 1:
+            hip.conv2d_fwd(dy, wb, dx, B, H, W, N, C, R, S, 1, R - 1 - pad[0], S - 1 - pad[1], H, W, **bn)
           else:
-            hip.conv2d_fwd(dy, wb, dx, B, H, W, N, C, R, S, 1, R - 1 - pad[0], S - 1 - pad[1], H, W)
-      elif (OWN_CONV2D_BWD_STRIDED and stride > 1 and N % 64 == 0 and C % 8 == 0 and x.shape[2] % stride == 0 and x.shape[3] % stride == 0
-            and R >= stride and S >= stride and dy.dtype == torch.bfloat16 and igemm_limits_ok(dy.numel(), w.numel(), R * S)):
-        # strided backward-data by output-parity classes on the implicit-GEMM kernel (pf_conv2d_bwd_data_strided; MIOpen until round 4)
-        B, _, H, W = x.shape
-        wv = ctx.w_var
-        if USE_SEG_TRANSPOSE and wv is not None and wv.store is graph.store and wv.tensor is w:
-          wb = graph.store.transposed(wv)                                                 # [C][R][S][N], flipped
-        else:
-          wb = w.detach().permute(0, 2, 3, 1).flip(1, 2).permute(3, 1, 2, 0).contiguous()
-        dx = torch.empty_like(x)
-        fuse = (FUSE_BN_BWD_STATS and bn_box is not None and bn_box.get('n_consumers') == 1
-                and bn_box.get('act') in ('Relu', 'Relu6') and bn_box['x'].shape == x.shape)
-        with region('conv2d_bwd_data', float((dy.numel() + x.numel() * (2 if fuse else 1)) * 2)):
-          if fuse:                                 # bn2 in front of a stage's strided 3x3: its backward sums from the class launches (round 6)
-            G = hip.conv2d_bwd_data_strided_stats_groups(B, H, W, C, stride)
-            partial = torch.empty((G, 2, C), dtype=torch.float32, device=x.device)
-            hip.conv2d_bwd_data_strided(dy, wb, dx, B, H, W, C, N, R, S, stride, pad[0], pad[1], dy.shape[2], dy.shape[3],
-                                        partial=partial, bn_x=bn_box['x'], bn_scale_shift=bn_box['scale_shift'],
-                                        bn_mean_invstd=bn_box['mean_invstd'], bn_act=bn_box['act'])
+            hip.conv2d_bwd_data_strided(dy, wb, dx, B, H, W, C, N, R, S, stride, pad[0], pad[1], Ho, Wo, **bn)
+          if fuse:
             bn_box['bwd_stats'] = (partial, G, dx.data_ptr())
-          else:
-            hip.conv2d_bwd_data_strided(dy, wb, dx, B, H, W, C, N, R, S, stride, pad[0], pad[1], dy.shape[2], dy.shape[3])
       elif OWN_CONV2D and OWN_CONV_GENERIC and x.is_cuda and dy.dtype == x.dtype and w.dtype == x.dtype:
         # geometries outside the MFMA kernels' limits (odd strided sizes, channel counts, 31-bit offsets): the general kernel
-        B, _, H, W = x.shape
-        wk = w.detach().permute(0, 2, 3, 1)
-        if not wk.is_contiguous():
-          wk = wk.contiguous()
         dx = torch.empty_like(x)
         with region('conv2d_bwd_data', float((dy.numel() + x.numel()) * 2)):
-          hip.convg_bwd_data(dy, wk, dx, B, H, W, C, N, R, S, stride, pad[0], pad[1], dy.shape[2], dy.shape[3],
+          hip.convg_bwd_data(dy, _krsc(w, x.dtype), dx, B, H, W, C, N, R, S, stride, pad[0], pad[1], Ho, Wo,
                              slab=_convg_slab(graph, x.dtype, B * H * W, C, R * S * N))
       else:
         with region('conv2d_bwd_data', float((dy.numel() + x.numel()) * 2)):
@@ -1146,9 +1153,7 @@ class _ConvGeneric(torch.autograd.Function):
     B, C, H, Wd = x.shape
     N, _, R, S = w.shape
     Ho, Wo = out_hw
-    wk = w.detach().permute(0, 2, 3, 1)
-    if not wk.is_contiguous() or wk.dtype != x.dtype:
-      wk = wk.contiguous().to(x.dtype)
+    wk = _krsc(w, x.dtype)
     y = torch.empty((B, N, Ho, Wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     bf = None if bias is None else bias.detach().float().contiguous()
     with region('convg_fwd', float((x.numel() + y.numel()) * x.element_size())):
@@ -1171,9 +1176,7 @@ class _ConvGeneric(torch.autograd.Function):
       dy = dy.to(x.dtype)
     dx = dw = db = None
     if ctx.needs_input_grad[0]:
-      wk = w.detach().permute(0, 2, 3, 1)
-      if not wk.is_contiguous() or wk.dtype != x.dtype:
-        wk = wk.contiguous().to(x.dtype)
+      wk = _krsc(w, x.dtype)
       dx = torch.empty_like(x, memory_format=torch.channels_last)
       with region('convg_bwd_data', float((dy.numel() + dx.numel()) * x.element_size())):
         hip.convg_bwd_data(dy, wk, dx, B, H, Wd, C, N, R, S, stride, pad[0], pad[1], Ho, Wo,
@@ -1251,16 +1254,11 @@ class _ConvIm2col(torch.autograd.Function):
     if ctx.needs_input_grad[1]:
       xcol = torch.empty((M, K), dtype=x.dtype, device=x.device)
       hip.im2col(x, xcol, B, H, Wd, C, R, S, stride, pad[0], pad[1], Ho, Wo)
-      gw = getattr(w, 'grad', None)
-      direct = (gw is not None and gw.shape == w.shape and gw.permute(0, 2, 3, 1).is_contiguous() and gw.dtype == w.dtype)
-      dw2d = gw.permute(0, 2, 3, 1).reshape(N, K) if direct else torch.empty((N, K), dtype=w.dtype, device=x.device)
       splits = hip.conv1x1_wrw_splits(M, N, K)
-      with _wrw_queue(graph, direct, dy, xcol) as scratch, region('conv_im2col_wrw', float((M * K + M * N) * 2)):
-        hip.conv1x1_wrw(dy, xcol, dw2d, scratch((splits + 32) * N * K), M, N, K)
-        if direct:
-          graph.store.notify_grad(w_var)
-      if not direct:
-        dw = dw2d.view(N, R, S, C).permute(0, 3, 1, 2)
+
+      def wrw(dwk, scratch):                     # dwk: [N][R][S][C] memory = [N][K]
+        hip.conv1x1_wrw(dy, xcol, dwk.view(N, K), scratch((splits + 32) * N * K), M, N, K)
+      dw = _filter_grad(graph, w, w_var, (dy, xcol), 'conv_im2col_wrw', float((M * K + M * N) * 2), wrw)
     if ctx.needs_input_grad[0]:
       dxcol = torch.empty((M, K), dtype=x.dtype, device=x.device)
       dx = torch.empty_like(x)
@@ -1274,8 +1272,17 @@ def im2col_conv_ok(x, conv, pad) -> bool:
   """R x S convolutions the implicit-GEMM kernel does not take for their channel count (cin % 64 != 0) but the 1x1 kernels do."""
   kh, kw, cin, cout = conv.kernel.ref_shape
   return (OWN_CONV_IM2COL and conv.k > 1 and conv.bias is None and isinstance(x, torch.Tensor) and fusable_tensor(x) and x.dim() == 4
-          and cin % 8 == 0 and cin % 64 != 0 and cout % 8 == 0 and pad is not None and conv.graph.fuse_conv1x1
+          and cin % 8 == 0 and cin % 64 != 0 and cout % 8 == 0 and conv.graph.fuse_conv1x1
           and x.shape[0] * x.shape[2] * x.shape[3] * kh * kw * cin < (1 << 31))
+
+
+def _run_stem(x, w):
+  """x: the image batch, logical NCHW / physical NHWC bf16; w: logical [64][3][7][7] over KRSC memory."""
+  B, _, H, Wd = x.shape
+  y = torch.empty((B, w.shape[0], H // 2, Wd // 2), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+  with region('conv_stem_fwd', float((x.numel() + y.numel()) * 2)):
+    hip.conv_stem_fwd(x, w.detach().permute(0, 2, 3, 1), y, B, H, Wd)
+  return y
 
 
 class _StemConv(torch.autograd.Function):
@@ -1284,13 +1291,9 @@ class _StemConv(torch.autograd.Function):
 
   @staticmethod
   def forward(ctx, x, w, graph, w_var):
-    B, _, H, Wd = x.shape
-    y = torch.empty((B, w.shape[0], H // 2, Wd // 2), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-    with region('conv_stem_fwd', float((x.numel() + y.numel()) * 2)):
-      hip.conv_stem_fwd(x, w.detach().permute(0, 2, 3, 1), y, B, H, Wd)
     ctx.save_for_backward(x, w)
     ctx.meta = (graph, w_var)
-    return y
+    return _run_stem(x, w)
 
   @staticmethod
   def backward(ctx, dy):
@@ -1301,25 +1304,30 @@ class _StemConv(torch.autograd.Function):
     if ctx.needs_input_grad[1]:
       B, _, H, Wd = x.shape
       S = hip.conv_stem_wrw_slabs(B, H, Wd) if OWN_CONV2D_WRW else 0
-      with region('conv_stem_wrw', float((x.numel() + dy.numel()) * 2)):
-        if S > 0:
-          gw = getattr(w, 'grad', None)
-          direct = (gw is not None and gw.shape == w.shape and gw.permute(0, 2, 3, 1).is_contiguous()
-                    and gw.dtype in (torch.float32, torch.bfloat16))
-          dwk = gw.permute(0, 2, 3, 1) if direct else torch.empty((w.shape[0], 7, 7, 3), dtype=w.dtype, device=x.device)
-          with _wrw_queue(graph, direct, dy, x) as scratch:
-            hip.conv_stem_wrw(dy, x, dwk, scratch((S + 32) * 64 * 147), B, H, Wd)
-            if direct:
-              graph.store.notify_grad(w_var)
-          if not direct:
-            dw = dwk.permute(0, 3, 1, 2)
-        else:
+      nbytes = float((x.numel() + dy.numel()) * 2)
+      if S > 0:
+        def wrw(dwk, scratch):
+          hip.conv_stem_wrw(dy, x, dwk, scratch((S + 32) * 64 * 147), B, H, Wd)
+        dw = _filter_grad(graph, w, w_var, (dy, x), 'conv_stem_wrw', nbytes, wrw)
+      else:
+        with region('conv_stem_wrw', nbytes):
           dw = torch.ops.aten.convolution_backward(dy, x, w.detach(), None, [2, 2], [3, 3], [1, 1], False, [0, 0], 1,
                                                    [False, True, False])[1]
     if ctx.needs_input_grad[0]:
       dx = torch.ops.aten.convolution_backward(dy, x, w.detach(), None, [2, 2], [3, 3], [1, 1], False, [0, 0], 1,
                                                [True, False, False])[0]
     return dx, dw, None, None
+
+
+def _run_stem3(x, w, pads, out_hw):
+  """x: the image batch, logical NCHW / physical NHWC bf16; w: logical [N][3][3][3] over KRSC memory; pads: the FRONT pads."""
+  B, _, H, Wd = x.shape
+  N = w.shape[0]
+  Ho, Wo = out_hw
+  y = torch.empty((B, N, Ho, Wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+  with region('conv_stem_fwd', float((x.numel() + y.numel()) * 2)):
+    hip.conv_stem3_fwd(x, w.detach().permute(0, 2, 3, 1), y, B, H, Wd, N, pads[0], pads[1], Ho, Wo)
+  return y
 
 
 class _Stem3Conv(torch.autograd.Function):
@@ -1329,15 +1337,9 @@ class _Stem3Conv(torch.autograd.Function):
 
   @staticmethod
   def forward(ctx, x, w, graph, w_var, pads, out_hw):
-    B, _, H, Wd = x.shape
-    N = w.shape[0]
-    Ho, Wo = out_hw
-    y = torch.empty((B, N, Ho, Wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-    with region('conv_stem_fwd', float((x.numel() + y.numel()) * 2)):
-      hip.conv_stem3_fwd(x, w.detach().permute(0, 2, 3, 1), y, B, H, Wd, N, pads[0], pads[1], Ho, Wo)
     ctx.save_for_backward(x, w)
     ctx.meta = (graph, w_var, pads, out_hw)
-    return y
+    return _run_stem3(x, w, pads, out_hw)
 
   @staticmethod
   def backward(ctx, dy):
@@ -1351,17 +1353,10 @@ class _Stem3Conv(torch.autograd.Function):
       S = hip.conv_stem3_wrw_slabs(B, H, Wd, N, pads[0], pads[1], Ho, Wo)
       if S <= 0:
         raise RuntimeError('pf_conv_stem3_wrw does not take the shape its forward kernel took')
-      with region('conv_stem_wrw', float((x.numel() + dy.numel()) * 2)):
-        gw = getattr(w, 'grad', None)
-        direct = (gw is not None and gw.shape == w.shape and gw.permute(0, 2, 3, 1).is_contiguous()
-                  and gw.dtype in (torch.float32, torch.bfloat16))
-        dwk = gw.permute(0, 2, 3, 1) if direct else torch.empty((N, 3, 3, 3), dtype=w.dtype, device=x.device)
-        with _wrw_queue(graph, direct, dy, x) as scratch:
-          hip.conv_stem3_wrw(dy, x, dwk, scratch((S + 32) * N * 27), B, H, Wd, N, pads[0], pads[1], Ho, Wo)
-          if direct:
-            graph.store.notify_grad(w_var)
-        if not direct:
-          dw = dwk.permute(0, 3, 1, 2)
+
+      def wrw(dwk, scratch):
+        hip.conv_stem3_wrw(dy, x, dwk, scratch((S + 32) * N * 27), B, H, Wd, N, pads[0], pads[1], Ho, Wo)
+      dw = _filter_grad(graph, w, w_var, (dy, x), 'conv_stem_wrw', float((x.numel() + dy.numel()) * 2), wrw)
     if ctx.needs_input_grad[0]:
       raise RuntimeError('the MobileNet stem kernels compute no image gradient')
     return None, dw, None, None, None, None
@@ -1379,7 +1374,7 @@ def own_stem3_ok(x, conv, front_pads, out_hw) -> bool:
 
 def own_stem_ok(x, conv, pad) -> bool:
   return (OWN_STEM and conv.bias is None and isinstance(x, torch.Tensor) and fusable_tensor(x) and x.dim() == 4
-          and pad is not None and pad[0] == pad[1] and conv.graph.fuse_conv1x1
+          and pad[0] == pad[1] and conv.graph.fuse_conv1x1
           and x.is_contiguous(memory_format=torch.channels_last)
           and hip.conv_stem_supported(x.shape[2], x.shape[3], x.shape[1], conv.kernel.ref_shape[3], conv.k, conv.stride, pad[0]))
 
@@ -1393,7 +1388,7 @@ def own_conv2d_ok(x, conv, pad) -> bool:
   kh, kw, cin, cout = conv.kernel.ref_shape
   return (OWN_CONV2D and conv.k > 1 and conv.bias is None and isinstance(x, torch.Tensor) and fusable_tensor(x)
           and x.dim() == 4 and cin % 64 == 0 and cout % 8 == 0
-          and pad is not None and conv.graph.fuse_conv1x1 and igemm_limits_ok(x.numel(), kh * kw * cin * cout, kh * kw))
+          and conv.graph.fuse_conv1x1 and igemm_limits_ok(x.numel(), kh * kw * cin * cout, kh * kw))
 
 
 def fusable_tensor(t: torch.Tensor) -> bool:
@@ -1417,6 +1412,14 @@ def _same_pads(size: int, k: int, stride: int) -> Tuple[int, int]:
   out = -(-size // stride)
   total = max((out - 1) * stride + k - size, 0)
   return total // 2, total - total // 2
+
+
+def _symmetric_pads(x: torch.Tensor, ph: Tuple[int, int], pw: Tuple[int, int]):
+  """(x, (pad_h, pad_w)): the convolution kernels pad both ends of an axis alike, so (begin, end) pads that differ -- TF 'SAME' with
+  an odd total -- become a zero-padded copy of `x` and no padding."""
+  if ph[0] == ph[1] and pw[0] == pw[1]:
+    return x, (ph[0], pw[0])
+  return F.pad(x, (pw[0], pw[1], ph[0], ph[1])), (0, 0)
 
 
 def variance_scaling_init(ref_shape, fan_in: int):
@@ -1487,7 +1490,7 @@ class Conv2D:
       return _tapped(self, materialize(x), residual)
     if self.kernel.gather_host is not None:      # a physically shrunk layer (Graph.apply_gathers): inference on pf_conv_gather.hip
       return self._call_gathered(x, residual, out_bn)
-    if fused_conv1x1_ok(x, self):
+    if fused_conv1x1_ok(x, self):                # 1x1 on pf_conv.hip: the producer BN's normalise / act / fake-quant in the prologue
       lazy = x if isinstance(x, LazyAct) else None
       if lazy is not None:
         lazy.n_consumers += 1
@@ -1495,79 +1498,57 @@ class Conv2D:
         x._pf_bn['n_consumers'] += 2             # a materialised BN output read by a 1x1: its BN-backward sums are not fused
       xin = lazy.x if lazy is not None else _nhwc(x)
       if torch.is_grad_enabled() and (xin.requires_grad or w.requires_grad):
-        box = []
         if lazy is not None and xin.requires_grad:
           lazy.n_grad_consumers += 1
-        y = _FusedConv1x1.apply(xin, w, residual, lazy, want_stats, self.stride, self.graph, box, self.kernel)
-        if box and box[0] is not None:
-          y._pf_stats = box[0]
-        return y
+        return _apply_with_stats(_FusedConv1x1, xin, w, residual, lazy, want_stats, self.stride, self.graph, self.kernel)
       w2d = w.detach().permute(0, 2, 3, 1).reshape(w.shape[0], w.shape[1])
       return _run_conv1x1(xin, w2d, lazy, _nhwc(residual) if residual is not None else None, want_stats,
                           self.stride, out_bn=out_bn)
     x = materialize(x)
     b = self.bias.tensor.to(x.dtype) if self.bias is not None else None
-    pad = 0
-    sym = None                                   # symmetric (pad_h, pad_w) when the padding needs no padded copy
-    if isinstance(self.padding, int):
-      pad = self.padding
-      sym = (pad, pad)
-    elif self.padding == 'SAME' and self.k > 1:
-      ph = _same_pads(x.shape[2], self.k, self.stride)
-      pw = _same_pads(x.shape[3], self.k, self.stride)
-      if residual is None and x.shape[1] == 3 and self.k == 3 and self.stride == 2:
-        out_hw = (-(-x.shape[2] // 2), -(-x.shape[3] // 2))
-        if own_stem3_ok(x, self, (ph[0], pw[0]), out_hw):    # the MobileNet stem: asymmetric 'SAME' pads without a padded image copy
-          if torch.is_grad_enabled() and w.requires_grad:
-            return _Stem3Conv.apply(x, w, self.graph, self.kernel, (ph[0], pw[0]), out_hw)
-          y = torch.empty((x.shape[0], w.shape[0]) + out_hw, dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-          hip.conv_stem3_fwd(x, w.detach().permute(0, 2, 3, 1), y, x.shape[0], x.shape[2], x.shape[3], w.shape[0], ph[0], pw[0],
-                             out_hw[0], out_hw[1])
-          return y
-      if ph[0] == ph[1] and pw[0] == pw[1]:
-        pad = (ph[0], pw[0])
-        sym = pad
-      else:
-        x = F.pad(x, (pw[0], pw[1], ph[0], ph[1]))
-        sym = (0, 0)
-    elif self.padding == 'VALID':
-      sym = (0, 0)
-    if residual is None and own_stem_ok(x, self, sym):
+    ph, pw, out_hw = self._geometry(x)
+    if (self.padding == 'SAME' and residual is None and x.shape[1] == 3 and self.k == 3 and self.stride == 2
+        and own_stem3_ok(x, self, (ph[0], pw[0]), out_hw)):    # the MobileNet stem: asymmetric 'SAME' pads without a padded image copy
+      if torch.is_grad_enabled() and w.requires_grad:
+        return _Stem3Conv.apply(x, w, self.graph, self.kernel, (ph[0], pw[0]), out_hw)
+      return _run_stem3(x, w, (ph[0], pw[0]), out_hw)
+    x, pad = _symmetric_pads(x, ph, pw)
+    if residual is None and own_stem_ok(x, self, pad):         # the ResNet stem
       if torch.is_grad_enabled() and (x.requires_grad or w.requires_grad):
         return _StemConv.apply(x, w, self.graph, self.kernel)
-      y = torch.empty((x.shape[0], w.shape[0], x.shape[2] // 2, x.shape[3] // 2), dtype=x.dtype, device=x.device,
-                      memory_format=torch.channels_last)
-      hip.conv_stem_fwd(x, w.detach().permute(0, 2, 3, 1), y, x.shape[0], x.shape[2], x.shape[3])
-      return y
-    if own_conv2d_ok(x, self, sym):
+      return _run_stem(x, w)
+    if own_conv2d_ok(x, self, pad):              # RxS on the implicit-GEMM kernel
       bn_box = getattr(x, '_pf_bn', None)
       if bn_box is not None:
         bn_box['n_consumers'] += 1
       xin = _nhwc(x)
       if torch.is_grad_enabled() and (xin.requires_grad or w.requires_grad):
-        box = []
-        y = _Conv2dIgemm.apply(xin, w, self.stride, sym, want_stats, self.graph, box, bn_box, self.kernel)
-        if box and box[0] is not None:
-          y._pf_stats = box[0]
+        y = _apply_with_stats(_Conv2dIgemm, xin, w, self.stride, pad, want_stats, self.graph, bn_box, self.kernel)
       else:
-        y = _run_conv2d(xin, w.detach().permute(0, 2, 3, 1), self.stride, sym, want_stats, out_bn=out_bn)
+        y = _run_conv2d(xin, w.detach().permute(0, 2, 3, 1), self.stride, pad, want_stats, out_bn=out_bn)
       return y if residual is None else y + residual
     bn_box = getattr(x, '_pf_bn', None)
     if bn_box is not None:
       bn_box['n_consumers'] += 2                 # a consumer that cannot fuse the BN-backward sums
-    if im2col_conv_ok(x, self, sym):
-      Ho = (x.shape[2] + 2 * sym[0] - self.k) // self.stride + 1
-      Wo = (x.shape[3] + 2 * sym[1] - self.k) // self.stride + 1
-      y = _ConvIm2col.apply(_nhwc(x), w, self.stride, sym, (Ho, Wo), self.graph, self.kernel)
-      return y if residual is None else y + residual
-    if convg_ok(x, w):
-      ph, pw = (pad, pad) if isinstance(pad, int) else pad
-      Ho = (x.shape[2] + 2 * ph - self.k) // self.stride + 1
-      Wo = (x.shape[3] + 2 * pw - self.k) // self.stride + 1
-      y = conv_generic(x, w, self.bias.tensor if self.bias is not None else None, self.stride, (ph, pw), (Ho, Wo), self.graph)
+    if im2col_conv_ok(x, self, pad):             # few-channel RxS as im2col + the 1x1 kernels
+      y = _ConvIm2col.apply(_nhwc(x), w, self.stride, pad, out_hw, self.graph, self.kernel)
+    elif convg_ok(x, w):                         # everything else on the general kernel
+      y = conv_generic(x, w, self.bias.tensor if self.bias is not None else None, self.stride, pad, out_hw, self.graph)
     else:
       y = F.conv2d(x, w, b, stride=self.stride, padding=pad)
     return y if residual is None else y + residual
+
+  def _geometry(self, x):
+    """What `self.padding` means for the input `x`: ((top, bottom), (left, right), (Ho, Wo)).  An int pads every side by that much;
+    TF 'SAME' puts the odd pixel at the END; 'VALID', 'SAME' with a 1x1 kernel and any other string pad nothing."""
+    ph = pw = (0, 0)
+    if isinstance(self.padding, int):
+      ph = pw = (self.padding, self.padding)
+    elif self.padding == 'SAME' and self.k > 1:
+      ph = _same_pads(x.shape[2], self.k, self.stride)
+      pw = _same_pads(x.shape[3], self.k, self.stride)
+    return ph, pw, (_out_size(x.shape[2], self.k, self.stride, ph[0] + ph[1]),
+                    _out_size(x.shape[3], self.k, self.stride, pw[0] + pw[1]))
 
   def _call_gathered(self, x, residual, out_bn) -> torch.Tensor:
     """The shrunk layer: reduction over the kept input channels only (hip.conv_gather_fwd), with the epilogues the dense inference
@@ -1580,30 +1561,18 @@ class Conv2D:
                          'on a graph finalised with requires_grad=False' % var.name)
     if x.dim() != 4 or x.shape[1] != var.cin_full:
       raise ValueError('%s: input of shape %s, the layer has %d input channels' % (var.name, tuple(x.shape), var.cin_full))
-    sym = (0, 0)                                 # 'VALID', and 'SAME' with a 1x1 kernel
-    if isinstance(self.padding, int):
-      sym = (self.padding, self.padding)
-    elif self.padding == 'SAME' and self.k > 1:
-      ph = _same_pads(x.shape[2], self.k, self.stride)
-      pw = _same_pads(x.shape[3], self.k, self.stride)
-      if ph[0] == ph[1] and pw[0] == pw[1]:
-        sym = (ph[0], pw[0])
-      else:
-        x = F.pad(x, (pw[0], pw[1], ph[0], ph[1]))
+    ph, pw, (Ho, Wo) = self._geometry(x)
+    x, pad = _symmetric_pads(x, ph, pw)
     x = _nhwc(x)
     B, C, H, Wd = x.shape
     N = w.shape[0]
-    Ho = (H + 2 * sym[0] - self.k) // self.stride + 1
-    Wo = (Wd + 2 * sym[1] - self.k) // self.stride + 1
-    wk = w.detach().permute(0, 2, 3, 1)
-    if not wk.is_contiguous() or wk.dtype != x.dtype:
-      wk = wk.contiguous().to(x.dtype)
+    wk = _krsc(w, x.dtype)
     y = torch.empty((B, N, Ho, Wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     bias = None if self.bias is None else self.bias.tensor.detach().float().contiguous()
     res = None if residual is None else _nhwc(residual).to(x.dtype)
     ss = out_bn._eval_scale_shift(y) if out_bn is not None else None
     with region('conv_gather_fwd', float((x.numel() + y.numel() * (2 if res is not None else 1)) * x.element_size())):
-      hip.conv_gather_fwd(x, wk, var.gather, y, B, H, Wd, C, N, self.k, self.k, self.stride, sym[0], sym[1], Ho, Wo,
+      hip.conv_gather_fwd(x, wk, var.gather, y, B, H, Wd, C, N, self.k, self.k, self.stride, pad[0], pad[1], Ho, Wo,
                           bias=bias, residual=res, scale_shift=ss, act=out_bn.act if out_bn is not None else None)
     if out_bn is not None:
       y._pf_bn_done = out_bn
@@ -1641,12 +1610,20 @@ def _pass_tag(x, y):
   return y
 
 
-class _NoCtx(object):
-  """Stand-in for an autograd context when a Function's forward is called directly (no gradient needed)."""
-  needs_input_grad = (False,) * 16
-
-  def save_for_backward(self, *a):
-    pass
+def _run_depthwise(x, w, stride, ph, pw, Ho, Wo, want_stats):
+  """x: logical NCHW / physical NHWC, float32 or bf16; w: [C][1][k][k]; ph / pw: the FRONT pads."""
+  B, C, H, W = x.shape
+  k = w.shape[2]
+  y = torch.empty((B, C, Ho, Wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+  partial = None
+  if want_stats:
+    G = hip.depthwise_groups(B, Ho, Wo, C)
+    partial = torch.empty((G, 4, C), dtype=torch.float32, device=x.device)
+  with region('depthwise_fwd', float((x.numel() + y.numel()) * x.element_size())):
+    hip.depthwise_fwd(x, w.detach().reshape(C, k, k), y, B, H, W, C, k, stride, ph, pw, Ho, Wo, partial=partial)
+  if want_stats:
+    y._pf_stats = (partial, G)
+  return y
 
 
 class _Depthwise(torch.autograd.Function):
@@ -1654,21 +1631,12 @@ class _Depthwise(torch.autograd.Function):
   the statistics of y for the BatchNorm behind it (`want_stats`)."""
 
   @staticmethod
-  def forward(ctx, x, w, stride, ph, pw, Ho, Wo, want_stats, graph, box, w_var):
+  def forward(ctx, x, w, stride, ph, pw, Ho, Wo, want_stats, graph, w_var, box):
     x = _nhwc(x)
-    B, C, H, W = x.shape
-    k = w.shape[2]
-    y = torch.empty((B, C, Ho, Wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-    wk = w.detach().reshape(C, k, k)
-    partial = None
-    if want_stats:
-      G = hip.depthwise_groups(B, Ho, Wo, C)
-      partial = torch.empty((G, 4, C), dtype=torch.float32, device=x.device)
-      box.append((partial, G))
-    with region('depthwise_fwd', float((x.numel() + y.numel()) * x.element_size())):
-      hip.depthwise_fwd(x, wk, y, B, H, W, C, k, stride, ph, pw, Ho, Wo, partial=partial)
+    y = _run_depthwise(x, w, stride, ph, pw, Ho, Wo, want_stats)
     ctx.save_for_backward(x, w)
     ctx.meta = (stride, ph, pw, Ho, Wo, graph, w_var)
+    box.append(getattr(y, '_pf_stats', None))
     return y
 
   @staticmethod
@@ -1682,16 +1650,11 @@ class _Depthwise(torch.autograd.Function):
     k = w.shape[2]
     dx = dw = None
     if ctx.needs_input_grad[1]:
-      gw = getattr(w, 'grad', None)
-      direct = gw is not None and gw.shape == w.shape and gw.is_contiguous() and gw.dtype in (torch.float32, torch.bfloat16)
-      dwk = gw if direct else torch.empty(w.shape, dtype=w.dtype, device=x.device)
       G = hip.depthwise_groups(B, Ho, Wo, C)
-      with _wrw_queue(graph, direct, dy, x) as scratch, region('depthwise_wrw', float((x.numel() + dy.numel()) * x.element_size())):
+
+      def wrw(dwk, scratch):                       # dwk: [C][k][k][1] memory = [C][k][k]
         hip.depthwise_wrw(dy, x, dwk, scratch((G + 32) * C * k * k), B, H, W, C, k, stride, ph, pw, Ho, Wo)
-        if direct:
-          graph.store.notify_grad(w_var)           # written straight into the flat gradient buffer
-      if not direct:
-        dw = dwk
+      dw = _filter_grad(graph, w, w_var, (dy, x), 'depthwise_wrw', float((x.numel() + dy.numel()) * x.element_size()), wrw)
     if ctx.needs_input_grad[0]:
       dx = torch.empty_like(x)
       with region('depthwise_bwd_data', float((x.numel() + dy.numel()) * x.element_size())):
@@ -1731,19 +1694,10 @@ class DepthwiseConv2D:
       bn_box = getattr(x, '_pf_bn', None)
       if bn_box is not None:
         bn_box['n_consumers'] += 2                 # a consumer that does not fuse the BN-backward sums of its producer
-      box = []
       if torch.is_grad_enabled() and (x.requires_grad or w.requires_grad):
-        y = _Depthwise.apply(x, w, self.stride, ph[0], pw[0], Ho, Wo, want_stats, self.graph, box, self.kernel)
-      else:
-        y = _Depthwise.forward(_NoCtx(), x, w, self.stride, ph[0], pw[0], Ho, Wo, want_stats, self.graph, box, self.kernel)
-      if box:
-        y._pf_stats = box[0]
-      return y
-    pad = 0
-    if ph[0] == ph[1] and pw[0] == pw[1]:
-      pad = (ph[0], pw[0])
-    else:
-      x = F.pad(x, (pw[0], pw[1], ph[0], ph[1]))
+        return _apply_with_stats(_Depthwise, x, w, self.stride, ph[0], pw[0], Ho, Wo, want_stats, self.graph, self.kernel)
+      return _run_depthwise(_nhwc(x), w, self.stride, ph[0], pw[0], Ho, Wo, want_stats)
+    x, pad = _symmetric_pads(x, ph, pw)
     return F.conv2d(x, self.kernel.tensor, None, stride=self.stride, padding=pad, groups=self.channels)
 
 
@@ -1833,30 +1787,38 @@ class BatchNormAct:
       return False                                # inference-mode BN WITH gradients (_BnEvalAct): its input must exist
     return self.op is None or self.op.bits is None
 
-  def __call__(self, x: torch.Tensor) -> torch.Tensor:
+  def __call__(self, x: torch.Tensor, with_skip: bool = False):
+    """`with_skip`: also return x for the block's identity shortcut (see _BnLazy)."""
     g = self.graph
-    if getattr(x, '_pf_bn_done', None) is self:   # applied in the epilogue of the producing convolution (Conv2D `out_bn`)
-      return x
     bits = self.op.bits if self.op is not None else None
     slot = g.act_slots[self.op.index] if (self.op is not None and bits is not None) else None
     lazy = self.lazy_ok and g.fuse_conv1x1 and fusable_tensor(x)
-    if g.training and torch.is_grad_enabled():
+    skip = x
+    if getattr(x, '_pf_bn_done', None) is self:   # applied in the epilogue of the producing convolution (Conv2D `out_bn`)
+      y = x
+    elif g.training and torch.is_grad_enabled():
       stats = getattr(x, '_pf_stats', None)      # left by the fused convolution that produced x
       if lazy:
         box = []
         alias, skip = _BnLazy.apply(_nhwc(x), self.gamma.tensor, self.beta.tensor, self, g, slot, bits, box, stats)
-        lazy_out = LazyAct(alias, box[0], self.act, slot, bits, x.numel() // self.C, self.C, mean_invstd=box[1])
-        box.append(weakref.ref(lazy_out))
-        return (lazy_out, skip) if getattr(self, '_want_skip', False) else lazy_out
-      box = {}
-      q = _BnActQuant.apply(x, self.gamma.tensor, self.beta.tensor, self, g, True, slot, bits, stats, box)
-      q._pf_bn = box
-      return q
-    if torch.is_grad_enabled() and not g.frozen and (x.requires_grad or self.gamma.tensor.requires_grad):
+        y = LazyAct(alias, box[0], self.act, slot, bits, x.numel() // self.C, self.C, mean_invstd=box[1])
+        box.append(weakref.ref(y))
+      else:
+        box = {}
+        y = _BnActQuant.apply(x, self.gamma.tensor, self.beta.tensor, self, g, True, slot, bits, stats, box)
+        y._pf_bn = box
+    elif torch.is_grad_enabled() and not g.frozen and (x.requires_grad or self.gamma.tensor.requires_grad):
       if bits is not None:
         raise NotImplementedError('inference-mode BN with gradients and activation quantisation (no learner needs it)')
-      return _BnEvalAct.apply(materialize(x), self.gamma.tensor, self.beta.tensor, self, g)
-    x = _nhwc(x)
+      y = _BnEvalAct.apply(materialize(x), self.gamma.tensor, self.beta.tensor, self, g)
+    else:
+      y = self._inference(_nhwc(x), slot, bits, lazy)
+    if g.taps is not None and isinstance(y, torch.Tensor):
+      y = _pass_tag(x, y)
+    return (y, skip) if with_skip else y
+
+  def _inference(self, x, slot, bits, lazy):
+    """Inference mode without gradients, x in NHWC memory."""
     C = self.C
     rows = x.numel() // C
     if bits is None and lazy:
@@ -1869,46 +1831,26 @@ class BatchNormAct:
     # eval graph of a quantising learner: moving statistics + freshly calibrated activation range
     with torch.no_grad():
       nblk = _bn_blocks(rows, C)
-      partial = g.scratch(nblk * 4 * C)
+      partial = self.graph.scratch(nblk * 4 * C)
       ss = torch.empty((2, C), dtype=torch.float32, device=x.device)
       mi = torch.empty((2, C), dtype=torch.float32, device=x.device)
       hip.bn_stats(x, rows, C, partial, nblk)
       hip.bn_finalize(partial, nblk, rows, C, x, self.gamma.tensor, self.beta.tensor, self.moving_mean.tensor,
-                      self.moving_var.tensor, self.momentum, self.eps, g.training, self.act, ss, mi, slot)
+                      self.moving_var.tensor, self.momentum, self.eps, self.graph.training, self.act, ss, mi, slot)
       hip.bn_act_quant_apply(x, q, rows, C, ss, self.act, slot, bits, True)
     return q
 
-
-def _bn_eval_scale_shift(self, x):
-  """Inference BN folded to scale/shift; the teacher's (frozen) pair is cached."""
-  g = self.graph
-  if g.frozen and self._frozen_ss is not None:
-    return self._frozen_ss
-  ss = torch.empty((2, self.C), dtype=torch.float32, device=x.device)
-  hip.bn_eval_scale_shift(self.gamma.tensor, self.beta.tensor, self.moving_mean.tensor, self.moving_var.tensor,
-                          self.eps, ss)
-  if g.frozen:
-    self._frozen_ss = ss
-  return ss
-
-
-BatchNormAct._eval_scale_shift = _bn_eval_scale_shift
-_bn_call = BatchNormAct.__call__
-
-
-def _bn_call_tagged(self, x, with_skip: bool = False):
-  """`with_skip`: also return x for the block's identity shortcut (see _BnLazy)."""
-  self._want_skip = with_skip
-  y = _bn_call(self, x)
-  skip = x
-  if isinstance(y, tuple):
-    y, skip = y
-  if self.graph.taps is not None and isinstance(y, torch.Tensor):
-    y = _pass_tag(x, y)
-  return (y, skip) if with_skip else y
-
-
-BatchNormAct.__call__ = _bn_call_tagged
+  def _eval_scale_shift(self, x):
+    """Inference BN folded to scale/shift; the teacher's (frozen) pair is cached."""
+    g = self.graph
+    if g.frozen and self._frozen_ss is not None:
+      return self._frozen_ss
+    ss = torch.empty((2, self.C), dtype=torch.float32, device=x.device)
+    hip.bn_eval_scale_shift(self.gamma.tensor, self.beta.tensor, self.moving_mean.tensor, self.moving_var.tensor,
+                            self.eps, ss)
+    if g.frozen:
+      self._frozen_ss = ss
+    return ss
 
 
 class _MaxPool(torch.autograd.Function):
@@ -1919,8 +1861,7 @@ class _MaxPool(torch.autograd.Function):
     need_grad = ctx.needs_input_grad[0]          # of the ARGUMENT: a channels_last copy made in here never requires grad
     x = _nhwc(x)
     B, C, H, W = x.shape
-    Ho = (H + ph[0] + ph[1] - k) // stride + 1
-    Wo = (W + pw[0] + pw[1] - k) // stride + 1
+    Ho, Wo = _out_size(H, k, stride, ph[0] + ph[1]), _out_size(W, k, stride, pw[0] + pw[1])
     y = torch.empty((B, C, Ho, Wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     idx = torch.empty((B, Ho, Wo, C), dtype=torch.uint8, device=x.device) if need_grad else None
     with region('maxpool_fwd', float((x.numel() + y.numel()) * x.element_size())):

@@ -224,6 +224,56 @@ def test_mobilenet_pointwise_fusion_is_exact_on_cpu(monkeypatch):
     assert err <= 5e-4, (k, err)      # 27 BN layers deep; the fused statistics are un-pivoted sums
 
 
+_RESNET_SMALL_CENSUS = dict(bn_apply=5, bn_bwd_apply=11, bn_bwd_apply_add=2, bn_bwd_stats=7, bn_finalize=13, bn_stats=5, col2im=4,
+                            conv1x1_bwd_data_bnstats=6, conv1x1_fwd=10, conv1x1_plain=12, conv1x1_wrw=14, im2col=8)
+_MOBILENET_CENSUS = dict(bn_apply=14, bn_bwd_apply=27, bn_bwd_stats=14, bn_finalize=27, bn_stats=1, conv1x1_bwd_data_bnstats=13,
+                         conv1x1_fwd=13, conv1x1_wrw=13, depthwise_bwd_data=13, depthwise_fwd=13, depthwise_wrw=13)
+STEP_LAUNCH_CENSUS = {
+    # 8 filters: the 3x3 convolutions run as im2col + the 1x1 kernels (`conv1x1_plain` = a 1x1 launch without a prologue)
+    ('resnet', None, 8): _RESNET_SMALL_CENSUS,
+    ('resnet', 6, 8): _RESNET_SMALL_CENSUS,
+    # 64 filters: the 3x3 convolutions run on the implicit-GEMM entry point
+    ('resnet', None, 64): dict(bn_apply=5, bn_bwd_apply=11, bn_bwd_apply_add=2, bn_bwd_stats=4, bn_finalize=13, bn_stats=1,
+                               conv1x1_bwd_data_bnstats=6, conv1x1_fwd=10, conv1x1_plain=4, conv1x1_wrw=10,
+                               conv2d_bwd_data_bnstats=3, conv2d_fwd=4, conv2d_wrw=4),
+    # depth multiplier 0.25: an 8-channel first layer, which the stem kernel does not take (the library convolution of the emulation)
+    ('mobilenet', 0.25): _MOBILENET_CENSUS,
+    # depth multiplier 0.5: a 16-channel first layer on the MobileNet stem kernels
+    ('mobilenet', 0.5): dict(_MOBILENET_CENSUS, conv_stem3_fwd=1, conv_stem3_wrw=1),
+}
+
+
+@pytest.mark.parametrize('config', list(STEP_LAUNCH_CENSUS), ids=lambda c: '-'.join(str(v) for v in c))
+def test_step_launch_census(monkeypatch, config):
+  """How often ONE training step (forward + backward) calls each HIP entry point, and through that which route every layer took:
+  the 1x1 / im2col / implicit-GEMM / stem / depthwise convolution routes, the lazy and the materialised BN, every fused epilogue.
+  The neighbouring tests compare fused against unfused results and assert a few counts each; this one pins all of them, so that a
+  change to the plumbing that moves a layer to another route, or adds or drops a launch, shows up as a changed table."""
+  from pocketflow_amd import graph as G
+  from pocketflow_amd.utils.external.mobilenet_v1 import MobilenetV1
+  fake = FakeHip()
+  monkeypatch.setattr(G, 'hip', fake)
+  monkeypatch.setattr(G, 'fusable_tensor', lambda t: True)
+  if config[0] == 'resnet':
+    g, net = _build(True, fake, config[1], config[2])
+    shape, ncls = (4, 3, 12, 12), 7
+  else:
+    monkeypatch.setattr(G, 'DEPTHWISE_ANY_DEVICE', True)
+    g = G.Graph('model', 'cpu', torch.float32)
+    net = MobilenetV1(g, num_classes=16, depth_multiplier=config[1], dropout_keep_prob=1.0)
+    g.finalize(seed=5, requires_grad=True)
+    shape, ncls = (8, 3, 64, 64), 16
+  torch.manual_seed(0)
+  x = torch.randn(*shape).contiguous(memory_format=torch.channels_last)
+  wts = torch.randn(shape[0], ncls)
+  g.begin_step = lambda: None
+  fake.minmax_slots_init(g.act_slots)
+  with g.as_default():
+    logits = net(x, True)
+  (logits * wts).sum().backward()
+  assert dict(fake.calls) == STEP_LAUNCH_CENSUS[config], sorted(fake.calls.items())
+
+
 @pytest.mark.parametrize('dataset,size,ncls,shape', [('cifar_10', 20, 10, (32, 32, 3)), ('ilsvrc_12', 50, 11, (64, 64, 3)),
                                                      ('ilsvrc_12', 18, 7, (64, 64, 3))])
 def test_product_resnet_matches_the_reference_network_code(monkeypatch, dataset, size, ncls, shape):

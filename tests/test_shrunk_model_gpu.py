@@ -63,13 +63,14 @@ def forward64(graph, mh, images):
   def dense(self, x):
     return F.linear(x.double(), self.kernel.tensor.detach().double(), self.bias.tensor.detach().double())
 
-  def bn(self, x):
+  def bn(self, x, with_skip=False):
     v = lambda t: t.detach().double().view(1, -1, 1, 1)
     y = (x.double() - v(self.moving_mean.tensor)) / torch.sqrt(v(self.moving_var.tensor) + self.eps) * v(self.gamma.tensor) + v(self.beta.tensor)
-    return torch.relu(y) if self.act == 'Relu' else (torch.clamp(y, 0, 6) if self.act == 'Relu6' else y)
+    y = torch.relu(y) if self.act == 'Relu' else (torch.clamp(y, 0, 6) if self.act == 'Relu6' else y)
+    return (y, x) if with_skip else y            # the bottleneck block asks for its identity shortcut in inference too
 
   with mock.patch.object(G.Conv2D, '__call__', conv), mock.patch.object(G.DepthwiseConv2D, '__call__', depthwise), \
-      mock.patch.object(G.Dense, '__call__', dense), mock.patch.object(G, '_bn_call', bn), torch.no_grad(), graph.as_default():
+      mock.patch.object(G.Dense, '__call__', dense), mock.patch.object(G.BatchNormAct, '__call__', bn), torch.no_grad(), graph.as_default():
     return mh.forward_eval(G.to_device_images(images, graph).double())
 
 
