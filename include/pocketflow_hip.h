@@ -253,6 +253,23 @@ int pf_conv1x1_fwd_affine(const void* X, const void* W, void* Y, const float* sc
 int pf_conv1x1_bwd_data_bnstats(const void* dY, const void* Wt, void* dQ, const void* bn_x,
                                 const float* bn_scale_shift, const float* bn_mean_invstd, int bn_act,
                                 float* partial, int M, int N, int K, void* stream);
+/* backward-data of a stride-1 1x1 convolution that JOINS the gradient of a second consumer of Q (a projection block: conv1 and the
+ * shortcut convolution both read bn1's output):  dQ[m][k] = bf16( sum_n dY[m][n] * W[n][k] + R(m)[k] ), one rounding.
+ *   r_stride == 1: R is dense, [M][K], R(m) = R[m] (the other arguments of the geometry are ignored).
+ *   r_stride  > 1: R is COMPACT, [imgs][r_Ho][r_Wo][K] with r_Ho = ceil(r_H / r_stride), r_Wo = ceil(r_W / r_stride) and
+ *     M = imgs * r_H * r_W: row m = (img, h, w) takes row (img, h / r_stride, w / r_stride) of R when h and w are multiples of
+ *     r_stride and exactly +0.0f otherwise -- bit for bit what a zero-filled [M][K] tensor with the rows scattered into it gives,
+ *     without writing and reading the zeros.
+ *   bn_x != NULL: the BN-backward sums of pf_conv1x1_bwd_data_bnstats, taken from the stored (joined, rounded) dQ:
+ *     partial[G][2][K], G = pf_conv1x1_stats_groups_k(M, K, N, 0).  bn_x == NULL: no sums, partial is ignored.
+ * Only the shapes pf_conv1x1_join_plan(M, N, K, 0) accepts; hipErrorInvalidValue otherwise (there is no slower route behind it).
+ * pf_conv1x1_join_plan(M, N, K, with_stats): 0 = refused, 1 = resident-kernel variant, 2 = staged GEMM.  With with_stats it also
+ * refuses the shapes on which the sums in the launch measured slower than the separate pf_bn_bwd_stats pass (the staged GEMM below
+ * 2^17 rows): advice to the caller -- the entry itself computes the sums on every shape whose kernel carries them.           */
+int pf_conv1x1_join_plan(int M, int N, int K, int with_stats);
+int pf_conv1x1_bwd_data_join(const void* dY, const void* Wt, void* dQ, const void* R, int r_Ho, int r_Wo, int r_H, int r_W,
+                             int r_stride, const void* bn_x, const float* bn_scale_shift, const float* bn_mean_invstd,
+                             int bn_act, float* partial, int M, int N, int K, void* stream);
 int pf_conv1x1_wrw_splits(int M, int N, int K);
 int pf_conv1x1_wrw(const void* dY, const void* X, void* dW, int dw_dtype, float* workspace,
                    const float* scale_shift, int act, const uint32_t* slot, int bits, int M, int N,

@@ -317,6 +317,7 @@ static int conv_fwd_grid(int tiles_m, int tiles_n, int* G_out) {
 int pf_conv_stream_plan(int M, int N, int K, int* nw_out);
 int pf_conv_stream_groups(int nsplit);
 int pf_conv_stream_launch(const ConvArgs& a, bool pro, bool bwd, hipStream_t st);
+bool pf_conv_stream_join_ok(int nw, bool with_stats);
 
 extern "C" int pf_conv1x1_stats_groups(int M, int N) {
   const int bn = conv_bn_of(N);
@@ -333,7 +334,8 @@ int pf_igemm_stats_groups(int M, int N, int pro);           // the launcher's ow
 int pf_igemm_conv1x1(const void* X, const void* W, void* Y, const void* R, float* partial, const void* bn_x,
                      const float* bss, const float* bmi, float b_lo, float b_hi, const float* scale_shift,
                      const uint32_t* slot, float kq, float act_lo, float act_hi, int M, int N, int K, int Ho, int Wo,
-                     int H, int Wd, int stride, const float* oss, int oact, hipStream_t st, int ymap = 0);
+                     int H, int Wd, int stride, const float* oss, int oact, hipStream_t st, int ymap = 0, const int* rgeom = nullptr);
+bool pf_igemm_join_ok(int M, int N, int K);
 // Which 1x1 shapes go to the direct-to-LDS staged kernel (after the resident-kernel variant had its pick).  Measured
 // (tools/gpu/igemm_bench.py, conv_bench2.py): prologue-free GEMMs win from K = 512 up; with the prologue the in-LDS pass
 // behind asynchronous staging beats the register-staged tiles of this file on every shape it was tried on.
@@ -355,11 +357,34 @@ extern "C" int pf_conv1x1_stats_groups_k(int M, int N, int K, int prologue) {
   return pf_conv1x1_stats_groups(M, N);
 }
 
+// Which kernel takes the joined backward-data dQ[M][K] = dY[M][N] * Wt + R (pf_conv1x1_bwd_data_join; the GEMM it launches is
+// [M][N] x [K][N]): 1 = the resident-kernel variant, 2 = the staged GEMM, 0 = none (the register-staged tiles of this file carry
+// neither the inverse row map nor the sums beside a residual: such shapes stay on the separate launches).
+static int conv_join_kernel(int M, int N, int K, bool with_stats) {
+  if (M <= 0 || N <= 0 || K <= 0) return 0;
+  int nw = 0;
+  if (pf_conv_stream_plan(M, K, N, &nw) > 0) return pf_conv_stream_join_ok(nw, with_stats) ? 1 : 0;
+  if (conv_use_igemm(false, N) && pf_igemm_join_ok(M, K, N)) return 2;
+  return 0;
+}
+
+// ... and whether the caller SHOULD ask for the sums in that launch: on the staged GEMM they pay from about 2^17 rows up (measured at
+// batch 256, profiles/proj_join_ab.txt: 28 x 28, 256 -> 512: 184 us against 147 + 81 for the join and the separate pass; 14 x 14,
+// 512 -> 1024: 125 against 86 + 34 -- six tiles per workgroup leave the BN-input loads of the row pass nothing to hide behind).
+// Below that the plan refuses `with_stats` and the shape keeps pf_bn_bwd_stats; the entry itself runs whatever the kernels carry.
+#define PF_JOIN_STATS_IGEMM_MIN_M (1 << 17)
+extern "C" int pf_conv1x1_join_plan(int M, int N, int K, int with_stats) {
+  const int k = conv_join_kernel(M, N, K, with_stats != 0);
+  if (k == 2 && with_stats && M < PF_JOIN_STATS_IGEMM_MIN_M) return 0;
+  return k;
+}
+
 static int conv_fwd_launch(const void* X, const void* W, void* Y, const void* R, const float* scale_shift,
                            int act, const uint32_t* slot, int bits, float* partial, int M, int N, int K,
                            int Ho, int Wo, int H, int Wd, int stride, int ymap, const void* bx,
                            const float* bss, const float* bmi, int bact, void* stream, const float* oss = nullptr,
-                           int oact = PF_ACT_NONE) {
+                           int oact = PF_ACT_NONE, const int* rgeom = nullptr) {
+  // rgeom = {Ho, Wo, H, W, stride} of the residual: the joined backward-data of a projection block (pf_conv1x1_bwd_data_join below)
   if (oss != nullptr && (R != nullptr || partial != nullptr || bx != nullptr || ymap)) return (int)hipErrorInvalidValue;
   if (M <= 0 || N <= 0 || K <= 0 || (K % 8) || (N % 8)) return (int)hipErrorInvalidValue;
   if (!pf_aligned16(X) || !pf_aligned16(W) || !pf_aligned16(Y) || (R && !pf_aligned16(R)))
@@ -379,7 +404,9 @@ static int conv_fwd_launch(const void* X, const void* W, void* Y, const void* R,
   a.b_lo = (bact == PF_ACT_NONE) ? -INFINITY : 0.0f;
   a.b_hi = (bact == PF_ACT_RELU6) ? 6.0f : INFINITY;
   a.oss = oss; a.oact = oact;
-  if (bx != nullptr && (R != nullptr || partial == nullptr || bss == nullptr || bmi == nullptr || stride != 1 ||
+  a.rHo = 0; a.rWo = 0; a.rH = 0; a.rW = 0; a.rstride = 1;
+  if (rgeom != nullptr) { a.rHo = rgeom[0]; a.rWo = rgeom[1]; a.rH = rgeom[2]; a.rW = rgeom[3]; a.rstride = rgeom[4]; }
+  if (bx != nullptr && ((R != nullptr && rgeom == nullptr) || partial == nullptr || bss == nullptr || bmi == nullptr || stride != 1 ||
                         !pf_aligned16(bx)))
     return (int)hipErrorInvalidValue;
   const int bn = conv_bn_of(N);
@@ -389,6 +416,17 @@ static int conv_fwd_launch(const void* X, const void* W, void* Y, const void* R,
   hipStream_t st = (hipStream_t)stream;
   const bool pro = scale_shift != nullptr;
   if (bx != nullptr && pro) return (int)hipErrorInvalidValue;
+  if (rgeom != nullptr) {
+    // exactly the kernel conv_join_kernel names (pf_conv1x1_stats_groups_k sizes `partial` by the same decision); no other kernel
+    // carries these variants
+    if (pro || ymap || stride != 1 || oss != nullptr || R == nullptr) return (int)hipErrorInvalidValue;
+    const int plan = conv_join_kernel(M, K, N, bx != nullptr);           // this launch: [M][K] x [N][K], N = the channels of dQ
+    int r = -1;
+    if (plan == 1) r = pf_conv_stream_launch(a, false, bx != nullptr, st);
+    else if (plan == 2) r = pf_igemm_conv1x1(X, W, Y, R, partial, bx, bss, bmi, a.b_lo, a.b_hi, nullptr, nullptr, a.kq, a.act_lo,
+                                             a.act_hi, M, N, K, 0, 0, 0, 0, 1, nullptr, PF_ACT_NONE, st, 0, rgeom);
+    return (r >= 0) ? r : (int)hipErrorInvalidValue;
+  }
   {
     const int r = pf_conv_stream_launch(a, pro, bx != nullptr, st);      // HBM-bound shapes: kernel resident in LDS
     if (r >= 0) return r;
@@ -456,6 +494,23 @@ extern "C" int pf_conv1x1_bwd_data_bnstats(const void* dY, const void* Wt, void*
                                            float* partial, int M, int N, int K, void* stream) {
   return conv_fwd_launch(dY, Wt, dQ, nullptr, nullptr, PF_ACT_NONE, nullptr, 8, partial, M, K, N, 0, 0, 0, 0, 1, 0,
                          bn_x, bn_scale_shift, bn_mean_invstd, bn_act, stream);
+}
+
+// backward-data of a stride-1 1x1 convolution joined with the gradient R of a second consumer of Q (include/pocketflow_hip.h):
+// dQ = bf16(dY * W + R(m)), R dense (r_stride == 1) or compact behind the inverse row map, optionally with the BN-backward sums
+// of pf_conv1x1_bwd_data_bnstats taken from the joined, rounded dQ.
+extern "C" int pf_conv1x1_bwd_data_join(const void* dY, const void* Wt, void* dQ, const void* R, int r_Ho, int r_Wo, int r_H, int r_W,
+                                        int r_stride, const void* bn_x, const float* bn_scale_shift, const float* bn_mean_invstd,
+                                        int bn_act, float* partial, int M, int N, int K, void* stream) {
+  if (R == nullptr || r_stride < 1) return (int)hipErrorInvalidValue;
+  if (r_stride > 1) {
+    if (r_H <= 0 || r_W <= 0 || (M % (r_H * r_W)) || r_Ho != (r_H + r_stride - 1) / r_stride || r_Wo != (r_W + r_stride - 1) / r_stride)
+      return (int)hipErrorInvalidValue;
+  }
+  if (conv_join_kernel(M, N, K, bn_x != nullptr) == 0) return (int)hipErrorInvalidValue;
+  const int rgeom[5] = {r_Ho, r_Wo, r_H, r_W, r_stride};
+  return conv_fwd_launch(dY, Wt, dQ, R, nullptr, PF_ACT_NONE, nullptr, 8, (bn_x != nullptr) ? partial : nullptr, M, K, N, 0, 0, 0, 0, 1,
+                         0, bn_x, bn_scale_shift, bn_mean_invstd, bn_act, stream, nullptr, PF_ACT_NONE, rgeom);
 }
 
 // ---------------------------------------------------------------------------------------------

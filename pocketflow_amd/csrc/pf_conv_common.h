@@ -56,7 +56,22 @@ struct ConvArgs {
   // of the CONSUMER folded into this launch (out_affine8 below); no statistics, no residual with it
   const float* oss;     // scale | shift   [2][N]
   int oact;             // PF_ACT_*
+  // compact residual (kernels instantiated with RMAP only, rmap_row below): R is [img][rHo][rWo][N] and belongs to the pixels
+  // (h, w) of the launch's dense [rH x rW] output grid with h % rstride == 0 and w % rstride == 0
+  int rHo, rWo, rH, rW, rstride;
 };
+
+// Inverse row map of a compact residual: output row m = (img, h, w) of a dense [H x W] grid -> row (img, h / stride, w / stride) of
+// the [Ho x Wo] tensor, or -1 when the pixel has no partner (its residual is +0.0f: what the zero-filled full-size tensor of the
+// backward-data of a strided convolution held there).
+__device__ __forceinline__ int64_t rmap_row(int m, int Ho, int Wo, int H, int W, int stride) {
+  const int hw = H * W;
+  const int img = m / hw, rem = m - img * hw;
+  const int h = rem / W, w = rem - h * W;
+  const int hq = h / stride, wq = w / stride;
+  if (hq * stride != h || wq * stride != w) return -1;
+  return ((int64_t)img * Ho + hq) * Wo + wq;
+}
 
 // The output affine on one 16-byte vector of the row pass: 8 consecutive channels n .. n + 7 of one pixel, ALREADY rounded to bf16.
 // Exactly the arithmetic of pf_bn_act_quant_apply without a quantiser on exactly the value it would read back from HBM --

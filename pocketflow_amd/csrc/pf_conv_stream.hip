@@ -33,7 +33,12 @@
 // (it is inlined at every load and store site: without the split the loop body outgrows the instruction cache)
 // AFF: the output affine of the row pass (ConvArgs.oss; forward launches of an inference-mode network only) -- a template
 // parameter, not a run-time branch: the branch cost the training kernels 8-16 registers (k_conv1x1_stream<256, true> spilled)
-template <int NW, bool PRO, bool BWD, bool MAP, bool AFF = false>
+// RMAP: the residual is COMPACT and read through the inverse row map (rmap_row, ConvArgs.r*): the joined backward-data of a
+// projection block, whose strided shortcut leaves a gradient for every stride-th pixel only.  It changes the residual loads alone.
+// BR: backward-data with the BN-backward sums AND a residual (BWD alone has none): the residual lands on the accumulators, they are
+// rounded once and staged, and the row pass takes the sums from the staged values -- the arithmetic of BWD on the value a separate
+// statistics pass would read back.  The sums keep no min / max, whose registers pay for the residual's.
+template <int NW, bool PRO, bool BWD, bool MAP, bool AFF = false, bool RMAP = false, bool BR = false>
 __global__ __launch_bounds__(ST_THREADS) void k_conv1x1_stream(const ConvArgs a, const int nsplit) {
   constexpr int JM = (NW == 256) ? 1 : 2;           // 16-pixel blocks per strip
   constexpr int RS = 16 * JM;                       // pixel rows per strip
@@ -96,16 +101,19 @@ __global__ __launch_bounds__(ST_THREADS) void k_conv1x1_stream(const ConvArgs a,
 
   const int wswz = (KV >= 16) ? l15 : (l15 & 7);                          // this lane's weight-row swizzle
   const bf16_t* __restrict__ side = BWD ? a.bx : nullptr;                // second [M][N] operand of the row pass
-  const bool has_r = !BWD && a.R != nullptr;                             // residual: added on the fp32 accumulators
+  static_assert(!BR || BWD, "BR is a variant of BWD");
+  const bool has_r = BWD ? BR : (a.R != nullptr);                        // residual: added on the fp32 accumulators
   const int wvec = lane % VPR, wrow = lane / VPR;
 
   f32x4 acc[NI][JM];
   uint4 ring[D][NR];
   uint4 rres[NP];
   uint2 rr[NI][JM];                                                      // residual of the NEXT strip, accumulator layout
-  float st_s[8], st_q[8], st_mn[8], st_mx[8];
+  float st_s[8], st_q[8], st_mn[BR ? 1 : 8], st_mx[BR ? 1 : 8];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) { st_s[j] = 0.f; st_q[j] = 0.f; st_mn[j] = INFINITY; st_mx[j] = -INFINITY; }
+  for (int j = 0; j < 8; ++j) { st_s[j] = 0.f; st_q[j] = 0.f; }
+#pragma unroll
+  for (int j = 0; j < (BR ? 1 : 8); ++j) { st_mn[j] = INFINITY; st_mx[j] = -INFINITY; }
 
   // load-side cursor (chunk t -> strip, 64-channel step)
   int ld_s = s_first, ld_kc = 0;
@@ -136,12 +144,17 @@ __global__ __launch_bounds__(ST_THREADS) void k_conv1x1_stream(const ConvArgs a,
 #pragma unroll
     for (int j = 0; j < JM; ++j) {
       const int m = s * RS + j * 16 + l15;
-      const int64_t orow = (m < a.M) ? ((MAP && a.ymap) ? map_row(a, m) : (int64_t)m) : 0;
+      int64_t orow = (m < a.M) ? ((MAP && a.ymap) ? map_row(a, m) : (int64_t)m) : 0;
+      bool live = m < a.M;
+      if constexpr (RMAP) {                                              // pixels without a partner: +0.0f, no load
+        orow = live ? rmap_row(m, a.rHo, a.rWo, a.rH, a.rW, a.rstride) : -1;
+        live = orow >= 0;
+      }
 #pragma unroll
       for (int i = 0; i < NI; ++i) {
         const int n = n0 + i * 16 + q * 4;
         uint2 v = make_uint2(0, 0);
-        if (m < a.M && n < a.N) v = *reinterpret_cast<const uint2*>(a.R + orow * a.N + n);
+        if (live && n < a.N) v = *reinterpret_cast<const uint2*>(a.R + orow * a.N + n);
         rr[i][j] = v;
       }
     }
@@ -149,7 +162,10 @@ __global__ __launch_bounds__(ST_THREADS) void k_conv1x1_stream(const ConvArgs a,
 #pragma clang loop unroll(full)
   for (int d = 0; d < D; ++d)
     if (d < T) issue(ring[d]);
-  if (has_r && cnt > 0) issue_res(s_first);
+  // BR at NW = 256: no 32 registers for a residual that travels under the main loop beside the BN-input vectors -- loaded at use
+  // (one exposed round trip per strip and wavefront, covered by the other seven of the CU)
+  constexpr bool RLATE = BR && NW == 256;
+  if (has_r && !RLATE && cnt > 0) issue_res(s_first);
   if (side != nullptr && cnt > 0) {
 #pragma unroll
     for (int p = 0; p < NP; ++p) issue_side(s_first, p);
@@ -231,7 +247,32 @@ __global__ __launch_bounds__(ST_THREADS) void k_conv1x1_stream(const ConvArgs a,
     if (!last) continue;
 
     // ---- epilogue of one [RS][NW] tile: wave-private transposition, no workgroup barrier ----------------------
-    if (has_r) {                                                         // ONE rounding to bf16 (in the staging below)
+    if constexpr (RLATE) {                                               // eight channel blocks at a time: 16 registers live
+      const int m = s * RS + l15;
+      int64_t orow = m;
+      bool live = m < a.M;
+      if constexpr (RMAP) {
+        orow = live ? rmap_row(m, a.rHo, a.rWo, a.rH, a.rW, a.rstride) : -1;
+        live = orow >= 0;
+      }
+#pragma unroll
+      for (int ib = 0; ib < NI; ib += 8) {
+        uint2 t[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const int n = n0 + (ib + i) * 16 + q * 4;
+          t[i] = make_uint2(0, 0);
+          if (live && n < a.N) t[i] = *reinterpret_cast<const uint2*>(a.R + orow * a.N + n);
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          acc[ib + i][0][0] += __uint_as_float(t[i].x << 16); acc[ib + i][0][1] += __uint_as_float(t[i].x & 0xFFFF0000u);
+          acc[ib + i][0][2] += __uint_as_float(t[i].y << 16); acc[ib + i][0][3] += __uint_as_float(t[i].y & 0xFFFF0000u);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    if (has_r && !RLATE) {                                                       // ONE rounding to bf16 (in the staging below)
 #pragma unroll
       for (int i = 0; i < NI; ++i)
 #pragma unroll
@@ -248,9 +289,11 @@ __global__ __launch_bounds__(ST_THREADS) void k_conv1x1_stream(const ConvArgs a,
         *reinterpret_cast<uint2*>(Cs + (j * 16 + l15) * CS_LD + i * 16 + q * 4) = w;
       }
     const bool more = (cs < NS);                                         // this wavefront has another strip
-    if (has_r && more) issue_res(cs);                                    // next strip's residual travels under its main loop
+    if (has_r && !RLATE && more) issue_res(cs);                                 // next strip's residual travels under its main loop
     float bpr[32];                                                       // BWD: this lane's 8 channels of scale | shift | mean | invstd
-    if (BWD && NW != 128) {
+    // BR: the residual's registers take the room of the hoisted constants -- they are read from LDS in every pass, as at NW = 128
+    constexpr bool BPL = (NW == 128) || BR;
+    if (BWD && !BPL) {
 #pragma unroll
       for (int qq = 0; qq < 4; ++qq)
 #pragma unroll
@@ -259,7 +302,7 @@ __global__ __launch_bounds__(ST_THREADS) void k_conv1x1_stream(const ConvArgs a,
 #pragma unroll
       for (int i = 0; i < 32; ++i) bpr[i] = 0.f;
     }
-    constexpr int CB = (NW == 128) ? 1 : 4;                              // scheduling experiment: rows requested CB at a time
+    constexpr int CB = (NW == 128 || (BR && NW == 256)) ? 1 : (BR ? 2 : 4);                  // scheduling experiment: rows requested CB at a time
     uint4 cv[CB];                                                        // (NW = 128 has no registers to spare: it spills as it is)
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
@@ -275,12 +318,12 @@ __global__ __launch_bounds__(ST_THREADS) void k_conv1x1_stream(const ConvArgs a,
       if (side != nullptr && more) issue_side(cs, p);                    // next strip's vector into the freed register
       if (m < a.M && n < a.N) {
         const int64_t orow = (MAP && a.ymap) ? map_row(a, m) : (int64_t)m;
-        if (BWD) {
+        if constexpr (BWD) {
           float f[8], xv[8];
           unpack8(c, f);
           unpack8(sv, xv);
-          const float* bp = (NW == 128) ? (aux + wvec * 8) : bpr;        // hoisted: hipcc re-reads the 8 vectors from LDS in every pass
-          constexpr int BPS = (NW == 128) ? NW : 8;
+          const float* bp = BPL ? (aux + wvec * 8) : bpr;                // hoisted: hipcc re-reads the 8 vectors from LDS in every pass
+          constexpr int BPS = BPL ? NW : 8;
 #pragma unroll
           for (int j = 0; j < 8; ++j) {
             const float u = fmaf(bp[j], xv[j], bp[BPS + j]);
@@ -315,8 +358,10 @@ __global__ __launch_bounds__(ST_THREADS) void k_conv1x1_stream(const ConvArgs a,
       for (int j = 0; j < 8; ++j) {
         st_s[j] += __shfl_xor(st_s[j], o, 64);
         st_q[j] += __shfl_xor(st_q[j], o, 64);
-        st_mn[j] = fminf(st_mn[j], __shfl_xor(st_mn[j], o, 64));
-        st_mx[j] = fmaxf(st_mx[j], __shfl_xor(st_mx[j], o, 64));
+        if constexpr (!BR) {
+          st_mn[j] = fminf(st_mn[j], __shfl_xor(st_mn[j], o, 64));
+          st_mx[j] = fmaxf(st_mx[j], __shfl_xor(st_mx[j], o, 64));
+        }
       }
     }
     __syncthreads();                                                     // every wavefront is done with its staging tile
@@ -325,8 +370,10 @@ __global__ __launch_bounds__(ST_THREADS) void k_conv1x1_stream(const ConvArgs a,
       for (int j = 0; j < 8; ++j) {
         red[(0 * ST_WAVES + wave) * NW + lane * 8 + j] = st_s[j];
         red[(1 * ST_WAVES + wave) * NW + lane * 8 + j] = st_q[j];
-        red[(2 * ST_WAVES + wave) * NW + lane * 8 + j] = st_mn[j];
-        red[(3 * ST_WAVES + wave) * NW + lane * 8 + j] = st_mx[j];
+        if constexpr (!BR) {
+          red[(2 * ST_WAVES + wave) * NW + lane * 8 + j] = st_mn[j];
+          red[(3 * ST_WAVES + wave) * NW + lane * 8 + j] = st_mx[j];
+        }
       }
     }
     __syncthreads();
@@ -371,13 +418,17 @@ int pf_conv_stream_plan(int M, int N, int K, int* nw_out) {
 
 int pf_conv_stream_groups(int nsplit) { return ST_GRID / nsplit; }
 
-template <int NW, bool PRO, bool BWD, bool MAP, bool AFF = false>
+// the joined backward-data variants (RMAP / BR): every slice width carries the compact residual; the sums with a residual are
+// compiled for 64 and 256 only (the 128-wide kernel is at its register limit without them)
+bool pf_conv_stream_join_ok(int nw, bool with_stats) { return !with_stats || nw == 64 || nw == 256; }
+
+template <int NW, bool PRO, bool BWD, bool MAP, bool AFF = false, bool RMAP = false, bool BR = false>
 static int stream_launch_t(const ConvArgs& a, int nsplit, hipStream_t st) {
   const int JM = (NW == 256) ? 1 : 2, RS = 16 * JM;
   const size_t aux_fl = PRO ? 2 * (size_t)a.K : (BWD ? 4 * (size_t)NW : 0);
   const size_t lds = (size_t)NW * a.K * 2 + aux_fl * 4 + (size_t)ST_WAVES * RS * (NW + 8) * 2;
-  if (int e = pf_require_lds(reinterpret_cast<const void*>(&k_conv1x1_stream<NW, PRO, BWD, MAP, AFF>), lds)) return e;
-  k_conv1x1_stream<NW, PRO, BWD, MAP, AFF><<<ST_GRID, ST_THREADS, lds, st>>>(a, nsplit);
+  if (int e = pf_require_lds(reinterpret_cast<const void*>(&k_conv1x1_stream<NW, PRO, BWD, MAP, AFF, RMAP, BR>), lds)) return e;
+  k_conv1x1_stream<NW, PRO, BWD, MAP, AFF, RMAP, BR><<<ST_GRID, ST_THREADS, lds, st>>>(a, nsplit);
   PF_LAUNCH_CHECK();
   return 0;
 }
@@ -388,6 +439,17 @@ int pf_conv_stream_launch(const ConvArgs& a, bool pro, bool bwd, hipStream_t st)
   const int nsplit = pf_conv_stream_plan(a.M, a.N, a.K, &nw);
   if (nsplit == 0) return -1;
   const bool map = a.stride != 1;
+  if (a.rstride > 1 || (bwd && a.R != nullptr)) {          // the joined backward-data of a projection block (pf_conv1x1_bwd_data_join)
+    if (!pf_conv_stream_join_ok(nw, bwd) || pro || map || a.oss != nullptr || a.R == nullptr) return -1;
+    const bool rmap = a.rstride > 1;
+#define PF_STJ(NWV) do { if (!bwd) return stream_launch_t<NWV, false, false, false, false, true, false>(a, nsplit, st);         \
+                         return rmap ? stream_launch_t<NWV, false, true, false, false, true, true>(a, nsplit, st)              \
+                                     : stream_launch_t<NWV, false, true, false, false, false, true>(a, nsplit, st); } while (0)
+    if (nw == 64) PF_STJ(64);
+    if (nw == 256) PF_STJ(256);
+#undef PF_STJ
+    return stream_launch_t<128, false, false, false, false, true, false>(a, nsplit, st);
+  }
   if (a.oss != nullptr) {                                  // output affine: stride-1 forward launches (the caller falls back otherwise)
     if (map || bwd) return -1;
 #define PF_STA(NWV) do { return pro ? stream_launch_t<NWV, true, false, false, true>(a, nsplit, st)     \

@@ -46,6 +46,9 @@ struct IgArgs {
   // output affine of the row pass (pf_conv_common.h out_affine8): the consumer's inference-mode BN + activation; null: off
   const float* oss;     // scale | shift [2][N]
   int oact;
+  // compact residual (kernels instantiated with RMAP only; pf_conv_common.h rmap_row): R is [img][rHo][rWo][N] and belongs to the
+  // pixels (h, w) of the launch's dense [rH x rW] output grid with h % rstride == 0 and w % rstride == 0
+  int rHo, rWo, rH, rW, rstride;
 };
 
 template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }

@@ -77,9 +77,13 @@ __device__ __forceinline__ bf16x8 ig_codes_to_bf16x8(uint2 c) {
 #define PF_IG_XB 2
 #endif
 
-template <int BM, int BN, int WM, int WN, int NS, int MODE, bool SUB = false, bool AFF = false>
+// RMAP: the residual is COMPACT and read through the inverse row map (rmap_row, IgArgs.r*) -- the joined backward-data of a projection
+// block (pf_conv1x1_bwd_data_join); it changes the residual loads alone.  BR: IG_BWD with a residual (IG_BWD alone has none): the
+// residual lands on the accumulators, they are rounded once and staged, the row pass takes the BN-backward sums from the staged values.
+template <int BM, int BN, int WM, int WN, int NS, int MODE, bool SUB = false, bool AFF = false, bool RMAP = false, bool BR = false>
 __global__ __launch_bounds__(64 * WM * WN) void k_igemm(const IgArgs a) {
   constexpr bool BWD = (MODE == IG_BWD), PRO = (MODE == IG_PRO);
+  static_assert(!BR || BWD, "BR is a variant of IG_BWD");
   static_assert(!PRO || NS == 2 || NS == 3, "the in-LDS prologue pass is written for the 2- and 3-stage rings");
   // PRO with three stages: the loads of step ks+2 travel, the lanes transform their own vectors of step ks+1 in LDS and the
   // matrix cores multiply step ks -- all inside ONE barrier interval (round 2's two-stage form ran them back to back:
@@ -246,17 +250,23 @@ __global__ __launch_bounds__(64 * WM * WN) void k_igemm(const IgArgs a) {
     // (shortcut added to a raw convolution) pay.  The loads are issued at the top of the LAST k-step and travel under its
     // MFMAs (issued in the epilogue they cost 10-13 us per launch on the 14x14 / 7x7 conv3 layers).
     uint2 rr[NI][JM];
-    const bool has_r = !BWD && a.R != nullptr;
+    const bool has_r = BWD ? BR : (a.R != nullptr);
     constexpr bool RPRE = BM * BN <= 128 * 256;                       // larger tiles have no 32 spare registers: load at use
     auto load_residual = [&]() {
 #pragma unroll
       for (int j = 0; j < JM; ++j) {
         const int m = m0 + wm * WR + j * 16 + l15;
+        int64_t rrow = m;
+        bool live = m < a.M;
+        if constexpr (RMAP) {                                             // pixels without a partner: +0.0f, no load
+          rrow = live ? rmap_row(m, a.rHo, a.rWo, a.rH, a.rW, a.rstride) : -1;
+          live = rrow >= 0;
+        }
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
           const int n = n0 + wn * WC + i * 16 + q * 4;
           rr[i][j] = make_uint2(0, 0);
-          if (m < a.M && n < a.N) rr[i][j] = *reinterpret_cast<const uint2*>(a.R + (int64_t)m * a.N + n);
+          if (live && n < a.N) rr[i][j] = *reinterpret_cast<const uint2*>(a.R + rrow * a.N + n);
         }
       }
     };
@@ -469,11 +479,17 @@ __global__ __launch_bounds__(64 * WM * WN) void k_igemm(const IgArgs a) {
 #pragma unroll
         for (int j = 0; j < JM; ++j) {                                      // row block by row block: NI vectors live at a time
           const int m = m0 + wm * WR + j * 16 + l15;
+          int64_t rrow = m;
+          bool live = m < a.M;
+          if constexpr (RMAP) {
+            rrow = live ? rmap_row(m, a.rHo, a.rWo, a.rH, a.rW, a.rstride) : -1;
+            live = rrow >= 0;
+          }
 #pragma unroll
           for (int i = 0; i < NI; ++i) {
             const int n = n0 + wn * WC + i * 16 + q * 4;
-            if (m < a.M && n < a.N) {
-              const uint2 r = *reinterpret_cast<const uint2*>(a.R + (int64_t)m * a.N + n);
+            if (live && n < a.N) {
+              const uint2 r = *reinterpret_cast<const uint2*>(a.R + rrow * a.N + n);
               acc[i][j][0] += __uint_as_float(r.x << 16); acc[i][j][1] += __uint_as_float(r.x & 0xFFFF0000u);
               acc[i][j][2] += __uint_as_float(r.y << 16); acc[i][j][3] += __uint_as_float(r.y & 0xFFFF0000u);
             }
@@ -534,7 +550,7 @@ __global__ __launch_bounds__(64 * WM * WN) void k_igemm(const IgArgs a) {
     };
     constexpr bool etid = true;                                             // every thread takes part in the row passes
     float bpr[32];                                                          // BWD: this thread's 8 channels of scale | shift | mean | invstd
-    if (BWD) {
+    if (BWD && !BR) {
 #pragma unroll
       for (int qq = 0; qq < 4; ++qq)
 #pragma unroll
@@ -570,8 +586,10 @@ __global__ __launch_bounds__(64 * WM * WN) void k_igemm(const IgArgs a) {
             float f[8], xv[8];
             unpack8(c, f);
             unpack8(rres[pp], xv);
-            const float* bp = bpr;                                          // hoisted (below): hipcc re-reads the 8 vectors from LDS in every pass
-            constexpr int BPS = 8;
+            // hoisted (above): hipcc re-reads the 8 vectors from LDS in every pass -- which BR accepts: beside the residual's
+            // registers the hoisted copy takes the 128 x 128 tile past 256 registers (one workgroup per CU instead of two)
+            const float* bp = BR ? (bpl + wvec * 8) : bpr;
+            constexpr int BPS = BR ? BN : 8;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
               const float u = fmaf(bp[j], xv[j], bp[BPS + j]);
@@ -701,7 +719,7 @@ int pf_igemm_stats_groups(int M, int N, int pro) { return pf_igemm_stats_groups_
 /* deprecated for RxS convolutions: use pf_conv2d_stats_groups_geom (the kernel, and with it the row count, depends on the window) */
 extern "C" int pf_conv2d_stats_groups(int M, int N) { return pf_igemm_stats_groups(M, N, 0); }
 
-template <int BM, int BN, int WM, int WN, int NS, int MODE, bool SUB = false, bool AFF = false>
+template <int BM, int BN, int WM, int WN, int NS, int MODE, bool SUB = false, bool AFF = false, bool RMAP = false, bool BR = false>
 static int ig_launch_t(IgArgs& a, int slots, hipStream_t st) {
   constexpr bool BWD = (MODE == IG_BWD), PRO3 = (MODE == IG_PRO && NS == 3);
   constexpr int THREADS = 64 * WM * WN;
@@ -714,8 +732,8 @@ static int ig_launch_t(IgArgs& a, int slots, hipStream_t st) {
   const size_t lds = base + (BWD ? 4 * BN * 4 : 0) + (PRO3 ? 2 * (size_t)a.C * 4 : 0);
   if (PRO3 && a.C > CV_MAXK) return (int)hipErrorInvalidValue;
   const size_t lds_max = base + (BWD ? 4 * BN * 4 : 0) + (PRO3 ? 2 * (size_t)CV_MAXK * 4 : 0);
-  if (int e = pf_require_lds(reinterpret_cast<const void*>(&k_igemm<BM, BN, WM, WN, NS, MODE, SUB, AFF>), lds_max)) return e;
-  k_igemm<BM, BN, WM, WN, NS, MODE, SUB, AFF><<<grid, THREADS, lds, st>>>(a);
+  if (int e = pf_require_lds(reinterpret_cast<const void*>(&k_igemm<BM, BN, WM, WN, NS, MODE, SUB, AFF, RMAP, BR>), lds_max)) return e;
+  k_igemm<BM, BN, WM, WN, NS, MODE, SUB, AFF, RMAP, BR><<<grid, THREADS, lds, st>>>(a);
   PF_LAUNCH_CHECK();
   return 0;
 }
@@ -798,6 +816,7 @@ static int conv2d_fwd_launch(const void* X, const void* W, void* Y, const void* 
   a.w_r0 = 0; a.w_rs = 1; a.w_s0 = 0; a.w_ss = 1; a.w_S = tw; a.w_taps_full = th * tw;
   a.o_sub = 0; a.o_y = 0; a.o_x = 0; a.o_H = 0; a.o_W = 0;
   a.oss = out_scale_shift; a.oact = out_act;
+  a.rHo = 0; a.rWo = 0; a.rH = 0; a.rW = 0; a.rstride = 1;
   return ig_launch(a, (hipStream_t)stream);
 }
 
@@ -900,6 +919,7 @@ static int strided_launch(const void* dY, const void* Wt, void* dX, const void* 
       a.w_s0 = (S - 1 - s1) - (tw - 1) * stride; a.w_ss = stride;
       a.w_S = S; a.w_taps_full = R * S;
       a.o_sub = stride; a.o_y = ay; a.o_x = ax; a.o_H = H; a.o_W = Wd; a.oss = nullptr; a.oact = PF_ACT_NONE;
+      a.rHo = 0; a.rWo = 0; a.rH = 0; a.rW = 0; a.rstride = 1;
       // (the two plain tile configurations the dispatcher picks for these shapes, with the sub-grid walk compiled in)
       int rc;
       if (bn_x != nullptr)
@@ -933,13 +953,21 @@ extern "C" int pf_conv2d_bwd_data_strided_bnstats(const void* dY, const void* Wt
                         bn_scale_shift, bn_mean_invstd, bn_act);
 }
 
+// the shapes whose joined backward-data (a residual through the inverse row map, the BN-backward sums beside a residual) this file
+// carries: those the dispatcher gives its default 128-row tiles (a PF_IGEMM_TILE override selects kernels without the variants)
+bool pf_igemm_join_ok(int M, int N, int K) {
+  if ((K % 64) || (N % 64) || (int64_t)M * K >= ((int64_t)1 << 30) || (int64_t)N * K >= ((int64_t)1 << 30)) return false;
+  const IgCfg c = ig_pick(M, N, false);
+  return c.bm == 128 && c.slots == 512 && c.bn == ((N % 128 == 0) ? 128 : 64);
+}
+
 // 1x1 convolutions through the same kernel (called by pf_conv.hip for the shapes it routes here): plain, backward-data with
 // BN-backward sums, or with the producer's BN/act/fake-quant prologue; stride > 1 reads input pixel (ho*stride, wo*stride).
 // No tap ever leaves the image, `zero` is unused.
 int pf_igemm_conv1x1(const void* X, const void* W, void* Y, const void* R, float* partial, const void* bn_x,
                      const float* bss, const float* bmi, float b_lo, float b_hi, const float* scale_shift,
                      const uint32_t* slot, float kq, float act_lo, float act_hi, int M, int N, int K, int Ho, int Wo,
-                     int H, int Wd, int stride, const float* oss, int oact, hipStream_t st, int ymap) {
+                     int H, int Wd, int stride, const float* oss, int oact, hipStream_t st, int ymap, const int* rgeom) {
   int64_t rows_in = M;
   if (stride > 1 && !ymap) rows_in = (int64_t)(M / (Ho * Wo)) * H * Wd;
   if ((K % 64) || rows_in * K >= ((int64_t)1 << 30) || (int64_t)N * K >= ((int64_t)1 << 30)) return -1;
@@ -961,6 +989,21 @@ int pf_igemm_conv1x1(const void* X, const void* W, void* Y, const void* R, float
   a.w_r0 = 0; a.w_rs = 1; a.w_s0 = 0; a.w_ss = 1; a.w_S = 1; a.w_taps_full = 1;
   a.o_sub = 0; a.o_y = 0; a.o_x = 0; a.o_H = 0; a.o_W = 0;
   a.oss = oss; a.oact = oact;
+  a.rHo = 0; a.rWo = 0; a.rH = 0; a.rW = 0; a.rstride = 1;
+  if (rgeom != nullptr) {
+    // the joined backward-data of a projection block (pf_conv1x1_bwd_data_join): rgeom = {Ho, Wo, H, W, stride} of the residual
+    // (stride 1: dense), with the BN-backward sums when bn_x is given.  The dispatcher's default 128-row tiles carry the variants.
+    if (!pf_igemm_join_ok(M, N, K) || ymap || stride != 1 || R == nullptr || scale_shift != nullptr || oss != nullptr) return -1;
+    a.rHo = rgeom[0]; a.rWo = rgeom[1]; a.rH = rgeom[2]; a.rW = rgeom[3]; a.rstride = rgeom[4];
+    const bool rmap = a.rstride > 1, bwd = bn_x != nullptr, wide = (N % 128 == 0);
+    if (!rmap && !bwd) return ig_launch(a, st);                          // dense residual, no sums: the plain launch has it
+    if (!bwd) return wide ? ig_launch_t<128, 128, 2, 2, 2, IG_PLAIN, false, false, true, false>(a, 512, st)
+                          : ig_launch_t<128, 64, 2, 2, 2, IG_PLAIN, false, false, true, false>(a, 512, st);
+    if (rmap) return wide ? ig_launch_t<128, 128, 2, 2, 2, IG_BWD, false, false, true, true>(a, 512, st)
+                          : ig_launch_t<128, 64, 2, 2, 2, IG_BWD, false, false, true, true>(a, 512, st);
+    return wide ? ig_launch_t<128, 128, 2, 2, 2, IG_BWD, false, false, false, true>(a, 512, st)
+                : ig_launch_t<128, 64, 2, 2, 2, IG_BWD, false, false, false, true>(a, 512, st);
+  }
   if (ymap) {
     // row (img, i, j) of the dense [Ho x Wo] grid goes to pixel (i * stride, j * stride) of the [H x Wd] image: the scatter of the
     // parity-class launches with class (0, 0); the other pixels keep the zeros the caller wrote

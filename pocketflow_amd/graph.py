@@ -710,6 +710,8 @@ class LazyAct(object):
     self.n_grad_consumers = 0                 # ... of which take part in the backward pass
     self.pending = None                       # dq of the first of TWO consumers, waiting to be joined by the second
     self.join_ok = False                      # set by the caller that KNOWS both consumers reach the loss (see _FusedConv1x1)
+    self.pending_geom = None                  # geometry of a COMPACT parked gradient (a strided first consumer), else None
+    self.dense_out = None                     # output channels of the stride-1 fused consumer that takes part in the backward pass
     self._q = None
 
   @property
@@ -976,10 +978,6 @@ class _FusedConv1x1(torch.autograd.Function):
       dw = _filter_grad(graph, ctx.w_leaf, ctx.w_var, (dy, x, w2d, ss, lazy), 'conv1x1_wrw', float((M * K + M * N) * 2), wrw)
     if ctx.needs_input_grad[0]:
       wt = _bwd_data_weight(graph, ctx.w_var, ctx.w_leaf).view(K, N)           # [K][N]
-      if geom is None:
-        dx = torch.empty_like(x)
-      else:
-        dx = torch.zeros_like(x)
       fuse_stats = (FUSE_BN_BWD_STATS and lazy is not None and lazy.n_consumers == 1 and geom is None
                     and lazy.mean_invstd is not None and lazy.act in ('Relu', 'Relu6'))
       # An activation with exactly TWO fused consumers (bn1 of a projection block: shortcut convolution + conv1): the
@@ -993,8 +991,35 @@ class _FusedConv1x1(torch.autograd.Function):
               and lazy.n_grad_consumers == 2)
       second = join and lazy.pending is not None
       res = lazy.pending if (second and geom is None) else None
+      # The projection join (pf_conv1x1_bwd_data_join), where the loaded library offers it and its plan takes the dense consumer's
+      # shape: a strided first consumer parks a COMPACT [B][K][Ho][Wo] gradient -- a plain dense GEMM, no zero fill, no row scatter --
+      # which the second reads through the inverse row map; and the second takes the BN-backward sums of the joined gradient in
+      # the same launch, so that _BnLazy.backward finds them (lazy.bwd_stats) and skips its statistics pass.
+      join_entry = getattr(hip, 'conv1x1_bwd_data_join', None) if PROJ_JOIN else None
+      compact = (join and not second and geom is not None and join_entry is not None and lazy.dense_out is not None
+                 and hip.conv1x1_join_plan(x.shape[0] * x.shape[2] * x.shape[3], lazy.dense_out, K) != 0)
+      rgeom = lazy.pending_geom if res is not None else None
+      join_stats = (res is not None and join_entry is not None and PROJ_JOIN_STATS and FUSE_BN_BWD_STATS
+                    and lazy.mean_invstd is not None and lazy.act in ('Relu', 'Relu6')
+                    and hip.conv1x1_join_plan(M, N, K, True) != 0)
+      if compact:
+        dx = torch.empty((x.shape[0], K, geom[0], geom[1]), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+      elif geom is None:
+        dx = torch.empty_like(x)
+      else:
+        dx = torch.zeros_like(x)
       with region('conv1x1_bwd_data', float((M * K * (2 if (fuse_stats or res is not None) else 1) + M * N) * 2)):
-        if fuse_stats:
+        if compact:
+          hip.conv1x1_fwd(dy, wt, dx, M, K, N)
+        elif join_stats:
+          G = hip.conv1x1_stats_groups(M, K, N)
+          partial = torch.empty((G, 2, K), dtype=torch.float32, device=x.device)
+          join_entry(dy, wt, dx, res, M, N, K, rgeom=rgeom, bn_x=x, bn_scale_shift=lazy.scale_shift,
+                     bn_mean_invstd=lazy.mean_invstd, bn_act=lazy.act, partial=partial)
+          lazy.bwd_stats = (partial, G, dx.data_ptr())
+        elif rgeom is not None:
+          join_entry(dy, wt, dx, res, M, N, K, rgeom=rgeom)
+        elif fuse_stats:
           G = hip.conv1x1_stats_groups(M, K, N)
           partial = torch.empty((G, 2, K), dtype=torch.float32, device=x.device)
           hip.conv1x1_bwd_data_bnstats(dy, wt, dx, x, lazy.scale_shift, lazy.mean_invstd, lazy.act, partial, M, N, K)
@@ -1006,15 +1031,20 @@ class _FusedConv1x1(torch.autograd.Function):
       if join:
         if not second:
           lazy.pending, dx = dx, None           # parked: the second consumer delivers the sum
+          lazy.pending_geom = geom if compact else None
         else:
           if res is None:
             dx = dx + lazy.pending              # the second one is the strided one: no residual operand under a row map
-          lazy.pending = None
+          lazy.pending = lazy.pending_geom = None
     return dx, dw, (dy if has_res else None), None, None, None, None, None, None
 
 
 # two fused consumers of one activation: join their input gradients inside the second backward-data kernel (0: autograd add)
 JOIN_TWO_CONSUMERS = os.environ.get('PF_JOIN_TWO_CONSUMERS', '1') != '0'
+# projection blocks: the strided shortcut's input gradient stays compact and conv1's backward-data reads it through the inverse row
+# map (0: the zero-filled full-size tensor and the row scatter); ..._STATS: the BN-backward sums of bn1 in that launch (0: pf_bn_bwd_stats)
+PROJ_JOIN = os.environ.get('PF_PROJ_JOIN', '1') != '0'
+PROJ_JOIN_STATS = os.environ.get('PF_PROJ_JOIN_STATS', '1') != '0'
 USE_SEG_TRANSPOSE = os.environ.get('PF_SEG_TRANSPOSE', '1') != '0'   # backward-data kernel layouts in one launch (0: aten)
 OWN_POOL = os.environ.get('PF_OWN_POOL', '1') != '0'         # stem max-pooling on pf_pool.hip (0: aten, for A/B runs)
 # backward-filter of the RxS convolutions on pf_wrw.hip (shared-tile kernel); PF_OWN_CONV2D_WRW=0: MIOpen, for A/B runs
@@ -1500,6 +1530,8 @@ class Conv2D:
       if torch.is_grad_enabled() and (xin.requires_grad or w.requires_grad):
         if lazy is not None and xin.requires_grad:
           lazy.n_grad_consumers += 1
+          if self.stride == 1:
+            lazy.dense_out = int(w.shape[0])
         return _apply_with_stats(_FusedConv1x1, xin, w, residual, lazy, want_stats, self.stride, self.graph, self.kernel)
       w2d = w.detach().permute(0, 2, 3, 1).reshape(w.shape[0], w.shape[1])
       return _run_conv1x1(xin, w2d, lazy, _nhwc(residual) if residual is not None else None, want_stats,

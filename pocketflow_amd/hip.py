@@ -54,6 +54,7 @@ SYMBOLS = [
     'pf_conv2d_bwd_data_strided_bnstats',
     'pf_cpr_gather', 'pf_cpr_gram_ws', 'pf_cpr_gram', 'pf_cpr_ista', 'pf_cpr_lstsq_splits', 'pf_cpr_lstsq_step', 'pf_cpr_lstsq_resid',
     'pf_conv_gather_fwd',
+    'pf_conv1x1_join_plan', 'pf_conv1x1_bwd_data_join',
 ]
 
 
@@ -502,6 +503,26 @@ def conv1x1_bwd_data_bnstats(dY, Wt, dQ, bn_x, bn_scale_shift, bn_mean_invstd, b
   _check(_lib.pf_conv1x1_bwd_data_bnstats(_ptr(dY), _ptr(Wt), _ptr(dQ), _ptr(bn_x), _ptr(bn_scale_shift),
                                           _ptr(bn_mean_invstd), c_int(ACT_CODES[bn_act]), _ptr(partial), c_int(M),
                                           c_int(N), c_int(K), _stream()), 'pf_conv1x1_bwd_data_bnstats')
+
+
+def conv1x1_join_plan(M: int, N: int, K: int, with_stats: bool = False) -> int:
+  """Non-zero when conv1x1_bwd_data_join takes dQ[M][K] = dY[M][N] * W + R (1: resident-kernel variant, 2: staged GEMM);
+  `with_stats`: with the BN-backward sums in the same launch."""
+  return int(_lib.pf_conv1x1_join_plan(c_int(M), c_int(N), c_int(K), c_int(1 if with_stats else 0)))
+
+
+def conv1x1_bwd_data_join(dY, Wt, dQ, R, M: int, N: int, K: int, rgeom=None, bn_x=None, bn_scale_shift=None,
+                          bn_mean_invstd=None, bn_act=None, partial=None) -> None:
+  """Backward-data of a stride-1 1x1 convolution joined with the gradient R of the activation's other consumer:
+  dQ = bf16(dY * W + R).  rgeom = (Ho, Wo, H, Wd, stride): R is the COMPACT [B][Ho][Wo][K] gradient a strided consumer left (rows
+  without a partner receive +0.0); None: R is dense [M][K].  bn_x (with scale_shift / mean_invstd / act and partial [G][2][K],
+  G = conv1x1_stats_groups(M, K, N)): the BN-backward sums of the joined dQ, as conv1x1_bwd_data_bnstats."""
+  _dev(dY)
+  Ho, Wo, H, Wd, stride = rgeom if rgeom is not None else (0, 0, 0, 0, 1)
+  _check(_lib.pf_conv1x1_bwd_data_join(_ptr(dY), _ptr(Wt), _ptr(dQ), _ptr(R), c_int(Ho), c_int(Wo), c_int(H), c_int(Wd),
+                                       c_int(stride), _ptr(bn_x), _ptr(bn_scale_shift), _ptr(bn_mean_invstd),
+                                       c_int(ACT_CODES[bn_act]), _ptr(partial), c_int(M), c_int(N), c_int(K), _stream()),
+         'pf_conv1x1_bwd_data_join')
 
 
 # ------------------------------------------------------------------------------------------------
