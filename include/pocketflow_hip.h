@@ -228,10 +228,11 @@ int pf_bn_eval_scale_shift(const float* gamma, const float* beta, const float* m
  * pf_conv1x1_wrw:  dW[n][k] = sum_m dY[m][n] * Q(X)[row(m)][k], dW float32 or bf16 [N][K];
  *   workspace: (pf_conv1x1_wrw_splits(M, N, K) + 32) * N * K floats (deterministic staged reduction).
  * Requirements: K % 8 == 0, N % 8 == 0, 16-byte aligned pointers; hipErrorInvalidValue otherwise.     */
-int pf_conv1x1_stats_groups(int M, int N);
-/* G of the partial-statistics array for an [M][K] x [N][K] problem: shapes whose kernel fits the LDS (K, N <= 512,
- * K * N <= 64 Ki) run on the barrier-free resident-kernel variant (pf_conv_stream.hip), prologue-free shapes with
- * K >= 512 on the direct-to-LDS staged GEMM (pf_igemm.hip); each has its own G.  prologue: scale_shift != NULL.  */
+/* G of the partial-statistics array for an [M][K] x [N][K] problem.  Three kernels serve these products (the barrier-free
+ * resident-kernel variant, the direct-to-LDS staged GEMM, the register-staged tiles), each with its own G; ONE host-side plan
+ * names the kernel, and this query and the launch both read it, so the rows a launch writes are the rows this names.
+ * prologue: scale_shift != NULL.  The query reads a stride-1 launch; a launch whose row map moves it to a kernel with another
+ * G (an input beyond a kernel's 31-bit addressing) returns hipErrorInvalidValue and writes nothing.                         */
 int pf_conv1x1_stats_groups_k(int M, int N, int K, int prologue);
 int pf_conv1x1_fwd(const void* X, const void* W, void* Y, const void* R, const float* scale_shift,
                    int act, const uint32_t* slot, int bits, float* partial, int M, int N, int K,
@@ -290,10 +291,7 @@ int pf_conv1x1_wrw(const void* dY, const void* X, void* dW, int dw_dtype, float*
  *   (dy = Y * act'(scale*x + shift)), as pf_conv1x1_bwd_data_bnstats.
  *   Backward-data of a stride-1 convolution is the same call on dY with the kernel flipped and transposed:
  *   W'[c][r][s][n] = W[n][th-1-r][tw-1-s][c], pad' = th-1-pad.                                                      */
-/* rows G of the statistics array for a 1x1 product of M x N outputs (DEPRECATED for R x S convolutions: the tile, and with it G,
- * depends on the geometry) */
-int pf_conv2d_stats_groups(int M, int N);
-/* rows G for the pf_conv2d_fwd call with these arguments: the ONLY valid query for R x S convolutions                          */
+/* rows G for the pf_conv2d_fwd call with these arguments (the kernel, and with it G, depends on the geometry)                 */
 int pf_conv2d_stats_groups_geom(int imgs, int H, int Wd, int C, int N, int th, int tw, int stride, int pad_h, int pad_w,
                                 int Ho, int Wo);
 int pf_conv2d_fwd(const void* X, const void* W, void* Y, const void* zero, const void* R, float* partial,

@@ -302,40 +302,12 @@ static int conv_bn_of(int N) {
   return (N % 128 == 0) ? 128 : 64;
 }
 
-static int conv_fwd_grid(int tiles_m, int tiles_n, int* G_out) {
-  // ~2 workgroups per CU (256 CUs); G is a multiple of 8 so that a row panel's column tiles share an XCD
-  int G = 512 / tiles_n;
-  G = (G / 8) * 8;
-  if (G < 8) G = 8;
-  const int need = ((tiles_m + 7) / 8) * 8;
-  if (G > need) G = need;
-  *G_out = G;
-  return G * tiles_n;
-}
+// the other kernels' parts of the plan, and their launchers (a: filled here, p: conv1x1_plan's answer)
+bool pf_conv_stream_plan(const Conv1x1Req& q, Conv1x1Plan* p);     // pf_conv_stream.hip: the barrier-free variant for kernels that fit the LDS
+int pf_conv_stream_launch(const ConvArgs& a, const Conv1x1Plan& p, hipStream_t st);
+bool pf_igemm_conv1x1_plan(const Conv1x1Req& q, Conv1x1Plan* p);   // pf_igemm.hip: direct-to-LDS staged GEMM
+int pf_igemm_conv1x1(const ConvArgs& a, const Conv1x1Plan& p, hipStream_t st);
 
-// pf_conv_stream.hip: the barrier-free variant for kernels that fit the LDS
-int pf_conv_stream_plan(int M, int N, int K, int* nw_out);
-int pf_conv_stream_groups(int nsplit);
-int pf_conv_stream_launch(const ConvArgs& a, bool pro, bool bwd, hipStream_t st);
-bool pf_conv_stream_join_ok(int nw, bool with_stats);
-
-extern "C" int pf_conv1x1_stats_groups(int M, int N) {
-  const int bn = conv_bn_of(N);
-  int G;
-  conv_fwd_grid((M + CV_BM - 1) / CV_BM, (N + bn - 1) / bn, &G);
-  return G;
-}
-
-// rows of the [G][stats][N] partial-statistics array pf_conv1x1_fwd / pf_conv1x1_bwd_data_bnstats write for an
-// [M][K] x [N][K] problem (depends on which kernel the shape is dispatched to)
-// pf_igemm.hip: direct-to-LDS staged GEMM for the prologue-free shapes with a deep contraction
-extern "C" int pf_conv2d_stats_groups(int M, int N);
-int pf_igemm_stats_groups(int M, int N, int pro);           // the launcher's own tile decision (prologue variant or not)
-int pf_igemm_conv1x1(const void* X, const void* W, void* Y, const void* R, float* partial, const void* bn_x,
-                     const float* bss, const float* bmi, float b_lo, float b_hi, const float* scale_shift,
-                     const uint32_t* slot, float kq, float act_lo, float act_hi, int M, int N, int K, int Ho, int Wo,
-                     int H, int Wd, int stride, const float* oss, int oact, hipStream_t st, int ymap = 0, const int* rgeom = nullptr);
-bool pf_igemm_join_ok(int M, int N, int K);
 // Which 1x1 shapes go to the direct-to-LDS staged kernel (after the resident-kernel variant had its pick).  Measured
 // (tools/gpu/igemm_bench.py, conv_bench2.py): prologue-free GEMMs win from K = 512 up; with the prologue the in-LDS pass
 // behind asynchronous staging beats the register-staged tiles of this file on every shape it was tried on.
@@ -349,129 +321,154 @@ static bool conv_use_igemm(bool pro, int K) {
   return (K % 64) == 0 && (pro || K >= PF_CONV_IGEMM_PLAIN_MINK);
 }
 
+// THE decision of the 1x1 forward / backward-data family: which kernel takes the launch, in which configuration, and how many rows G
+// of statistics it writes.  The launch (conv_fwd_launch) and the queries that size the caller's arrays read this one answer.
+static Conv1x1Plan conv1x1_plan(const Conv1x1Req& q) {
+  Conv1x1Plan p = {};                                     // kernel = CONV_NONE
+  if (pf_conv_stream_plan(q, &p)) return p;              // HBM-bound shapes: kernel resident in LDS
+  // the staged GEMM.  Behind an output row map it has the backward-data of a strided projection alone (dense dY rows scattered to
+  // (ho * stride, wo * stride) of a pre-zeroed dX, nothing else attached; round 6: the tiles of this file ran these at 106 us)
+  const bool scatter = q.ymap && q.map && !q.pro && !q.bwd && !q.res && !q.stats;
+  if ((!q.ymap || scatter) && conv_use_igemm(q.pro, q.K) && pf_igemm_conv1x1_plan(q, &p)) return p;
+  // the register-staged tiles of this file carry neither the variants of the joined backward-data, which runs on the kernel its
+  // shape names or not at all, ...
+  if (q.join) return p;
+  if (q.aff) {
+    // ... nor the folded output pass: whatever takes the plain launch, then the stand-alone pass IN PLACE (same result, one more
+    // read + write of Y)
+    Conv1x1Req plain = q;
+    plain.aff = false;
+    p = conv1x1_plan(plain);
+    p.affine_after = true;
+    return p;
+  }
+  p.kernel = CONV_TILES;
+  p.bn = conv_bn_of(q.N);
+  p.grid = pf_conv_grid(512, (q.M + CV_BM - 1) / CV_BM, (q.N + p.bn - 1) / p.bn, &p.G);     // ~2 workgroups per CU
+  return p;
+}
+
+// what a query knows of a launch: the GEMM and whether it carries the prologue -- stride 1, nothing else attached
+static Conv1x1Req conv_query_req(int M, int N, int K, bool pro) {
+  Conv1x1Req q = {};
+  q.M = M; q.N = N; q.K = K; q.rows_in = M; q.rows_out = M; q.pro = pro; q.stats = true;
+  return q;
+}
+
+// Rows G of the [G][.][N] partial-statistics array pf_conv1x1_fwd / pf_conv1x1_bwd_data_bnstats / pf_conv1x1_bwd_data_join write for
+// an [M][K] x [N][K] problem: the G of the plan of the stride-1 launch with these dimensions.  A launch whose own plan has another G
+// (its row map makes X exceed a kernel's addressing, say) refuses with hipErrorInvalidValue and writes nothing.
 extern "C" int pf_conv1x1_stats_groups_k(int M, int N, int K, int prologue) {
-  int nw = 0;
-  const int nsplit = pf_conv_stream_plan(M, N, K, &nw);
-  if (nsplit > 0) return pf_conv_stream_groups(nsplit);
-  if (conv_use_igemm(prologue != 0, K)) return pf_igemm_stats_groups(M, N, prologue != 0);
-  return pf_conv1x1_stats_groups(M, N);
+  return conv1x1_plan(conv_query_req(M, N, K, prologue != 0)).G;
 }
 
-// Which kernel takes the joined backward-data dQ[M][K] = dY[M][N] * Wt + R (pf_conv1x1_bwd_data_join; the GEMM it launches is
-// [M][N] x [K][N]): 1 = the resident-kernel variant, 2 = the staged GEMM, 0 = none (the register-staged tiles of this file carry
-// neither the inverse row map nor the sums beside a residual: such shapes stay on the separate launches).
-static int conv_join_kernel(int M, int N, int K, bool with_stats) {
-  if (M <= 0 || N <= 0 || K <= 0) return 0;
-  int nw = 0;
-  if (pf_conv_stream_plan(M, K, N, &nw) > 0) return pf_conv_stream_join_ok(nw, with_stats) ? 1 : 0;
-  if (conv_use_igemm(false, N) && pf_igemm_join_ok(M, K, N)) return 2;
-  return 0;
-}
-
-// ... and whether the caller SHOULD ask for the sums in that launch: on the staged GEMM they pay from about 2^17 rows up (measured at
-// batch 256, profiles/proj_join_ab.txt: 28 x 28, 256 -> 512: 184 us against 147 + 81 for the join and the separate pass; 14 x 14,
+// Which kernel takes the joined backward-data dQ[M][K] = dY[M][N] * Wt + R (pf_conv1x1_bwd_data_join; its launch is the GEMM
+// [M][N] x [K][N]): 1 = the resident-kernel variant, 2 = the staged GEMM, 0 = none: such shapes stay on the separate launches.
+// On top of the plan, advice: whether the caller SHOULD ask for the sums in that launch.  On the staged GEMM they pay from about 2^17
+// rows up (measured at batch 256, profiles/proj_join_ab.txt: 28 x 28, 256 -> 512: 184 us against 147 + 81 for the join and the separate pass; 14 x 14,
 // 512 -> 1024: 125 against 86 + 34 -- six tiles per workgroup leave the BN-input loads of the row pass nothing to hide behind).
-// Below that the plan refuses `with_stats` and the shape keeps pf_bn_bwd_stats; the entry itself runs whatever the kernels carry.
+// Below that the query refuses `with_stats` and the shape keeps pf_bn_bwd_stats; the entry itself runs whatever the kernels carry.
 #define PF_JOIN_STATS_IGEMM_MIN_M (1 << 17)
 extern "C" int pf_conv1x1_join_plan(int M, int N, int K, int with_stats) {
-  const int k = conv_join_kernel(M, N, K, with_stats != 0);
-  if (k == 2 && with_stats && M < PF_JOIN_STATS_IGEMM_MIN_M) return 0;
-  return k;
+  if (M <= 0 || N <= 0 || K <= 0) return 0;
+  Conv1x1Req q = conv_query_req(M, K, N, false);
+  q.res = true; q.join = true; q.bwd = q.stats = with_stats != 0;
+  const int kernel = conv1x1_plan(q).kernel;
+  if (kernel == CONV_IGEMM) return (with_stats && M < PF_JOIN_STATS_IGEMM_MIN_M) ? 0 : 2;
+  return kernel == CONV_STREAM ? 1 : 0;
 }
 
-static int conv_fwd_launch(const void* X, const void* W, void* Y, const void* R, const float* scale_shift,
-                           int act, const uint32_t* slot, int bits, float* partial, int M, int N, int K,
-                           int Ho, int Wo, int H, int Wd, int stride, int ymap, const void* bx,
-                           const float* bss, const float* bmi, int bact, void* stream, const float* oss = nullptr,
-                           int oact = PF_ACT_NONE, const int* rgeom = nullptr) {
-  // rgeom = {Ho, Wo, H, W, stride} of the residual: the joined backward-data of a projection block (pf_conv1x1_bwd_data_join below)
-  if (oss != nullptr && (R != nullptr || partial != nullptr || bx != nullptr || ymap)) return (int)hipErrorInvalidValue;
-  if (M <= 0 || N <= 0 || K <= 0 || (K % 8) || (N % 8)) return (int)hipErrorInvalidValue;
-  if (!pf_aligned16(X) || !pf_aligned16(W) || !pf_aligned16(Y) || (R && !pf_aligned16(R)))
-    return (int)hipErrorInvalidValue;
-  if (slot != nullptr && (bits < 1 || bits > 32 || scale_shift == nullptr)) return (int)hipErrorInvalidValue;
-  if (scale_shift != nullptr && K > CV_MAXK) return (int)hipErrorInvalidValue;
-  if (stride < 1 || (stride > 1 && (Ho <= 0 || Wo <= 0 || H <= 0 || Wd <= 0))) return (int)hipErrorInvalidValue;
+// A ConvArgs with nothing attached: the stride-1 product Y[M][N] = X[M][K] * W[N][K]^T.  The entries add what they carry:
+// the producer's BN + activation (+ fake-quant, slot != null) on the input operand, a row map, the BN-backward sums.
+static ConvArgs conv_args(const void* X, const void* W, void* Y, int M, int N, int K) {
   ConvArgs a;
-  a.X = (const bf16_t*)X; a.W = (const bf16_t*)W; a.Y = (bf16_t*)Y; a.R = (const bf16_t*)R;
-  a.ss = scale_shift; a.slot = slot; a.partial = partial;
-  a.kq = uq_k_of_bits(slot ? bits : 8);
-  a.act_lo = (act == PF_ACT_NONE) ? -INFINITY : 0.0f;
-  a.act_hi = (act == PF_ACT_RELU6) ? 6.0f : INFINITY;
-  a.M = M; a.N = N; a.K = K;
-  a.Ho = Ho; a.Wo = Wo; a.H = H; a.Wd = Wd; a.stride = stride; a.ymap = ymap; a.rows_per_split = 0;
-  a.bx = (const bf16_t*)bx; a.bss = bss; a.bmi = bmi;
-  a.b_lo = (bact == PF_ACT_NONE) ? -INFINITY : 0.0f;
-  a.b_hi = (bact == PF_ACT_RELU6) ? 6.0f : INFINITY;
-  a.oss = oss; a.oact = oact;
+  a.X = (const bf16_t*)X; a.W = (const bf16_t*)W; a.Y = (bf16_t*)Y; a.R = nullptr;
+  a.ss = nullptr; a.slot = nullptr; a.partial = nullptr;
+  a.kq = uq_k_of_bits(8); a.act_lo = -INFINITY; a.act_hi = INFINITY;
+  a.M = M; a.N = N; a.K = K; a.tiles_m = 0; a.tiles_n = 0; a.G = 0;
+  a.Ho = 0; a.Wo = 0; a.H = 0; a.Wd = 0; a.stride = 1; a.ymap = 0; a.rows_per_split = 0;
+  a.bx = nullptr; a.bss = nullptr; a.bmi = nullptr; a.b_lo = -INFINITY; a.b_hi = INFINITY;
+  a.oss = nullptr; a.oact = PF_ACT_NONE;
   a.rHo = 0; a.rWo = 0; a.rH = 0; a.rW = 0; a.rstride = 1;
-  if (rgeom != nullptr) { a.rHo = rgeom[0]; a.rWo = rgeom[1]; a.rH = rgeom[2]; a.rW = rgeom[3]; a.rstride = rgeom[4]; }
-  if (bx != nullptr && ((R != nullptr && rgeom == nullptr) || partial == nullptr || bss == nullptr || bmi == nullptr || stride != 1 ||
-                        !pf_aligned16(bx)))
+  return a;
+}
+static void conv_args_prologue(ConvArgs& a, const float* scale_shift, int act, const uint32_t* slot, int bits) {
+  a.ss = scale_shift; a.slot = slot;
+  a.kq = uq_k_of_bits(slot ? bits : 8);
+  pf_act_window(act, &a.act_lo, &a.act_hi);
+}
+static void conv_args_rowmap(ConvArgs& a, int Ho, int Wo, int H, int Wd, int stride, int ymap) {
+  a.Ho = Ho; a.Wo = Wo; a.H = H; a.Wd = Wd; a.stride = stride; a.ymap = ymap;
+}
+static void conv_args_bnstats(ConvArgs& a, const void* bn_x, const float* bss, const float* bmi, int bn_act, float* partial) {
+  a.bx = (const bf16_t*)bn_x; a.bss = bss; a.bmi = bmi; a.partial = partial;
+  pf_act_window(bn_act, &a.b_lo, &a.b_hi);
+}
+
+// join: R is the second consumer's gradient of pf_conv1x1_bwd_data_join, laid out as a.r* say
+static int conv_fwd_launch(ConvArgs a, bool join, void* stream) {
+  const bool pro = a.ss != nullptr, bwd = a.bx != nullptr;
+  if (a.oss != nullptr && (a.R != nullptr || a.partial != nullptr || bwd || a.ymap)) return (int)hipErrorInvalidValue;
+  if (a.M <= 0 || a.N <= 0 || a.K <= 0 || (a.K % 8) || (a.N % 8)) return (int)hipErrorInvalidValue;
+  if (!pf_aligned16(a.X) || !pf_aligned16(a.W) || !pf_aligned16(a.Y) || (a.R && !pf_aligned16(a.R)))
     return (int)hipErrorInvalidValue;
-  const int bn = conv_bn_of(N);
-  a.tiles_m = (M + CV_BM - 1) / CV_BM;
-  a.tiles_n = (N + bn - 1) / bn;
-  const int grid = conv_fwd_grid(a.tiles_m, a.tiles_n, &a.G);
+  if (pro && a.K > CV_MAXK) return (int)hipErrorInvalidValue;
+  if (a.stride < 1 || (a.stride > 1 && (a.Ho <= 0 || a.Wo <= 0 || a.H <= 0 || a.Wd <= 0))) return (int)hipErrorInvalidValue;
+  if (bwd && ((a.R != nullptr && !join) || a.partial == nullptr || a.bss == nullptr || a.bmi == nullptr || a.stride != 1 || pro ||
+              !pf_aligned16(a.bx)))
+    return (int)hipErrorInvalidValue;
+  if (join && (pro || a.ymap || a.stride != 1 || a.oss != nullptr || a.R == nullptr)) return (int)hipErrorInvalidValue;
+
+  Conv1x1Req q = {};
+  q.M = a.M; q.N = a.N; q.K = a.K; q.rows_in = a.M; q.rows_out = a.M;
+  q.pro = pro; q.bwd = bwd; q.res = a.R != nullptr; q.join = join; q.stats = a.partial != nullptr;
+  q.map = a.stride > 1; q.ymap = a.ymap != 0; q.aff = a.oss != nullptr;
+  if (q.map) (q.ymap ? q.rows_out : q.rows_in) = (int64_t)(a.M / (a.Ho * a.Wo)) * a.H * a.Wd;
+  const Conv1x1Plan p = conv1x1_plan(q);
+  if (p.kernel == CONV_NONE) return (int)hipErrorInvalidValue;
+  // the caller sized `partial` by pf_conv1x1_stats_groups_k, which reads (M, N, K, prologue) alone; this launch knows more (its row
+  // map).  Where that moves the launch to a kernel with another G, it does not write rows the caller did not allocate.
+  if (a.partial != nullptr && conv1x1_plan(conv_query_req(a.M, a.N, a.K, pro)).G != p.G) return (int)hipErrorInvalidValue;
+
   hipStream_t st = (hipStream_t)stream;
-  const bool pro = scale_shift != nullptr;
-  if (bx != nullptr && pro) return (int)hipErrorInvalidValue;
-  if (rgeom != nullptr) {
-    // exactly the kernel conv_join_kernel names (pf_conv1x1_stats_groups_k sizes `partial` by the same decision); no other kernel
-    // carries these variants
-    if (pro || ymap || stride != 1 || oss != nullptr || R == nullptr) return (int)hipErrorInvalidValue;
-    const int plan = conv_join_kernel(M, K, N, bx != nullptr);           // this launch: [M][K] x [N][K], N = the channels of dQ
-    int r = -1;
-    if (plan == 1) r = pf_conv_stream_launch(a, false, bx != nullptr, st);
-    else if (plan == 2) r = pf_igemm_conv1x1(X, W, Y, R, partial, bx, bss, bmi, a.b_lo, a.b_hi, nullptr, nullptr, a.kq, a.act_lo,
-                                             a.act_hi, M, N, K, 0, 0, 0, 0, 1, nullptr, PF_ACT_NONE, st, 0, rgeom);
-    return (r >= 0) ? r : (int)hipErrorInvalidValue;
-  }
-  {
-    const int r = pf_conv_stream_launch(a, pro, bx != nullptr, st);      // HBM-bound shapes: kernel resident in LDS
-    if (r >= 0) return r;
-  }
-  if (!ymap && conv_use_igemm(pro, K)) {
-    const int r = pf_igemm_conv1x1(X, W, Y, R, partial, bx, bss, bmi, a.b_lo, a.b_hi, scale_shift, slot, a.kq, a.act_lo,
-                                   a.act_hi, M, N, K, Ho, Wo, H, Wd, stride, oss, oact, st);
-    if (r >= 0) return r;
-  }
-  // backward-data of a strided projection (dense dY rows, output rows scattered to (ho * stride, wo * stride) of a pre-zeroed dX):
-  // the staged kernel with its row scatter (round 6; the register-staged tiles of this file ran these at 106 us)
-  if (ymap && stride > 1 && !pro && bx == nullptr && R == nullptr && partial == nullptr && oss == nullptr && conv_use_igemm(false, K) &&
-      (N % 64) == 0) {
-    const int r = pf_igemm_conv1x1(X, W, Y, nullptr, nullptr, nullptr, nullptr, nullptr, a.b_lo, a.b_hi, nullptr, nullptr, a.kq, a.act_lo,
-                                   a.act_hi, M, N, K, Ho, Wo, H, Wd, stride, nullptr, PF_ACT_NONE, st, 1);
-    if (r >= 0) return r;
-  }
-  if (oss != nullptr) {
-    // no kernel with the folded pass took the shape: the plain launch, then the stand-alone pass IN PLACE (same result, one more
-    // read + write of Y)
-    const int r = conv_fwd_launch(X, W, Y, R, scale_shift, act, slot, bits, partial, M, N, K, Ho, Wo, H, Wd, stride, ymap, bx, bss,
-                                  bmi, bact, stream);
-    if (r != 0) return r;
-    return pf_bn_act_quant_apply(Y, Y, PF_BF16, M, N, oss, oact, nullptr, 8, 0, stream);
-  }
-  const bool map = stride != 1;
+  const float* oss = a.oss;
+  if (p.affine_after) a.oss = nullptr;
+  int r = 0;
+  switch (p.kernel) {
+    case CONV_STREAM: r = pf_conv_stream_launch(a, p, st); break;
+    case CONV_IGEMM: r = pf_igemm_conv1x1(a, p, st); break;
+    default: {
+      a.tiles_m = (a.M + CV_BM - 1) / CV_BM;
+      a.tiles_n = (a.N + p.bn - 1) / p.bn;
+      a.G = p.G;
+      const int grid = p.grid;
+      const bool map = a.stride != 1;
 #define PF_CV(BNV)                                                                             \
   do {                                                                                         \
     if (pro) { if (map) k_conv1x1_fwd<BNV, true, false, true><<<grid, PF_THREADS, 0, st>>>(a);  \
                else k_conv1x1_fwd<BNV, true, false, false><<<grid, PF_THREADS, 0, st>>>(a); }   \
-    else if (bx != nullptr) k_conv1x1_fwd<BNV, false, true, false><<<grid, PF_THREADS, 0, st>>>(a); \
+    else if (bwd) k_conv1x1_fwd<BNV, false, true, false><<<grid, PF_THREADS, 0, st>>>(a);       \
     else { if (map) k_conv1x1_fwd<BNV, false, false, true><<<grid, PF_THREADS, 0, st>>>(a);     \
            else k_conv1x1_fwd<BNV, false, false, false><<<grid, PF_THREADS, 0, st>>>(a); }      \
   } while (0)
-  if (bn == 128) PF_CV(128); else PF_CV(64);
+      if (p.bn == 128) PF_CV(128); else PF_CV(64);
 #undef PF_CV
-  PF_LAUNCH_CHECK();
-  return 0;
+      PF_LAUNCH_CHECK();
+    }
+  }
+  if (r != 0 || !p.affine_after) return r;
+  return pf_bn_act_quant_apply(a.Y, a.Y, PF_BF16, a.M, a.N, oss, a.oact, nullptr, 8, 0, stream);
 }
 
 extern "C" int pf_conv1x1_fwd(const void* X, const void* W, void* Y, const void* R, const float* scale_shift,
                               int act, const uint32_t* slot, int bits, float* partial, int M, int N, int K,
                               int Ho, int Wo, int H, int Wd, int stride, int ymap, void* stream) {
-  return conv_fwd_launch(X, W, Y, R, scale_shift, act, slot, bits, partial, M, N, K, Ho, Wo, H, Wd, stride, ymap,
-                         nullptr, nullptr, nullptr, PF_ACT_NONE, stream);
+  if (slot != nullptr && (bits < 1 || bits > 32 || scale_shift == nullptr)) return (int)hipErrorInvalidValue;
+  ConvArgs a = conv_args(X, W, Y, M, N, K);
+  a.R = (const bf16_t*)R; a.partial = partial;
+  conv_args_prologue(a, scale_shift, act, slot, bits);
+  conv_args_rowmap(a, Ho, Wo, H, Wd, stride, ymap);
+  return conv_fwd_launch(a, false, stream);
 }
 
 // pf_conv1x1_fwd with the CONSUMER's inference-mode BN + activation folded into the row pass of the epilogue (round 6):
@@ -482,18 +479,22 @@ extern "C" int pf_conv1x1_fwd_affine(const void* X, const void* W, void* Y, cons
                                      const float* out_scale_shift, int out_act, int M, int N, int K, int Ho, int Wo, int H,
                                      int Wd, int stride, void* stream) {
   if (out_scale_shift == nullptr) return (int)hipErrorInvalidValue;
-  return conv_fwd_launch(X, W, Y, nullptr, scale_shift, act, nullptr, 8, nullptr, M, N, K, Ho, Wo, H, Wd, stride, 0,
-                         nullptr, nullptr, nullptr, PF_ACT_NONE, stream, out_scale_shift, out_act);
+  ConvArgs a = conv_args(X, W, Y, M, N, K);
+  conv_args_prologue(a, scale_shift, act, nullptr, 8);
+  conv_args_rowmap(a, Ho, Wo, H, Wd, stride, 0);
+  a.oss = out_scale_shift; a.oact = out_act;
+  return conv_fwd_launch(a, false, stream);
 }
 
 // backward-data of a stride-1 1x1 convolution, dQ[M][K] = dY[M][N] * W[N][K] (Wt = the transposed kernel
 // [K][N]), with the BN-backward statistics of the layer that produced Q in the epilogue:
-// partial[G][2][K] = {sum dy, sum dy*xhat} over the rows of each workgroup, G = pf_conv1x1_stats_groups(M, K).
+// partial[G][2][K] = {sum dy, sum dy*xhat} over the rows of each workgroup, G = pf_conv1x1_stats_groups_k(M, K, N, 0).
 extern "C" int pf_conv1x1_bwd_data_bnstats(const void* dY, const void* Wt, void* dQ, const void* bn_x,
                                            const float* bn_scale_shift, const float* bn_mean_invstd, int bn_act,
                                            float* partial, int M, int N, int K, void* stream) {
-  return conv_fwd_launch(dY, Wt, dQ, nullptr, nullptr, PF_ACT_NONE, nullptr, 8, partial, M, K, N, 0, 0, 0, 0, 1, 0,
-                         bn_x, bn_scale_shift, bn_mean_invstd, bn_act, stream);
+  ConvArgs a = conv_args(dY, Wt, dQ, M, K, N);
+  conv_args_bnstats(a, bn_x, bn_scale_shift, bn_mean_invstd, bn_act, partial);
+  return conv_fwd_launch(a, false, stream);
 }
 
 // backward-data of a stride-1 1x1 convolution joined with the gradient R of a second consumer of Q (include/pocketflow_hip.h):
@@ -507,10 +508,11 @@ extern "C" int pf_conv1x1_bwd_data_join(const void* dY, const void* Wt, void* dQ
     if (r_H <= 0 || r_W <= 0 || (M % (r_H * r_W)) || r_Ho != (r_H + r_stride - 1) / r_stride || r_Wo != (r_W + r_stride - 1) / r_stride)
       return (int)hipErrorInvalidValue;
   }
-  if (conv_join_kernel(M, N, K, bn_x != nullptr) == 0) return (int)hipErrorInvalidValue;
-  const int rgeom[5] = {r_Ho, r_Wo, r_H, r_W, r_stride};
-  return conv_fwd_launch(dY, Wt, dQ, R, nullptr, PF_ACT_NONE, nullptr, 8, (bn_x != nullptr) ? partial : nullptr, M, K, N, 0, 0, 0, 0, 1,
-                         0, bn_x, bn_scale_shift, bn_mean_invstd, bn_act, stream, nullptr, PF_ACT_NONE, rgeom);
+  ConvArgs a = conv_args(dY, Wt, dQ, M, K, N);
+  a.R = (const bf16_t*)R;
+  a.rHo = r_Ho; a.rWo = r_Wo; a.rH = r_H; a.rW = r_W; a.rstride = r_stride;
+  if (bn_x != nullptr) conv_args_bnstats(a, bn_x, bn_scale_shift, bn_mean_invstd, bn_act, partial);
+  return conv_fwd_launch(a, true, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -673,9 +675,9 @@ __global__ __launch_bounds__(PF_THREADS) void k_wrw_reduce(const float* __restri
   if (sg == 0 && e < n) store_one<TO>(out + (int64_t)blockIdx.y * out_stride + e, (l[0][e_l] + l[1][e_l]) + (l[2][e_l] + l[3][e_l]));
 }
 
-// pf_wrw.hip: backward-filter on transposed LDS reads (ds_read_b64_tr_b16), barrier-free main loop
-int pf_wrw_tr_splits_1x1(int M, int N, int C);
-int pf_wrw2_splits(int M, int N, int C, int taps);
+// pf_wrw.hip: the one decision of the backward-filter entries (pf_conv_common.h: WrwPlan), and the kernels on transposed LDS reads
+// (ds_read_b64_tr_b16) it may name
+WrwPlan pf_wrw_plan(int M, int N, int C, int taps, bool entry_1x1, int64_t x_rows, int window_imgs);
 int pf_wrw2_launch(const void* dY, const void* X, float* slabs, const float* scale_shift, int act, const uint32_t* slot,
                    int bits, int M, int N, int C, int th, int tw, int H, int Wd, int Ho, int Wo, int stride, int pad_h,
                    int pad_w, int S, int64_t x_rows, hipStream_t st);
@@ -703,12 +705,8 @@ int pf_wrw_reduce(float* workspace, int S, int64_t n, void* dW, int dw_dtype, hi
   return 0;
 }
 
-// number of pixel splits; the workspace must hold (splits + 32) * N * K floats
-extern "C" int pf_conv1x1_wrw_splits(int M, int N, int K) {
-  {
-    const int s2 = pf_wrw_tr_splits_1x1(M, N, K);
-    if (s2 > 0) return s2;
-  }
+// pixel splits of k_conv1x1_wrw (this kernel's part of pf_wrw_plan): it takes every shape the entry accepts
+int pf_wrw_scatter_splits(int M, int N, int K) {
   const int tiles = ((N + WR_TN - 1) / WR_TN) * ((K + WR_TK - 1) / WR_TK);
   int S = (768 + tiles - 1) / tiles;
   const int maxS = (M + 4 * WR_BM - 1) / (4 * WR_BM);       // at least 4 pixel steps per workgroup
@@ -719,6 +717,9 @@ extern "C" int pf_conv1x1_wrw_splits(int M, int N, int K) {
   return (M + rows - 1) / rows;
 }
 
+// number of pixel splits; the workspace must hold (splits + 32) * N * K floats
+extern "C" int pf_conv1x1_wrw_splits(int M, int N, int K) { return pf_wrw_plan(M, N, K, 1, true, 0, 0).S; }
+
 extern "C" int pf_conv1x1_wrw(const void* dY, const void* X, void* dW, int dw_dtype, float* workspace,
                               const float* scale_shift, int act, const uint32_t* slot, int bits, int M, int N,
                               int K, int Ho, int Wo, int H, int Wd, int stride, void* stream) {
@@ -726,41 +727,31 @@ extern "C" int pf_conv1x1_wrw(const void* dY, const void* X, void* dW, int dw_dt
   if (!pf_aligned16(dY) || !pf_aligned16(X) || !pf_aligned16(workspace) || !pf_aligned16(dW))
     return (int)hipErrorInvalidValue;
   if (slot != nullptr && (bits < 1 || bits > 32 || scale_shift == nullptr)) return (int)hipErrorInvalidValue;
-  ConvArgs a;
-  a.X = (const bf16_t*)X; a.W = (const bf16_t*)dY; a.Y = nullptr; a.R = nullptr;
-  a.ss = scale_shift; a.slot = slot; a.partial = workspace;
-  a.kq = uq_k_of_bits(slot ? bits : 8);
-  a.act_lo = (act == PF_ACT_NONE) ? -INFINITY : 0.0f;
-  a.act_hi = (act == PF_ACT_RELU6) ? 6.0f : INFINITY;
-  a.M = M; a.N = N; a.K = K;
-  a.Ho = Ho; a.Wo = Wo; a.H = H; a.Wd = Wd; a.stride = stride < 1 ? 1 : stride; a.ymap = 0;
-  a.bx = nullptr; a.bss = nullptr; a.bmi = nullptr; a.b_lo = 0.f; a.b_hi = INFINITY;
-  a.tiles_m = 0; a.G = 0;
-  a.tiles_n = (N + WR_TN - 1) / WR_TN;
-  const int tiles_k = (K + WR_TK - 1) / WR_TK;
-  const int S = pf_conv1x1_wrw_splits(M, N, K);
+  if (stride < 1) stride = 1;
   hipStream_t st = (hipStream_t)stream;
-  const int s_tr = pf_wrw_tr_splits_1x1(M, N, K);
-  int done = -1;
-  if (s_tr > 0) {
-    if (pf_wrw2_splits(M, N, K, 1) > 0) {
-      const int64_t x_rows = (a.stride > 1) ? (int64_t)(M / (Ho * Wo)) * H * Wd : (int64_t)M;
-      done = pf_wrw2_launch(dY, X, workspace, scale_shift, act, slot, bits, M, N, K, 1, 1, H, Wd, Ho, Wo, a.stride, 0, 0,
-                            s_tr, x_rows, st);
-    }
-    if (done < 0)
-      done = pf_wrw_tr_launch(dY, X, workspace, scale_shift, act, slot, bits, M, N, K, 1, 1, H, Wd, Ho, Wo, a.stride, 0, 0,
-                              s_tr, st);
-  }
-  if (done > 0) return done;
-  if (done < 0) {
-    int rows = (M + S - 1) / S;
+  if (stride > 1 && (Ho <= 0 || Wo <= 0 || H <= 0 || Wd <= 0)) return (int)hipErrorInvalidValue;
+  const int64_t x_rows = (stride > 1) ? (int64_t)(M / (Ho * Wo)) * H * Wd : (int64_t)M;
+  const WrwPlan p = pf_wrw_plan(M, N, K, 1, true, x_rows, 0);
+  int r = 0;
+  if (p.kernel == WRW_SHARED) {
+    r = pf_wrw2_launch(dY, X, workspace, scale_shift, act, slot, bits, M, N, K, 1, 1, H, Wd, Ho, Wo, stride, 0, 0, p.S, x_rows, st);
+  } else if (p.kernel == WRW_WAVE) {
+    r = pf_wrw_tr_launch(dY, X, workspace, scale_shift, act, slot, bits, M, N, K, 1, 1, H, Wd, Ho, Wo, stride, 0, 0, p.S, st);
+  } else {
+    ConvArgs a = conv_args(X, dY, nullptr, M, N, K);      // (W: dY)
+    conv_args_prologue(a, scale_shift, act, slot, bits);
+    conv_args_rowmap(a, Ho, Wo, H, Wd, stride, 0);
+    a.partial = workspace;
+    a.tiles_n = (N + WR_TN - 1) / WR_TN;
+    const int tiles_k = (K + WR_TK - 1) / WR_TK;
+    int rows = (M + p.S - 1) / p.S;
     rows = ((rows + WR_BM - 1) / WR_BM) * WR_BM;
     a.rows_per_split = rows;
-    dim3 grid(a.tiles_n * tiles_k, S);
+    dim3 grid(a.tiles_n * tiles_k, p.S);
     if (scale_shift != nullptr) k_conv1x1_wrw<true><<<grid, PF_THREADS, 0, st>>>(a);
     else k_conv1x1_wrw<false><<<grid, PF_THREADS, 0, st>>>(a);
     PF_LAUNCH_CHECK();
   }
-  return pf_wrw_reduce(workspace, (done == 0) ? s_tr : S, (int64_t)N * K, dW, dw_dtype, st);
+  if (r != 0) return r;
+  return pf_wrw_reduce(workspace, p.S, (int64_t)N * K, dW, dw_dtype, st);
 }

@@ -61,6 +61,57 @@ struct ConvArgs {
   int rHo, rWo, rH, rW, rstride;
 };
 
+// workgroups of a persistent tiled launch and (G) the row-tile groups they form: about `slots` resident workgroups (512: 2 per CU),
+// G a multiple of 8 so that the column tiles of one row panel share an XCD
+static inline int pf_conv_grid(int slots, int tiles_m, int tiles_n, int* G_out) {
+  int G = slots / tiles_n;
+  G = (G / 8) * 8;
+  if (G < 8) G = 8;
+  const int need = ((tiles_m + 7) / 8) * 8;
+  if (G > need) G = need;
+  *G_out = G;
+  return G * tiles_n;
+}
+
+// activation code -> the open window lo < u < hi its clamp leaves alone (none: everything; ReLU: 0, +inf; ReLU6: 0, 6)
+static inline void pf_act_window(int act, float* lo, float* hi) {
+  *lo = (act == PF_ACT_NONE) ? -INFINITY : 0.0f;
+  *hi = (act == PF_ACT_RELU6) ? 6.0f : INFINITY;
+}
+
+// ---- the plan of one launch of the 1x1 forward / backward-data family (host only) --------------------------------
+// conv1x1_plan (pf_conv.hip) is the ONE decision: the launch switches on it, and the queries that size the caller's
+// arrays (pf_conv1x1_stats_groups_k, pf_conv1x1_join_plan) read the same answer.  Each kernel file contributes the part
+// that is about its kernel (pf_conv_stream_plan, pf_igemm_conv1x1_plan) and may say "not mine".
+enum { CONV_NONE = 0, CONV_STREAM, CONV_IGEMM, CONV_TILES };
+struct IgCfg { int bm, bn, slots; bool pro3; };    // slots: resident workgroups on the chip (256 CUs x workgroups per CU)
+struct Conv1x1Req {
+  int M, N, K;           // the launch's GEMM [M][K] x [N][K]
+  int64_t rows_in;       // rows of X: M, or stride^2 * M behind the input row map
+  int64_t rows_out;      // rows of Y: M, or stride^2 * M behind the output row map
+  bool pro, bwd, stats;  // producer's BN / act / fake-quant prologue; BN-backward sums; partial != null
+  bool res, join;        // a residual; it is the second consumer's gradient of pf_conv1x1_bwd_data_join (dense or compact)
+  bool map, ymap;        // stride > 1: a row map, on the input rows or (ymap) on the output rows
+  bool aff;              // folded output affine
+};
+struct Conv1x1Plan {
+  int kernel;            // CONV_*
+  int nsplit, nw;        // CONV_STREAM: column slices of a row panel and their width
+  IgCfg ig;              // CONV_IGEMM: tile configuration, and the rows of X behind its buffer descriptor
+  int64_t rows_in;
+  int bn;                // CONV_TILES: column tile
+  int grid, G;           // workgroups, and rows of the [G][.][N] statistics array they write.  The tiles launch with both; the
+                         // resident kernel derives them from nsplit (fixed grid); the staged GEMM's launcher derives them from
+                         // `ig` again and refuses to launch on another G than this one
+  bool affine_after;     // the kernel does not carry the output affine: pf_bn_act_quant_apply in place behind a launch without it
+};
+
+// ---- the plan of one backward-filter launch (pf_wrw_plan, pf_wrw.hip): the kernel that writes the S split slabs pf_wrw_reduce folds.
+// WINDOW: the window-staged 3x3 kernel (pf_wrw3x3_c64.hip); SHARED / WAVE: the shared-tile and the wave-private kernel on transposed
+// LDS reads (pf_wrw.hip); SCATTER: the register-staged kernel of pf_conv.hip (1x1 entry only).
+enum { WRW_NONE = 0, WRW_WINDOW, WRW_SHARED, WRW_WAVE, WRW_SCATTER };
+struct WrwPlan { int kernel, S; };
+
 // Inverse row map of a compact residual: output row m = (img, h, w) of a dense [H x W] grid -> row (img, h / stride, w / stride) of
 // the [Ho x Wo] tensor, or -1 when the pixel has no partner (its residual is +0.0f: what the zero-filled full-size tensor of the
 // backward-data of a strided convolution held there).

@@ -391,36 +391,32 @@ __global__ __launch_bounds__(ST_THREADS) void k_conv1x1_stream(const ConvArgs a,
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
-static int stream_enabled() {
-  return pf_tuning().conv_stream;                         // PF_CONV_STREAM=0: tuning / A-B override
-}
-
-static int stream_max_split() {
-  return pf_tuning().conv_stream_maxsplit;                // PF_CONV_STREAM_MAXSPLIT: column slices a row panel may be cut into
-}
-
-// column slices (0: the stream kernel does not apply) and the slice width
-int pf_conv_stream_plan(int M, int N, int K, int* nw_out) {
-  if (!stream_enabled()) return 0;
-  if ((K % 64) || K > 512 || (N % 64) || N > 2048) return 0;
-  if (M < 4096) return 0;                                 // too few strips for 2048 persistent wavefronts
+// The resident kernel's part of conv1x1_plan (pf_conv.hip).  false: not this kernel's launch.  A joined backward-data whose SHAPE is
+// this kernel's but whose variant is not compiled is answered here with CONV_NONE: the join runs on the kernel the shape names or not
+// at all.
+bool pf_conv_stream_plan(const Conv1x1Req& q, Conv1x1Plan* p) {
+  const int M = q.M, N = q.N, K = q.K;
+  if (!pf_tuning().conv_stream) return false;             // PF_CONV_STREAM=0: tuning / A-B override
+  if ((K % 64) || K > 512 || (N % 64) || N > 2048) return false;
+  if (M < 4096) return false;                             // too few strips for 2048 persistent wavefronts
   int nsplit = 1;
   while ((int64_t)(N / nsplit) * K > 32768 || N / nsplit > 256) nsplit *= 2;
   const int nw = N / nsplit;
-  if (nsplit > stream_max_split() || (ST_GRID % (8 * nsplit)) || (nw != 64 && nw != 128 && nw != 256)) return 0;
+  // PF_CONV_STREAM_MAXSPLIT: column slices a row panel may be cut into
+  if (nsplit > pf_tuning().conv_stream_maxsplit || (ST_GRID % (8 * nsplit)) || (nw != 64 && nw != 128 && nw != 256)) return false;
   // column slices re-read the input panel (from L2) and repeat its prologue: only worth it when the input is the
   // small operand (128 -> 512, 256 -> 1024); 512 -> 128 stays on the tiled kernel (measured: 109 vs 83 us at 28x28,
   // batch 256)
-  if (nsplit >= 2 && N < 4 * K) return 0;
-  *nw_out = nw;
-  return nsplit;
+  if (nsplit >= 2 && N < 4 * K) return false;
+  if (q.aff && (q.map || q.bwd)) return false;            // output affine: stride-1 forward launches only
+  p->kernel = CONV_STREAM;
+  p->nsplit = nsplit; p->nw = nw;
+  p->grid = ST_GRID; p->G = ST_GRID / nsplit;
+  // the joined backward-data variants (RMAP / BR): every slice width carries the compact residual; the sums with a residual are
+  // compiled for 64 and 256 only (the 128-wide kernel is at its register limit without them)
+  if (q.join && ((q.bwd && nw == 128) || q.pro || q.map || q.aff || !q.res)) p->kernel = CONV_NONE;
+  return true;
 }
-
-int pf_conv_stream_groups(int nsplit) { return ST_GRID / nsplit; }
-
-// the joined backward-data variants (RMAP / BR): every slice width carries the compact residual; the sums with a residual are
-// compiled for 64 and 256 only (the 128-wide kernel is at its register limit without them)
-bool pf_conv_stream_join_ok(int nw, bool with_stats) { return !with_stats || nw == 64 || nw == 256; }
 
 template <int NW, bool PRO, bool BWD, bool MAP, bool AFF = false, bool RMAP = false, bool BR = false>
 static int stream_launch_t(const ConvArgs& a, int nsplit, hipStream_t st) {
@@ -433,14 +429,11 @@ static int stream_launch_t(const ConvArgs& a, int nsplit, hipStream_t st) {
   return 0;
 }
 
-// a: filled by conv_fwd_launch (pf_conv.hip); returns -1 when the stream kernel does not apply
-int pf_conv_stream_launch(const ConvArgs& a, bool pro, bool bwd, hipStream_t st) {
-  int nw = 0;
-  const int nsplit = pf_conv_stream_plan(a.M, a.N, a.K, &nw);
-  if (nsplit == 0) return -1;
-  const bool map = a.stride != 1;
+// a: filled by conv_fwd_launch (pf_conv.hip), p: its plan (kernel == CONV_STREAM)
+int pf_conv_stream_launch(const ConvArgs& a, const Conv1x1Plan& p, hipStream_t st) {
+  const int nw = p.nw, nsplit = p.nsplit;
+  const bool pro = a.ss != nullptr, bwd = a.bx != nullptr, map = a.stride != 1;
   if (a.rstride > 1 || (bwd && a.R != nullptr)) {          // the joined backward-data of a projection block (pf_conv1x1_bwd_data_join)
-    if (!pf_conv_stream_join_ok(nw, bwd) || pro || map || a.oss != nullptr || a.R == nullptr) return -1;
     const bool rmap = a.rstride > 1;
 #define PF_STJ(NWV) do { if (!bwd) return stream_launch_t<NWV, false, false, false, false, true, false>(a, nsplit, st);         \
                          return rmap ? stream_launch_t<NWV, false, true, false, false, true, true>(a, nsplit, st)              \
@@ -450,8 +443,7 @@ int pf_conv_stream_launch(const ConvArgs& a, bool pro, bool bwd, hipStream_t st)
 #undef PF_STJ
     return stream_launch_t<128, false, false, false, false, true, false>(a, nsplit, st);
   }
-  if (a.oss != nullptr) {                                  // output affine: stride-1 forward launches (the caller falls back otherwise)
-    if (map || bwd) return -1;
+  if (a.oss != nullptr) {                                  // output affine
 #define PF_STA(NWV) do { return pro ? stream_launch_t<NWV, true, false, false, true>(a, nsplit, st)     \
                                     : stream_launch_t<NWV, false, false, false, true>(a, nsplit, st); } while (0)
     if (nw == 64) PF_STA(64);

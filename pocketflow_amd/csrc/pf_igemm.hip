@@ -662,18 +662,13 @@ __global__ __launch_bounds__(64 * WM * WN) void k_igemm(const IgArgs a) {
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
-struct IgCfg { int bm, bn, slots; bool pro3; };    // slots: resident workgroups on the chip (256 CUs x workgroups per CU)
-
-static bool ig_pro3_enabled() {
-  return pf_tuning().igemm_pro3 != 0;                      // PF_IGEMM_PRO3=0: round 2's two-stage prologue kernel (A/B runs)
-}
-
+// (IgCfg: pf_conv_common.h -- the plan of a 1x1 launch carries one)
 // ONE decision for the launcher and for the statistics-group query (the [G][.][N] partial array is sized from it)
 static IgCfg ig_pick(int M, int N, bool pro) {
   if (pro) {
     // prologue variant.  Three stages, 8 wavefronts, one workgroup per CU: 128 x 256 tiles where N allows (the in-LDS
     // prologue pass over the input tile is amortised over 256 output channels), 256 x 128 otherwise.
-    if (ig_pro3_enabled()) {
+    if (pf_tuning().igemm_pro3 != 0) {                     // PF_IGEMM_PRO3=0: round 2's two-stage prologue kernel (A/B runs)
       if (N % 256 == 0) return IgCfg{128, 256, 256, true};
       if (N % 128 == 0) return IgCfg{256, 128, 256, true};
     }
@@ -694,30 +689,22 @@ static IgCfg ig_pick(int M, int N, bool pro) {
   return IgCfg{128, bn, 512, false};
 }
 
-static int ig_grid(int slots, int tiles_m, int tiles_n, int* G_out) {
-  int G = slots / tiles_n;
-  G = (G / 8) * 8;
-  if (G < 8) G = 8;
-  const int need = ((tiles_m + 7) / 8) * 8;
-  if (G > need) G = need;
-  *G_out = G;
-  return G * tiles_n;
+// An IgArgs with nothing attached: a plain th x tw convolution that walks its own kernel -- no residual, statistics, prologue, output
+// scatter or output affine.  The fill sites set the operands and the geometry, and the fields in which they differ from this.
+static IgArgs ig_args_plain(int th, int tw) {
+  IgArgs a;
+  a.X = nullptr; a.W = nullptr; a.Y = nullptr; a.zero = nullptr; a.x_bytes = 0; a.w_bytes = 0;
+  a.R = nullptr; a.partial = nullptr; a.bx = nullptr; a.bss = nullptr; a.bmi = nullptr; a.b_lo = -INFINITY; a.b_hi = INFINITY;
+  a.ss = nullptr; a.slot = nullptr; a.kq = 255.f; a.act_lo = -INFINITY; a.act_hi = INFINITY;
+  a.M = 0; a.N = 0; a.C = 0; a.th = th; a.tw = tw;
+  a.H = 1; a.Wd = 1; a.Ho = 1; a.Wo = 1; a.stride = 1; a.pad_h = 0; a.pad_w = 0;
+  a.tiles_m = 0; a.tiles_n = 0; a.G = 0;
+  a.w_r0 = 0; a.w_rs = 1; a.w_s0 = 0; a.w_ss = 1; a.w_S = tw; a.w_taps_full = th * tw;
+  a.o_sub = 0; a.o_y = 0; a.o_x = 0; a.o_H = 0; a.o_W = 0;
+  a.oss = nullptr; a.oact = PF_ACT_NONE;
+  a.rHo = 0; a.rWo = 0; a.rH = 0; a.rW = 0; a.rstride = 1;
+  return a;
 }
-
-// taps, C: the window and the input channels of the launch (1, K for the 1x1 products)
-int pf_igemm_stats_groups_geom(int M, int N, int pro, int taps, int C) {
-  (void)taps; (void)C;
-  const IgCfg c = ig_pick(M, N, pro != 0);
-  int G;
-  ig_grid(c.slots, (M + c.bm - 1) / c.bm, (N + c.bn - 1) / c.bn, &G);
-  return G;
-}
-
-// (M, N) alone: the 1x1 reading -- what pf_conv1x1_stats_groups_k answers for the products it routes here
-int pf_igemm_stats_groups(int M, int N, int pro) { return pf_igemm_stats_groups_geom(M, N, pro, 1, 64); }
-
-/* deprecated for RxS convolutions: use pf_conv2d_stats_groups_geom (the kernel, and with it the row count, depends on the window) */
-extern "C" int pf_conv2d_stats_groups(int M, int N) { return pf_igemm_stats_groups(M, N, 0); }
 
 template <int BM, int BN, int WM, int WN, int NS, int MODE, bool SUB = false, bool AFF = false, bool RMAP = false, bool BR = false>
 static int ig_launch_t(IgArgs& a, int slots, hipStream_t st) {
@@ -725,7 +712,9 @@ static int ig_launch_t(IgArgs& a, int slots, hipStream_t st) {
   constexpr int THREADS = 64 * WM * WN;
   a.tiles_m = (a.M + BM - 1) / BM;
   a.tiles_n = (a.N + BN - 1) / BN;
-  const int grid = ig_grid(slots, a.tiles_m, a.tiles_n, &a.G);
+  const int planned_G = a.G;                              // a 1x1 launch arrives with its plan's G (pf_igemm_conv1x1); 0: none
+  const int grid = pf_conv_grid(slots, a.tiles_m, a.tiles_n, &a.G);
+  if (planned_G > 0 && a.G != planned_G) return (int)hipErrorInvalidValue;   // never write rows the plan did not name
   // stage ring and (aliased on it) the C tile; the BWD vectors / the folded prologue constants sit behind whichever is larger
   constexpr size_t ring = NS * (size_t)(BM + BN) * 128, ctile = (size_t)BM * (BN + 8) * 2;
   constexpr size_t base = (ring > ctile ? ring : ctile);
@@ -744,24 +733,27 @@ bool pf_conv3x3_c64_takes(const IgArgs& a);
 int pf_conv3x3_c64_stats_groups(int M);
 int pf_conv3x3_c64_launch(const IgArgs& a, hipStream_t st);
 
-static int ig_launch(IgArgs& a, hipStream_t st) {
+// which selections carry the output affine (the AFF instantiations of ig_launch below): the dispatcher's default tiles; any other
+// (tile override, two-stage prologue kernel, a prologue beside a window) runs the plain launch and the stand-alone pass in place
+static bool ig_carries_affine(const IgCfg& c, bool pro, int taps) { return pro ? (c.pro3 && taps == 1) : c.bm == 128; }
+
+// c: ig_pick's answer for the launch (a 1x1 launch brings it in its plan)
+static int ig_launch(IgArgs& a, const IgCfg& c, hipStream_t st) {
   const bool bwd = a.bx != nullptr, pro = a.ss != nullptr;
   if (pf_conv3x3_c64_takes(a)) return pf_conv3x3_c64_launch(a, st);
-  const IgCfg c = ig_pick(a.M, a.N, pro);
   if (a.oss != nullptr) {
-    // output affine: the dispatcher's default tiles carry it; any other selection (tile override, two-stage prologue kernel) runs
-    // the plain launch and the stand-alone pass in place
     if (bwd) return (int)hipErrorInvalidValue;
-    if (pro && c.pro3 && a.th * a.tw == 1)
-      return (c.bn == 256) ? ig_launch_t<128, 256, 2, 4, 3, IG_PRO, false, true>(a, c.slots, st)
-                           : ig_launch_t<256, 128, 4, 2, 3, IG_PRO, false, true>(a, c.slots, st);
-    if (!pro && c.bm == 128 && c.bn == 128) return ig_launch_t<128, 128, 2, 2, 2, IG_PLAIN, false, true>(a, c.slots, st);
-    if (!pro && c.bm == 128 && c.bn == 64) return ig_launch_t<128, 64, 2, 2, 2, IG_PLAIN, false, true>(a, c.slots, st);
-    const float* oss = a.oss;
-    a.oss = nullptr;
-    const int r = ig_launch(a, st);
-    if (r != 0) return r;
-    return pf_bn_act_quant_apply(a.Y, a.Y, PF_BF16, a.M, a.N, oss, a.oact, nullptr, 8, 0, st);
+    if (!ig_carries_affine(c, pro, a.th * a.tw)) {
+      const float* oss = a.oss;
+      a.oss = nullptr;
+      const int r = ig_launch(a, c, st);
+      if (r != 0) return r;
+      return pf_bn_act_quant_apply(a.Y, a.Y, PF_BF16, a.M, a.N, oss, a.oact, nullptr, 8, 0, st);
+    }
+    if (pro) return (c.bn == 256) ? ig_launch_t<128, 256, 2, 4, 3, IG_PRO, false, true>(a, c.slots, st)
+                                  : ig_launch_t<256, 128, 4, 2, 3, IG_PRO, false, true>(a, c.slots, st);
+    return (c.bn == 128) ? ig_launch_t<128, 128, 2, 2, 2, IG_PLAIN, false, true>(a, c.slots, st)
+                         : ig_launch_t<128, 64, 2, 2, 2, IG_PLAIN, false, true>(a, c.slots, st);
   }
   if (pro) {
     if (a.th * a.tw != 1 || bwd) return (int)hipErrorInvalidValue;
@@ -782,12 +774,16 @@ extern "C" int pf_conv2d_stats_groups_geom(int imgs, int H, int Wd, int C, int N
                                            int pad_w, int Ho, int Wo) {
   if (pf_conv3x3_c64_geom(H, Wd, C, N, th, tw, stride, pad_h, pad_w, Ho, Wo) && (imgs * Ho * Wo) % (Ho * Wo) == 0)
     return pf_conv3x3_c64_stats_groups(imgs * Ho * Wo);
-  return pf_igemm_stats_groups_geom(imgs * Ho * Wo, N, 0, th * tw, C);
+  const int M = imgs * Ho * Wo;
+  const IgCfg c = ig_pick(M, N, false);
+  int G;
+  pf_conv_grid(c.slots, (M + c.bm - 1) / c.bm, (N + c.bn - 1) / c.bn, &G);
+  return G;
 }
 
 // forward convolution (or any implicit GEMM of that form).  X [img][H][Wd][C], W [N][th][tw][C], Y [img][Ho][Wo][N].
 // zero: >= 128 zero bytes in device memory.  R / partial / bn_*: epilogue options as for pf_conv1x1_fwd /
-// pf_conv1x1_bwd_data_bnstats (partial: [G][4][N] or, with bn_x, [G][2][N]; G = pf_conv2d_stats_groups(M, N)).
+// pf_conv1x1_bwd_data_bnstats (partial: [G][4][N] or, with bn_x, [G][2][N]; G = pf_conv2d_stats_groups_geom(<this geometry>)).
 static int conv2d_fwd_launch(const void* X, const void* W, void* Y, const void* zero, const void* R, float* partial,
                              const void* bn_x, const float* bn_scale_shift, const float* bn_mean_invstd, int bn_act,
                              int imgs, int H, int Wd, int C, int N, int th, int tw, int stride, int pad_h, int pad_w,
@@ -803,21 +799,16 @@ static int conv2d_fwd_launch(const void* X, const void* W, void* Y, const void* 
     return (int)hipErrorInvalidValue;
   if ((int64_t)imgs * H * Wd * C >= ((int64_t)1 << 30) || (int64_t)N * th * tw * C >= ((int64_t)1 << 30) || th * tw > 32)
     return (int)hipErrorInvalidValue;                     // 31-bit byte offsets and a 32-bit tap mask inside the kernel
-  IgArgs a;
+  IgArgs a = ig_args_plain(th, tw);
   a.X = (const bf16_t*)X; a.W = (const bf16_t*)W; a.Y = (bf16_t*)Y; a.zero = (const bf16_t*)zero;
   a.R = (const bf16_t*)R; a.partial = partial; a.bx = (const bf16_t*)bn_x; a.bss = bn_scale_shift; a.bmi = bn_mean_invstd;
-  a.b_lo = (bn_act == PF_ACT_NONE) ? -INFINITY : 0.0f;
-  a.b_hi = (bn_act == PF_ACT_RELU6) ? 6.0f : INFINITY;
-  a.ss = nullptr; a.slot = nullptr; a.kq = 255.f; a.act_lo = -INFINITY; a.act_hi = INFINITY;
-  a.M = imgs * Ho * Wo; a.N = N; a.C = C; a.th = th; a.tw = tw;
+  pf_act_window(bn_act, &a.b_lo, &a.b_hi);
+  a.M = imgs * Ho * Wo; a.N = N; a.C = C;
   a.H = H; a.Wd = Wd; a.Ho = Ho; a.Wo = Wo; a.stride = stride; a.pad_h = pad_h; a.pad_w = pad_w;
   a.x_bytes = (uint32_t)((int64_t)imgs * H * Wd * C * 2);
   a.w_bytes = (uint32_t)((int64_t)N * th * tw * C * 2);
-  a.w_r0 = 0; a.w_rs = 1; a.w_s0 = 0; a.w_ss = 1; a.w_S = tw; a.w_taps_full = th * tw;
-  a.o_sub = 0; a.o_y = 0; a.o_x = 0; a.o_H = 0; a.o_W = 0;
   a.oss = out_scale_shift; a.oact = out_act;
-  a.rHo = 0; a.rWo = 0; a.rH = 0; a.rW = 0; a.rstride = 1;
-  return ig_launch(a, (hipStream_t)stream);
+  return ig_launch(a, ig_pick(a.M, N, false), (hipStream_t)stream);
 }
 
 extern "C" int pf_conv2d_fwd(const void* X, const void* W, void* Y, const void* zero, const void* R, float* partial,
@@ -834,18 +825,13 @@ extern "C" int pf_probe_conv2d_fwd_codes(const void* Xc, float alpha, const void
                                          int Wd, int C, int N, int th, int tw, int stride, int pad_h, int pad_w, int Ho, int Wo,
                                          void* stream) {
   if ((C % 64) || (N % 64) || !pf_aligned16(Xc) || !pf_aligned16(W) || !pf_aligned16(Y)) return (int)hipErrorInvalidValue;
-  IgArgs a;
+  IgArgs a = ig_args_plain(th, tw);
   a.X = (const bf16_t*)Xc; a.W = (const bf16_t*)W; a.Y = (bf16_t*)Y; a.zero = (const bf16_t*)zero;
-  a.R = nullptr; a.partial = nullptr; a.bx = nullptr; a.bss = nullptr; a.bmi = nullptr;
-  a.b_lo = -INFINITY; a.b_hi = INFINITY;
-  a.ss = nullptr; a.slot = nullptr; a.kq = alpha; a.act_lo = -INFINITY; a.act_hi = INFINITY;
-  a.M = imgs * Ho * Wo; a.N = N; a.C = C; a.th = th; a.tw = tw;
+  a.kq = alpha;                                              // the grid step rides where the quantiser's k would
+  a.M = imgs * Ho * Wo; a.N = N; a.C = C;
   a.H = H; a.Wd = Wd; a.Ho = Ho; a.Wo = Wo; a.stride = stride; a.pad_h = pad_h; a.pad_w = pad_w;
-  a.x_bytes = (uint32_t)((int64_t)imgs * H * Wd * C);
+  a.x_bytes = (uint32_t)((int64_t)imgs * H * Wd * C);        // one byte per element
   a.w_bytes = (uint32_t)((int64_t)N * th * tw * C * 2);
-  a.w_r0 = 0; a.w_rs = 1; a.w_s0 = 0; a.w_ss = 1; a.w_S = tw; a.w_taps_full = th * tw;
-  a.o_sub = 0; a.o_y = 0; a.o_x = 0; a.o_H = 0; a.o_W = 0;
-  a.oss = nullptr; a.oact = PF_ACT_NONE;
   const IgCfg c = ig_pick(a.M, a.N, false);
   if (c.bm == 256 && c.bn == 128) return ig_launch_t<256, 128, 4, 2, 3, IG_PLAIN>(a, c.slots, (hipStream_t)stream);
   if (c.bm == 128 && c.bn == 128) return ig_launch_t<128, 128, 2, 2, 2, IG_PLAIN>(a, c.slots, (hipStream_t)stream);
@@ -874,7 +860,7 @@ extern "C" int pf_conv2d_fwd_affine(const void* X, const void* W, void* Y, const
 static int strided_class_groups(int imgs, int H, int Wd, int C, int stride) {
   const int bn = (C % 128 == 0) ? 128 : 64;
   int G;
-  ig_grid(512, (imgs * (H / stride) * (Wd / stride) + 127) / 128, (C + bn - 1) / bn, &G);
+  pf_conv_grid(512, (imgs * (H / stride) * (Wd / stride) + 127) / 128, (C + bn - 1) / bn, &G);
   return G;
 }
 
@@ -899,17 +885,14 @@ static int strided_launch(const void* dY, const void* Wt, void* dX, const void* 
       const int r1 = (ay + pad_h) % stride, s1 = (ax + pad_w) % stride;
       const int th = (R - r1 + stride - 1) / stride, tw = (S - s1 + stride - 1) / stride;
       const int dmin_h = (ay + pad_h - r1) / stride - (th - 1), dmin_w = (ax + pad_w - s1) / stride - (tw - 1);
-      IgArgs a;
+      IgArgs a = ig_args_plain(th, tw);
       a.X = (const bf16_t*)dY; a.W = (const bf16_t*)Wt; a.Y = (bf16_t*)dX; a.zero = (const bf16_t*)zero;
-      a.R = nullptr; a.partial = nullptr; a.bx = nullptr; a.bss = nullptr; a.bmi = nullptr; a.b_lo = -INFINITY; a.b_hi = INFINITY;
       if (bn_x != nullptr) {                                     // the BN-backward sums of the BN whose input has dX's shape: one
         a.partial = partial + (int64_t)(ay * stride + ax) * strided_class_groups(imgs, H, Wd, C, stride) * 2 * C;   // slice per class
         a.bx = (const bf16_t*)bn_x; a.bss = bss; a.bmi = bmi;
-        a.b_lo = (bn_act == PF_ACT_NONE) ? -INFINITY : 0.0f;
-        a.b_hi = (bn_act == PF_ACT_RELU6) ? 6.0f : INFINITY;
+        pf_act_window(bn_act, &a.b_lo, &a.b_hi);
       }
-      a.ss = nullptr; a.slot = nullptr; a.kq = 255.f; a.act_lo = -INFINITY; a.act_hi = INFINITY;
-      a.M = imgs * Hc * Wc; a.N = C; a.C = N; a.th = th; a.tw = tw;
+      a.M = imgs * Hc * Wc; a.N = C; a.C = N;
       // the launch's "input image" is dY, its "output grid" the class's pixels; tap u reads dY row i + dmin + u = i*1 + u - pad'
       a.H = Ho; a.Wd = Wo; a.Ho = Hc; a.Wo = Wc; a.stride = 1; a.pad_h = -dmin_h; a.pad_w = -dmin_w;
       a.x_bytes = (uint32_t)((int64_t)imgs * Ho * Wo * N * 2);
@@ -918,8 +901,7 @@ static int strided_launch(const void* dY, const void* Wt, void* dX, const void* 
       a.w_r0 = (R - 1 - r1) - (th - 1) * stride; a.w_rs = stride;
       a.w_s0 = (S - 1 - s1) - (tw - 1) * stride; a.w_ss = stride;
       a.w_S = S; a.w_taps_full = R * S;
-      a.o_sub = stride; a.o_y = ay; a.o_x = ax; a.o_H = H; a.o_W = Wd; a.oss = nullptr; a.oact = PF_ACT_NONE;
-      a.rHo = 0; a.rWo = 0; a.rH = 0; a.rW = 0; a.rstride = 1;
+      a.o_sub = stride; a.o_y = ay; a.o_x = ax; a.o_H = H; a.o_W = Wd;
       // (the two plain tile configurations the dispatcher picks for these shapes, with the sub-grid walk compiled in)
       int rc;
       if (bn_x != nullptr)
@@ -953,63 +935,64 @@ extern "C" int pf_conv2d_bwd_data_strided_bnstats(const void* dY, const void* Wt
                         bn_scale_shift, bn_mean_invstd, bn_act);
 }
 
-// the shapes whose joined backward-data (a residual through the inverse row map, the BN-backward sums beside a residual) this file
-// carries: those the dispatcher gives its default 128-row tiles (a PF_IGEMM_TILE override selects kernels without the variants)
-bool pf_igemm_join_ok(int M, int N, int K) {
-  if ((K % 64) || (N % 64) || (int64_t)M * K >= ((int64_t)1 << 30) || (int64_t)N * K >= ((int64_t)1 << 30)) return false;
-  const IgCfg c = ig_pick(M, N, false);
-  return c.bm == 128 && c.slots == 512 && c.bn == ((N % 128 == 0) ? 128 : 64);
+// ---- 1x1 convolutions through the same kernel (the shapes conv1x1_plan of pf_conv.hip routes here) ------------------------------
+// This kernel's part of conv1x1_plan; false: not this kernel's launch.  Plain, backward-data with BN-backward sums, or with the
+// producer's BN/act/fake-quant prologue; an input row map (stride > 1 reads input pixel (ho*stride, wo*stride)); the joined
+// backward-data of a projection block; or (ymap, nothing else attached) the row scatter of a strided backward-data.
+bool pf_igemm_conv1x1_plan(const Conv1x1Req& q, Conv1x1Plan* p) {
+  const int64_t lim = (int64_t)1 << 30;                    // 31-bit byte offsets inside the kernel
+  if ((q.K % 64) || q.rows_in * q.K >= lim || (int64_t)q.N * q.K >= lim) return false;
+  IgCfg c = ig_pick(q.M, q.N, q.pro);
+  if (q.join) {
+    // the residual through the inverse row map, the BN-backward sums beside a residual: carried by the dispatcher's default 128-row
+    // tiles (a PF_IGEMM_TILE override selects kernels without the variants)
+    if ((q.N % 64) || c.bm != 128 || c.slots != 512 || c.bn != ((q.N % 128 == 0) ? 128 : 64)) return false;
+    if (q.ymap || q.map || !q.res || q.pro || q.aff) return false;
+  } else if (q.ymap) {
+    // row (img, i, j) of the dense [Ho x Wo] grid goes to pixel (i * stride, j * stride) of the [H x Wd] image: the scatter of the
+    // parity-class launches with class (0, 0), compiled for their two tile configurations
+    if ((q.N % 64) || q.rows_out * q.N >= lim) return false;
+    c = IgCfg{128, (q.N % 128 == 0) ? 128 : 64, 512, false};
+  }
+  p->kernel = CONV_IGEMM;
+  p->ig = c;
+  p->grid = pf_conv_grid(c.slots, (q.M + c.bm - 1) / c.bm, (q.N + c.bn - 1) / c.bn, &p->G);
+  p->rows_in = q.rows_in;
+  p->affine_after = q.aff && !ig_carries_affine(c, q.pro, 1);
+  return true;
 }
 
-// 1x1 convolutions through the same kernel (called by pf_conv.hip for the shapes it routes here): plain, backward-data with
-// BN-backward sums, or with the producer's BN/act/fake-quant prologue; stride > 1 reads input pixel (ho*stride, wo*stride).
-// No tap ever leaves the image, `zero` is unused.
-int pf_igemm_conv1x1(const void* X, const void* W, void* Y, const void* R, float* partial, const void* bn_x,
-                     const float* bss, const float* bmi, float b_lo, float b_hi, const float* scale_shift,
-                     const uint32_t* slot, float kq, float act_lo, float act_hi, int M, int N, int K, int Ho, int Wo,
-                     int H, int Wd, int stride, const float* oss, int oact, hipStream_t st, int ymap, const int* rgeom) {
-  int64_t rows_in = M;
-  if (stride > 1 && !ymap) rows_in = (int64_t)(M / (Ho * Wo)) * H * Wd;
-  if ((K % 64) || rows_in * K >= ((int64_t)1 << 30) || (int64_t)N * K >= ((int64_t)1 << 30)) return -1;
-  IgArgs a;
-  a.X = (const bf16_t*)X; a.W = (const bf16_t*)W; a.Y = (bf16_t*)Y; a.zero = (const bf16_t*)X;
+// a: filled by conv_fwd_launch (pf_conv.hip), p: its plan (kernel == CONV_IGEMM).  No tap ever leaves the image, `zero` is unused.
+int pf_igemm_conv1x1(const ConvArgs& c, const Conv1x1Plan& p, hipStream_t st) {
+  const bool rowmap = c.stride > 1 && !c.ymap;
+  IgArgs a = ig_args_plain(1, 1);
+  a.X = c.X; a.W = c.W; a.Y = c.Y; a.zero = c.X;
 #ifdef PF_IG_TIMING
   a.zero = (const bf16_t*)(uintptr_t)strtoull(getenv("PF_IG_TIMING_PTR"), nullptr, 0);
 #endif
-  a.R = (const bf16_t*)R; a.partial = partial; a.bx = (const bf16_t*)bn_x; a.bss = bss; a.bmi = bmi;
-  a.b_lo = b_lo; a.b_hi = b_hi;
-  a.ss = scale_shift; a.slot = slot; a.kq = kq; a.act_lo = act_lo; a.act_hi = act_hi;
-  a.M = M; a.N = N; a.C = K; a.th = 1; a.tw = 1;
-  if (ymap) { a.H = Ho; a.Wd = Wo; a.Ho = Ho; a.Wo = Wo; a.stride = 1; }       // dense input rows; the OUTPUT rows are scattered (below)
-  else if (stride > 1) { a.H = H; a.Wd = Wd; a.Ho = Ho; a.Wo = Wo; a.stride = stride; }
-  else { a.H = 1; a.Wd = 1; a.Ho = 1; a.Wo = 1; a.stride = 1; }
-  a.pad_h = 0; a.pad_w = 0;
-  a.x_bytes = (uint32_t)(rows_in * K * 2);
-  a.w_bytes = (uint32_t)((int64_t)N * K * 2);
-  a.w_r0 = 0; a.w_rs = 1; a.w_s0 = 0; a.w_ss = 1; a.w_S = 1; a.w_taps_full = 1;
-  a.o_sub = 0; a.o_y = 0; a.o_x = 0; a.o_H = 0; a.o_W = 0;
-  a.oss = oss; a.oact = oact;
-  a.rHo = 0; a.rWo = 0; a.rH = 0; a.rW = 0; a.rstride = 1;
-  if (rgeom != nullptr) {
-    // the joined backward-data of a projection block (pf_conv1x1_bwd_data_join): rgeom = {Ho, Wo, H, W, stride} of the residual
-    // (stride 1: dense), with the BN-backward sums when bn_x is given.  The dispatcher's default 128-row tiles carry the variants.
-    if (!pf_igemm_join_ok(M, N, K) || ymap || stride != 1 || R == nullptr || scale_shift != nullptr || oss != nullptr) return -1;
-    a.rHo = rgeom[0]; a.rWo = rgeom[1]; a.rH = rgeom[2]; a.rW = rgeom[3]; a.rstride = rgeom[4];
-    const bool rmap = a.rstride > 1, bwd = bn_x != nullptr, wide = (N % 128 == 0);
-    if (!rmap && !bwd) return ig_launch(a, st);                          // dense residual, no sums: the plain launch has it
-    if (!bwd) return wide ? ig_launch_t<128, 128, 2, 2, 2, IG_PLAIN, false, false, true, false>(a, 512, st)
-                          : ig_launch_t<128, 64, 2, 2, 2, IG_PLAIN, false, false, true, false>(a, 512, st);
+  a.R = c.R; a.partial = c.partial; a.bx = c.bx; a.bss = c.bss; a.bmi = c.bmi; a.b_lo = c.b_lo; a.b_hi = c.b_hi;
+  a.ss = c.ss; a.slot = c.slot; a.kq = c.kq; a.act_lo = c.act_lo; a.act_hi = c.act_hi;
+  a.M = c.M; a.N = c.N; a.C = c.K; a.G = p.G;             // (ig_launch_t refuses to write another G than the plan's)
+  if (c.ymap) { a.H = c.Ho; a.Wd = c.Wo; a.Ho = c.Ho; a.Wo = c.Wo; }         // dense input rows; the OUTPUT rows are scattered (below)
+  else if (rowmap) { a.H = c.H; a.Wd = c.Wd; a.Ho = c.Ho; a.Wo = c.Wo; a.stride = c.stride; }
+  a.x_bytes = (uint32_t)(p.rows_in * c.K * 2);
+  a.w_bytes = (uint32_t)((int64_t)c.N * c.K * 2);
+  a.oss = c.oss; a.oact = c.oact;
+  a.rHo = c.rHo; a.rWo = c.rWo; a.rH = c.rH; a.rW = c.rW; a.rstride = c.rstride;
+  const bool rmap = a.rstride > 1, br = a.bx != nullptr && a.R != nullptr, wide = (p.ig.bn == 128);
+  if (rmap || br) {
+    // the joined backward-data of a projection block (pf_conv1x1_bwd_data_join) on the default 128-row tiles; a dense residual
+    // without sums is the plain launch below
+    if (!br) return wide ? ig_launch_t<128, 128, 2, 2, 2, IG_PLAIN, false, false, true, false>(a, 512, st)
+                         : ig_launch_t<128, 64, 2, 2, 2, IG_PLAIN, false, false, true, false>(a, 512, st);
     if (rmap) return wide ? ig_launch_t<128, 128, 2, 2, 2, IG_BWD, false, false, true, true>(a, 512, st)
                           : ig_launch_t<128, 64, 2, 2, 2, IG_BWD, false, false, true, true>(a, 512, st);
     return wide ? ig_launch_t<128, 128, 2, 2, 2, IG_BWD, false, false, false, true>(a, 512, st)
                 : ig_launch_t<128, 64, 2, 2, 2, IG_BWD, false, false, false, true>(a, 512, st);
   }
-  if (ymap) {
-    // row (img, i, j) of the dense [Ho x Wo] grid goes to pixel (i * stride, j * stride) of the [H x Wd] image: the scatter of the
-    // parity-class launches with class (0, 0); the other pixels keep the zeros the caller wrote
-    if ((int64_t)(M / (Ho * Wo)) * H * Wd * N >= ((int64_t)1 << 30)) return -1;
-    a.o_sub = stride; a.o_y = 0; a.o_x = 0; a.o_H = H; a.o_W = Wd;
-    return (N % 128 == 0) ? ig_launch_t<128, 128, 2, 2, 2, IG_PLAIN, true>(a, 512, st) : ig_launch_t<128, 64, 2, 2, 2, IG_PLAIN, true>(a, 512, st);
+  if (c.ymap) {                                            // the other pixels keep the zeros the caller wrote
+    a.o_sub = c.stride; a.o_y = 0; a.o_x = 0; a.o_H = c.H; a.o_W = c.Wd;
+    return wide ? ig_launch_t<128, 128, 2, 2, 2, IG_PLAIN, true>(a, 512, st) : ig_launch_t<128, 64, 2, 2, 2, IG_PLAIN, true>(a, 512, st);
   }
-  return ig_launch(a, st);
+  return ig_launch(a, p.ig, st);
 }

@@ -223,23 +223,10 @@ __global__ __launch_bounds__(256) void k_wrw_tr(const WrwArgs a) {
 // per 32 MFMAs (43 flop / byte) through one workgroup of 4 wavefronts per CU -- load-bandwidth bound per CU.  The 1x1
 // dispatcher therefore uses it only on request (PF_WRW_TR=1); pf_conv2d_wrw (the RxS entry point, which has no
 // other implementation here) always runs it.  The fix is a shared 256 x 256 output tile.
-static bool wrw_tr_1x1_enabled() {
-  return pf_tuning().wrw_tr != 0;                          // PF_WRW_TR
-}
-
-int pf_wrw_tr_splits(int M, int N, int C, int taps);
-// the 1x1 dispatcher's gate (pf_conv.hip): > 0 -> this many pixel splits on a kernel of this file
-int pf_wrw2_splits(int M, int N, int C, int taps);
-int pf_wrw_tr_splits_1x1(int M, int N, int C) {
-  const int s2 = pf_wrw2_splits(M, N, C, 1);
-  if (s2 > 0) return s2;
-  return wrw_tr_1x1_enabled() ? pf_wrw_tr_splits(M, N, C, 1) : 0;
-}
-
 static int wrw_tr_bn(int N) { return (N % 128 == 0) ? 128 : 64; }
 
 // pixel splits of the transposed-read kernel (0: the kernel does not apply)
-int pf_wrw_tr_splits(int M, int N, int C, int taps) {
+static int wrw_tr_splits(int M, int N, int C, int taps) {
   if ((C % 64) || (N % 64) || M < 2048) return 0;
   const int bn = wrw_tr_bn(N);
   const int tiles = (N / bn) * (taps * C / 64);
@@ -264,17 +251,16 @@ static int wrw_tr_launch_t(const WrwArgs& a, int grid, hipStream_t st) {
   return 0;
 }
 
-// slabs: [S][N][taps*C] floats; returns -1 when the kernel does not apply, else a hipError_t
+// slabs: [S][N][taps*C] floats, S from pf_wrw_plan
 int pf_wrw_tr_launch(const void* dY, const void* X, float* slabs, const float* scale_shift, int act,
                      const uint32_t* slot, int bits, int M, int N, int C, int th, int tw, int H, int Wd, int Ho, int Wo,
                      int stride, int pad_h, int pad_w, int S, hipStream_t st) {
-  if (S <= 0) return -1;
+  if (S <= 0) return (int)hipErrorInvalidValue;
   WrwArgs a;
   a.dY = (const bf16_t*)dY; a.X = (const bf16_t*)X; a.slabs = slabs;
   a.ss = scale_shift; a.slot = slot;
   a.kq = uq_k_of_bits(slot ? bits : 8);
-  a.act_lo = (act == PF_ACT_NONE) ? -INFINITY : 0.0f;
-  a.act_hi = (act == PF_ACT_RELU6) ? 6.0f : INFINITY;
+  pf_act_window(act, &a.act_lo, &a.act_hi);
   a.M = M; a.N = N; a.C = C; a.th = th; a.tw = tw; a.H = H; a.Wd = Wd; a.Ho = Ho; a.Wo = Wo;
   a.stride = stride; a.pad_h = pad_h; a.pad_w = pad_w;
   const int bn = wrw_tr_bn(N);
@@ -286,7 +272,7 @@ int pf_wrw_tr_launch(const void* dY, const void* X, float* slabs, const float* s
   const int grid = a.tiles * S;
   const bool pro = scale_shift != nullptr;
   const bool map = stride != 1 || th * tw > 1;
-  if (pro && th * tw > 1) return -1;                      // padding taps need Q = 0, not Q(0): materialised inputs only
+  if (pro && th * tw > 1) return (int)hipErrorInvalidValue;   // padding taps need Q = 0, not Q(0): materialised inputs only
 #define PF_WT(BNV)                                                                            \
   do {                                                                                        \
     if (pro) return map ? wrw_tr_launch_t<BNV, true, true>(a, grid, st) : wrw_tr_launch_t<BNV, true, false>(a, grid, st);   \
@@ -655,14 +641,15 @@ static Wrw2Cfg wrw2_pick(int N, int C) {
   return Wrw2Cfg{tn, tk};
 }
 
-static bool wrw2_enabled() {
-  return pf_tuning().wrw2 != 0;                            // PF_WRW2=0: tuning / A-B override
+// 31-bit byte offsets inside the kernel: dY and (x_rows rows of) X stay below 2 GiB
+static bool wrw2_fits(int M, int N, int C, int64_t x_rows) {
+  return (int64_t)M * N < ((int64_t)1 << 30) && x_rows * C < ((int64_t)1 << 30);
 }
 
 // pixel splits of the shared-tile kernel (0: does not apply)
 int pf_wrw2_splits(int M, int N, int C, int taps) {
-  if (!wrw2_enabled() || (C % 64) || (N % 64) || M < 2048) return 0;
-  if ((int64_t)M * N >= ((int64_t)1 << 30)) return 0;
+  if (pf_tuning().wrw2 == 0) return 0;                     // PF_WRW2=0: tuning / A-B override
+  if ((C % 64) || (N % 64) || M < 2048 || !wrw2_fits(M, N, C, 0)) return 0;
   const Wrw2Cfg c = wrw2_pick(N, C);
   const int tiles = (N / c.tn) * (taps * C / c.tk);
   // workgroups a launch aims at: every pixel split writes (and the reduction reads) one fp32 slab of the whole dW tile, so
@@ -691,13 +678,11 @@ static int wrw2_launch_t(const Wrw2Args& a, int grid, hipStream_t st) {
 int pf_wrw2_launch(const void* dY, const void* X, float* slabs, const float* scale_shift, int act, const uint32_t* slot,
                    int bits, int M, int N, int C, int th, int tw, int H, int Wd, int Ho, int Wo, int stride, int pad_h,
                    int pad_w, int S, int64_t x_rows, hipStream_t st) {
-  if (S <= 0) return -1;
-  if (x_rows * C >= ((int64_t)1 << 30) || (int64_t)M * N >= ((int64_t)1 << 30)) return -1;   // 31-bit byte offsets inside the kernel
+  if (S <= 0 || !wrw2_fits(M, N, C, x_rows)) return (int)hipErrorInvalidValue;
   Wrw2Args a;
   a.dY = (const bf16_t*)dY; a.X = (const bf16_t*)X; a.slabs = slabs; a.ss = scale_shift; a.slot = slot;
   a.kq = uq_k_of_bits(slot ? bits : 8);
-  a.act_lo = (act == PF_ACT_NONE) ? -INFINITY : 0.0f;
-  a.act_hi = (act == PF_ACT_RELU6) ? 6.0f : INFINITY;
+  pf_act_window(act, &a.act_lo, &a.act_hi);
   a.dy_bytes = (uint32_t)((int64_t)M * N * 2);
   a.x_bytes = (uint32_t)(x_rows * C * 2);
   a.M = M; a.N = N; a.C = C; a.th = th; a.tw = tw; a.H = H; a.Wd = Wd; a.Ho = Ho; a.Wo = Wo;
@@ -714,7 +699,7 @@ int pf_wrw2_launch(const void* dY, const void* X, float* slabs, const float* sca
   // enough: 32 / Wo + 1 <= Ho); 2: general
   int mapm = 0;
   if (stride != 1 || th * tw > 1) mapm = (stride == 1 && Ho == H && Wo == Wd && 32 / Wo + 1 <= Ho) ? 1 : 2;
-  if (pro && th * tw > 1) return -1;
+  if (pro && th * tw > 1) return (int)hipErrorInvalidValue;
   if (pro && mapm == 1) mapm = 2;                       // (prologue variants: identity and general only)
 #define PF_W2(TNV, TKV, WTNV, WTKV)                                                                           \
   do {                                                                                                        \
@@ -737,20 +722,37 @@ int pf_wrw2_launch(const void* dY, const void* X, float* slabs, const float* sca
 // ---- RxS backward-filter behind the C ABI ------------------------------------------------------------------------
 int pf_wrw_reduce(float* workspace, int S, int64_t n, void* dW, int dw_dtype, hipStream_t st);   // pf_conv.hip
 
-// pixel splits of pf_conv2d_wrw (0: shape not supported); the workspace must hold (splits + 32) * N * th*tw*C floats
 // pf_wrw3x3_c64.hip: the window-staged kernel for 3x3 / stride 1, 64 -> 64 channels on 56 x 56 maps
 bool pf_wrw3x3_c64_geom(int H, int Wd, int C, int N, int th, int tw, int stride, int pad_h, int pad_w, int Ho, int Wo);
+bool pf_wrw3x3_c64_fits(int imgs);
 int pf_wrw3x3_c64_splits(int imgs);
 int pf_wrw3x3_c64_launch(const void* dY, const void* X, float* slabs, int imgs, hipStream_t st);
+int pf_wrw_scatter_splits(int M, int N, int K);           // pf_conv.hip: the register-staged kernel behind the 1x1 entry
 
-extern "C" int pf_conv2d_wrw_splits(int M, int N, int C, int taps) {
+// THE decision of the backward-filter entries: which kernel writes the slabs, and how many (S).  The window-staged kernel where the
+// launch's geometry is its own (window_imgs > 0: its images; only pf_conv2d_wrw sees the image and can say so), else shared-tile, else
+// wave-private, else (1x1 entry) the register-staged scatter.
+// x_rows: the rows of X, known to a launch only (queries pass 0).  The caller sized the workspace by the query, so S never depends on
+// it: an X beyond the shared-tile kernel's addressing moves the launch to the wave-private kernel and keeps the count.
+WrwPlan pf_wrw_plan(int M, int N, int C, int taps, bool entry_1x1, int64_t x_rows, int window_imgs) {
+  if (window_imgs > 0 && pf_wrw3x3_c64_fits(window_imgs)) return WrwPlan{WRW_WINDOW, pf_wrw3x3_c64_splits(window_imgs)};
   const int s2 = pf_wrw2_splits(M, N, C, taps);
-  int s = s2 > 0 ? s2 : pf_wrw_tr_splits(M, N, C, taps);
+  if (s2 > 0) return WrwPlan{wrw2_fits(M, N, C, x_rows) ? WRW_SHARED : WRW_WAVE, s2};
+  // the 1x1 entry uses the wave-private kernel on request only (see above); the RxS entry has nothing else
+  const int s1 = (!entry_1x1 || pf_tuning().wrw_tr != 0) ? wrw_tr_splits(M, N, C, taps) : 0;      // PF_WRW_TR
+  if (s1 > 0) return WrwPlan{WRW_WAVE, s1};
+  if (entry_1x1) return WrwPlan{WRW_SCATTER, pf_wrw_scatter_splits(M, N, C)};
+  return WrwPlan{WRW_NONE, 0};
+}
+
+// pixel splits of pf_conv2d_wrw (0: shape not supported); the workspace must hold (splits + 32) * N * th*tw*C floats
+extern "C" int pf_conv2d_wrw_splits(int M, int N, int C, int taps) {
+  const int s = pf_wrw_plan(M, N, C, taps, false, 0, 0).S;
   // this query does not see the image size: where the window-staged kernel COULD take the launch (its geometry is 56 x 56 images),
-  // the answer covers its slab count too -- an upper bound for sizing the workspace; pf_conv2d_wrw folds what it actually wrote
+  // the answer is the larger of the two plans' counts -- an upper bound for sizing the workspace; pf_conv2d_wrw folds what it wrote
   if (pf_tuning().conv3x3_c64 != 0 && taps == 9 && N == 64 && C == 64 && M % (56 * 56) == 0) {
-    const int s3 = pf_wrw3x3_c64_splits(M / (56 * 56));
-    if (s3 > s) s = s3;
+    const int s3 = pf_wrw_plan(M, N, C, taps, false, 0, M / (56 * 56)).S;
+    return s3 > s ? s3 : s;
   }
   return s;
 }
@@ -763,21 +765,15 @@ extern "C" int pf_conv2d_wrw(const void* dY, const void* X, void* dW, int dw_dty
   if (!pf_aligned16(dY) || !pf_aligned16(X) || !pf_aligned16(dW) || !pf_aligned16(workspace)) return (int)hipErrorInvalidValue;
   const int M = imgs * Ho * Wo;
   hipStream_t st = (hipStream_t)stream;
-  if (pf_wrw3x3_c64_geom(H, Wd, C, N, th, tw, stride, pad_h, pad_w, Ho, Wo)) {
-    const int r3 = pf_wrw3x3_c64_launch(dY, X, workspace, imgs, st);
-    if (r3 == 0) return pf_wrw_reduce(workspace, pf_wrw3x3_c64_splits(imgs), (int64_t)N * th * tw * C, dW, dw_dtype, st);
-    if (r3 > 0) return r3;
-  }
-  const int s2 = pf_wrw2_splits(M, N, C, th * tw);
-  const int S = s2 > 0 ? s2 : pf_wrw_tr_splits(M, N, C, th * tw);
-  if (S <= 0) return (int)hipErrorInvalidValue;
-  int r = -1;
-  if (s2 > 0)
-    r = pf_wrw2_launch(dY, X, workspace, nullptr, PF_ACT_NONE, nullptr, 8, M, N, C, th, tw, H, Wd, Ho, Wo, stride, pad_h,
-                       pad_w, S, (int64_t)imgs * H * Wd, st);
-  if (r < 0)
-    r = pf_wrw_tr_launch(dY, X, workspace, nullptr, PF_ACT_NONE, nullptr, 8, M, N, C, th, tw, H, Wd, Ho, Wo, stride,
-                         pad_h, pad_w, S, st);
-  if (r != 0) return r < 0 ? (int)hipErrorInvalidValue : r;
-  return pf_wrw_reduce(workspace, S, (int64_t)N * th * tw * C, dW, dw_dtype, st);
+  const bool window = pf_wrw3x3_c64_geom(H, Wd, C, N, th, tw, stride, pad_h, pad_w, Ho, Wo);
+  const WrwPlan p = pf_wrw_plan(M, N, C, th * tw, false, (int64_t)imgs * H * Wd, window ? imgs : 0);
+  int r = (int)hipErrorInvalidValue;                      // WRW_NONE: shape not supported
+  if (p.kernel == WRW_WINDOW) r = pf_wrw3x3_c64_launch(dY, X, workspace, imgs, st);
+  if (p.kernel == WRW_SHARED)
+    r = pf_wrw2_launch(dY, X, workspace, nullptr, PF_ACT_NONE, nullptr, 8, M, N, C, th, tw, H, Wd, Ho, Wo, stride, pad_h, pad_w, p.S,
+                       (int64_t)imgs * H * Wd, st);
+  if (p.kernel == WRW_WAVE)
+    r = pf_wrw_tr_launch(dY, X, workspace, nullptr, PF_ACT_NONE, nullptr, 8, M, N, C, th, tw, H, Wd, Ho, Wo, stride, pad_h, pad_w, p.S, st);
+  if (r != 0) return r;
+  return pf_wrw_reduce(workspace, p.S, (int64_t)N * th * tw * C, dW, dw_dtype, st);
 }

@@ -195,8 +195,11 @@ int pf_wrw3x3_c64_splits(int imgs) {
   return n_tiles < 512 ? n_tiles : 512;
 }
 
+// 32-bit byte offsets inside the kernel: beyond them pf_conv2d_wrw keeps the launch on the GEMM kernels
+bool pf_wrw3x3_c64_fits(int imgs) { return (int64_t)imgs * W3_W * W3_W * W3_C * 2 < ((int64_t)1 << 31); }
+
 int pf_wrw3x3_c64_launch(const void* dY, const void* X, float* slabs, int imgs, hipStream_t st) {
-  if ((int64_t)imgs * W3_W * W3_W * W3_C * 2 >= ((int64_t)1 << 31)) return -1;
+  if (!pf_wrw3x3_c64_fits(imgs)) return (int)hipErrorInvalidValue;
   Wrw3Args a;
   a.dY = (const bf16_t*)dY; a.X = (const bf16_t*)X; a.slabs = slabs;
   a.bytes = (uint32_t)((int64_t)imgs * W3_W * W3_W * W3_C * 2);

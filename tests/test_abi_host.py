@@ -62,6 +62,45 @@ def test_host_side_shape_rules_of_the_convolution_entry_points():
   assert hip.conv2d_stats_groups(2 * 56 * 56, 64, geom=(2, 56, 56, 64, 64, 3, 3, 1, 1, 1, 56, 56)) == 56      # window kernel: one row per workgroup = tile
 
 
+def test_statistics_groups_stay_bounded_over_the_shape_grid_under_every_switch():
+  """1 <= G <= 1024 for every GEMM shape of tools/conv_plan_sweep.py's grid (both networks at three batch sizes, the shapes of the
+  GPU tests, the M x N x K grid around the kernels' thresholds) under each tuning switch that moves a shape between kernels:
+  tests/test_conv_plan_gpu.py allocates 1032 rows on the strength of it."""
+  import importlib.util
+  from pocketflow_amd import hip
+  spec = importlib.util.spec_from_file_location('conv_plan_sweep', os.path.join(ROOT, 'tools', 'conv_plan_sweep.py'))
+  sweep = importlib.util.module_from_spec(spec)
+  spec.loader.exec_module(sweep)
+  gemm, geom = sweep.shapes()
+  assert len(gemm) > 500
+  # the tool reads the GPU tests' parametrize lists: one shape of each list it is meant to find, so that a renamed axis there
+  # cannot shrink the grid unnoticed (test_conv_gpu.py: forward, three-stage prologue, bwd-data sums, backward-filter geometry;
+  # test_proj_join_gpu.py: _STRIDED, _DENSE; test_igemm_gpu.py: 3x3 statistics, strided backward-data)
+  for shape in ((70001, 256, 128), (8200, 64, 512), (100003, 256, 192), (4097, 512, 128), (2 * 47 * 49, 64, 64), (3 * 7 * 9, 512, 1024),
+                (2 * 14 * 14, 256, 192), (300 * 7 * 7, 128, 64)):
+    assert shape in gemm, shape
+  for g in ((300, 7, 7, 64, 128, 3, 3, 1, 1, 1, 7, 7), (2, 14, 14, 64, 64, 3, 3, 1, 1, 1, 14, 14)):
+    assert g in geom, g
+  for setting in sweep.SETTINGS:
+    key, val = setting.split('=') if setting else (None, None)
+    old = os.environ.get(key) if key else None
+    try:
+      if key:
+        os.environ[key] = val
+      hip.tuning_reload()
+      for M, N, K in gemm:
+        for pro in (False, True):
+          G = hip.conv1x1_stats_groups(M, N, K, prologue=pro)
+          assert 1 <= G <= 1024, (setting, M, N, K, pro, G)
+    finally:
+      if key:
+        if old is None:
+          del os.environ[key]
+        else:
+          os.environ[key] = old
+      hip.tuning_reload()
+
+
 def test_header_is_plain_c_and_struct_sizes_match(tmp_path):
   from pocketflow_amd import hip
   src = tmp_path / 'sz.c'

@@ -18,5 +18,7 @@ done
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt \
   -Wno-unused-function -DPF_W2_TIMING -shared pf_wrw.hip -o ../../tools/gpu/_build/libwrw_timing.so -L. -l:libpocketflow_hip.so -Wl,-rpath,'$ORIGIN/../../../pocketflow_amd/csrc'
+# (with pf_conv.hip: tools/gpu/igemm_timeline.py enters through THIS library's pf_conv1x1_fwd, whose pf_igemm_conv1x1 is then the
+# instrumented one of this library too -- the product's entry would bind to the product's kernels)
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt \
-  -Wno-unused-function -DPF_IG_TIMING -shared pf_igemm.hip -o ../../tools/gpu/_build/libig_timing.so -L. -l:libpocketflow_hip.so -Wl,-rpath,'$ORIGIN/../../../pocketflow_amd/csrc'
+  -Wno-unused-function -DPF_IG_TIMING -shared pf_igemm.hip pf_conv.hip -o ../../tools/gpu/_build/libig_timing.so -L. -l:libpocketflow_hip.so -Wl,-rpath,'$ORIGIN/../../../pocketflow_amd/csrc'
