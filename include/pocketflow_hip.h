@@ -169,6 +169,20 @@ int pf_ce_distill_fwd_bwd(const void* z_s, int zs_dtype, const float* labels, co
                           int zt_dtype, int B, int C, float tempr, float loss_w, float* losses,
                           void* dz_s, int dz_dtype, float* row_ws, void* stream);
 
+/* The training step's ONE loss launch (the network head): both losses, the top-1 / top-5 accuracy and the two terms of dz_s.
+ *   losses[0] = L_model, losses[1] = L_dst (0 without z_t), losses[2] / losses[3] = the fraction of rows whose label is in the
+ *   top 1 / top 5 (tf.nn.in_top_k: fewer than k logits STRICTLY greater than the logit at the FIRST arg-max of the label row).
+ *   dz_hard = T((softmax(z_s)*sum(labels) - labels)/B), dz_soft = T(loss_w/(B*T) * (softmax(z_s/T) - softmax(z_t/T))), each
+ *   rounded to the dz type: bit for bit the dz_s of one pf_ce_distill_fwd_bwd call without z_t and of one with z_t and all-zero
+ *   labels.  z_t, dz_soft may be NULL (no distillation).  row_ws: B*3 floats of scratch.                                   */
+int pf_ce_distill_head(const void* z_s, int zs_dtype, const float* labels, const void* z_t,
+                       int zt_dtype, int B, int C, float tempr, float loss_w, float* losses /*[4]*/,
+                       void* dz_hard, void* dz_soft, int dz_dtype, float* row_ws, void* stream);
+/* Its backward: dz = T( T(dz_hard * T(g0)) + T(dz_soft * T(g1)) ), g0 / g1 the upstream gradients of L_model / L_dst (float32
+ * DEVICE scalars) -- what autograd makes of the two calls above.  g0 or (dz_soft, g1) may be NULL: that term is dropped.      */
+int pf_ce_combine(const void* dz_hard, const void* dz_soft, const float* g0, const float* g1, void* dz,
+                  int dtype, int64_t n, void* stream);
+
 /* ---- K13 fused with K4: batch-norm (training) + ReLU + activation fake-quant ----------------
  * replaces tf.layers.batch_normalization(fused=True) -> tf.nn.relu -> (min/max, quantise) of
  * utils/external/resnet_model.py:55-62 + uq utils.py:51-79 for the BN->ReLU->conv chains of
@@ -188,6 +202,23 @@ int pf_bn_finalize(const float* partial, int n_blocks, int64_t rows, int C, cons
 int pf_bn_act_quant_apply(const void* x, void* q, int dtype, int64_t rows, int C,
                           const float* scale_shift, int act, const uint32_t* slot, int bits,
                           int quantize, void* stream);
+/* pass 2 of a BN whose output feeds nothing but the spatial mean (the network head; rows = B*HW, image-major):
+ *   pooled[b][c] = T( (sum_p q[b][p][c]) * float32(1/HW) ), q = the value pf_bn_act_quant_apply would have stored (rounded to T),
+ *   summed in float32 in ascending pixel order and scaled as aten's mean scales its sum; q itself is never written.
+ *   pooled: [B][C] of x's type.                                                                                           */
+int pf_bn_act_quant_pool(const void* x, void* pooled, int dtype, int64_t rows, int C,
+                         const float* scale_shift, int act, const uint32_t* slot, int bits,
+                         int quantize, int HW, void* stream);
+/* ... and its backward passes: pf_bn_bwd_stats / pf_bn_bwd_apply with dq[(b,p)][c] = T(float(g[b][c]) * float32(1/HW)) rebuilt
+ * from the [B][C] gradient g of the pooled tensor instead of read (the value autograd's mean / cast chain expands on the device:
+ * aten divides by a host scalar as a product with its rounded reciprocal); same row order, splits and partial layout, so partial,
+ * dgamma, dbeta and dx are bit-identical.  rows < 2^31, rows % HW == 0.                                                      */
+int pf_bn_bwd_stats_pooled(const void* g, const void* x, int dtype, int64_t rows, int C, int HW,
+                           const float* scale_shift, const float* mean_invstd, int act,
+                           float* partial /*[nblk][2][C]*/, int n_blocks, void* stream);
+int pf_bn_bwd_apply_pooled(const void* g, const void* x, void* dx, int dtype, int64_t rows, int C, int HW,
+                           const float* scale_shift, const float* mean_invstd,
+                           const float* dgamma, const float* dbeta, int act, void* stream);
 /* backward: dy = dq * actmask(scale*x+shift) (STE); per-channel sum(dy), sum(dy*xhat) */
 int pf_bn_bwd_stats(const void* dq, const void* x, int dtype, int64_t rows, int C,
                     const float* scale_shift, const float* mean_invstd, int act,

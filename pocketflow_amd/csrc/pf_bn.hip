@@ -353,6 +353,92 @@ extern "C" int pf_bn_act_quant_apply(const void* x, void* q, int dtype, int64_t 
 }
 
 // ---------------------------------------------------------------------------------------------
+// forward pass 2 of the network head:  pooled[b][c] = T( (sum_p q[b][p][c]) / HW ),  q never written
+// ---------------------------------------------------------------------------------------------
+// The last BN's activated map feeds nothing but the spatial mean, so pass 2 reduces it on the fly: q is the value k_bn_apply
+// would have stored (same scale / shift, activation, uq_point, and the rounding to T), summed in float32 in ASCENDING pixel
+// order p = 0 .. HW-1 by ONE thread per (image, channel) -- a fixed order, bit-deterministic -- and scaled by float32(1 / HW), the
+// last step of aten's mean on the device (an accumulated sum times the ROUNDED reciprocal, not a division).
+// FAST: a thread owns 8 consecutive channels of one image (16-byte loads, a wavefront reads 1 KiB contiguous per pixel);
+// a 256-thread workgroup covers 256 / (C/8) images.  Otherwise one thread per (image, channel).
+template <typename T, int ACT, bool FAST>
+__global__ __launch_bounds__(PF_THREADS) void k_bn_apply_pool(const T* __restrict__ x, T* __restrict__ pooled,
+                                                              int B, int HW, int C,
+                                                              const float* __restrict__ scale_shift,
+                                                              const uint32_t* __restrict__ slot, float k,
+                                                              int quantize) {
+  float alpha = 1.f, beta = 0.f;
+  if (quantize) slot_alpha_beta(slot, alpha, beta);
+  const float inv_hw = 1.0f / (float)HW;
+  const int64_t item = (int64_t)blockIdx.x * PF_THREADS + threadIdx.x;
+  if (FAST) {
+    const int G = C >> 3;
+    if (item >= (int64_t)B * G) return;
+    const int b = (int)(item / G), cg = (int)(item % G);
+    float sc[8], sh[8], acc[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { sc[j] = scale_shift[(cg << 3) + j]; sh[j] = scale_shift[C + (cg << 3) + j]; acc[j] = 0.f; }
+    const T* __restrict__ px = x + (int64_t)b * HW * C + (cg << 3);
+#pragma unroll 7
+    for (int p = 0; p < HW; ++p) {
+      float v[8];
+      load8<T>(px + (int64_t)p * C, v);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float y = apply_act<ACT>(fmaf(sc[j], v[j], sh[j]));
+        acc[j] += round_to<T>(quantize ? uq_point(y, alpha, beta, k) : y);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = acc[j] * inv_hw;
+    store8<T>(pooled + (int64_t)b * C + (cg << 3), acc);
+  } else {
+    if (item >= (int64_t)B * C) return;
+    const int b = (int)(item / C), c = (int)(item % C);
+    const float sc = scale_shift[c], sh = scale_shift[C + c];
+    const T* __restrict__ px = x + (int64_t)b * HW * C + c;
+    float acc = 0.f;
+    for (int p = 0; p < HW; ++p) {
+      const float y = apply_act<ACT>(fmaf(sc, load_one<T>(px + (int64_t)p * C), sh));
+      acc += round_to<T>(quantize ? uq_point(y, alpha, beta, k) : y);
+    }
+    store_one<T>(pooled + item, acc * inv_hw);
+  }
+}
+
+template <typename T>
+static int launch_bn_apply_pool(const T* x, T* pooled, int64_t rows, int C, int HW, const float* ss, int act,
+                                const uint32_t* slot, float k, int quantize, hipStream_t st) {
+  const bool fast = bn_fast_ok(C) && pf_aligned16(x) && pf_aligned16(pooled);
+  const int64_t B = rows / HW;
+  const int64_t items = fast ? B * (C / 8) : B * C;
+  const int64_t grid = (items + PF_THREADS - 1) / PF_THREADS;
+  if (grid > 0x7FFFFFFF) return (int)hipErrorInvalidValue;
+#define PF_BP(ACTV)                                                                                                          \
+  do {                                                                                                                       \
+    if (fast) k_bn_apply_pool<T, ACTV, true><<<(int)grid, PF_THREADS, 0, st>>>(x, pooled, (int)B, HW, C, ss, slot, k, quantize);   \
+    else k_bn_apply_pool<T, ACTV, false><<<(int)grid, PF_THREADS, 0, st>>>(x, pooled, (int)B, HW, C, ss, slot, k, quantize);       \
+  } while (0)
+  if (act == PF_ACT_RELU) PF_BP(PF_ACT_RELU);
+  else if (act == PF_ACT_RELU6) PF_BP(PF_ACT_RELU6);
+  else PF_BP(PF_ACT_NONE);
+#undef PF_BP
+  PF_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int pf_bn_act_quant_pool(const void* x, void* pooled, int dtype, int64_t rows, int C,
+                                    const float* scale_shift, int act, const uint32_t* slot, int bits,
+                                    int quantize, int HW, void* stream) {
+  if (rows <= 0 || C <= 0 || HW <= 0 || rows % HW != 0 || rows / HW > 0x7FFFFFFF) return (int)hipErrorInvalidValue;
+  if (quantize && (bits < 1 || bits > 32 || slot == nullptr)) return (int)hipErrorInvalidValue;
+  const float k = uq_k_of_bits(quantize ? bits : 8);
+  if (dtype == PF_F32) return launch_bn_apply_pool<float>((const float*)x, (float*)pooled, rows, C, HW, scale_shift, act, slot, k, quantize, (hipStream_t)stream);
+  if (dtype == PF_BF16) return launch_bn_apply_pool<bf16_t>((const bf16_t*)x, (bf16_t*)pooled, rows, C, HW, scale_shift, act, slot, k, quantize, (hipStream_t)stream);
+  return (int)hipErrorInvalidValue;
+}
+
+// ---------------------------------------------------------------------------------------------
 // backward pass 1: per-channel sum(dy), sum(dy * xhat),  dy = dq * act'(scale*x+shift)
 // ---------------------------------------------------------------------------------------------
 template <typename T, int ACT>
@@ -570,4 +656,192 @@ extern "C" int pf_bn_bwd_apply(const void* dq, const void* x, void* dx, int dtyp
                                const float* scale_shift, const float* mean_invstd, const float* dgamma,
                                const float* dbeta, int act, void* stream) {
   return pf_bn_bwd_apply_add(dq, x, nullptr, dx, dtype, rows, C, scale_shift, mean_invstd, dgamma, dbeta, act, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// backward of the network head: the two passes above with the dq load replaced
+// ---------------------------------------------------------------------------------------------
+// This BN's output feeds nothing but the spatial mean (pf_bn_act_quant_pool), so `g` is the [B][C] gradient of the POOLED tensor
+// and the value of row r = (b, p) is rebuilt on the fly, dq[(b, p)][c] = T(float(g[b][c]) * float32(1 / HW)) -- bit for bit what
+// autograd's cast / mean / cast chain writes into the expanded [B * HW][C] tensor on the device (aten divides a tensor by a host
+// scalar as a product with the rounded reciprocal), which is then never stored or read.  Everything else is
+// a copy of the plain kernel (kept apart so that those compile to the instructions they had): row order, splits and the partial
+// layout are the same, so every sum and dx come out bit-identical.  rows < 2^31: the row -> image division is a 32-bit one.
+template <typename T>
+__device__ __forceinline__ void pooled_dq8(const T* __restrict__ g, int64_t r, int C, int c0, int HW, float (&out)[8]) {
+  const float inv_hw = 1.0f / (float)HW;
+  load8<T>(g + (int64_t)((uint32_t)r / (uint32_t)HW) * C + c0, out);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) out[j] = round_to<T>(out[j] * inv_hw);
+}
+template <typename T>
+__device__ __forceinline__ float pooled_dq1(const T* __restrict__ g, int64_t r, int C, int c, int HW) {
+  return round_to<T>(load_one<T>(g + (int64_t)((uint32_t)r / (uint32_t)HW) * C + c) * (1.0f / (float)HW));
+}
+
+template <typename T, int ACT>
+__global__ __launch_bounds__(BN_BIG) void k_bn_bwd_stats_fast_pooled(const T* __restrict__ g, const T* __restrict__ x,
+                                                                     int64_t rows, int C,
+                                                                     const float* __restrict__ scale_shift,
+                                                                     const float* __restrict__ mean_invstd,
+                                                                     float* __restrict__ partial, int nslab, int nsplit,
+                                                                     int HW) {
+  __shared__ float lds[(BN_BIG / 64) * 2 * 64];
+  const int CG = bn_cg_of(C), slabC = CG * 8, RL = BN_BIG / CG;
+  const int slab = blockIdx.x % nslab, split = blockIdx.x / nslab;
+  const int cg = threadIdx.x % CG, rl = threadIdx.x / CG;
+  const int c0 = slab * slabC + cg * 8;
+  float sc[8], sh[8], mu[8], is[8], s1[8], s2[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int c = c0 + j;
+    sc[j] = scale_shift[c]; sh[j] = scale_shift[C + c];
+    mu[j] = mean_invstd[c]; is[j] = mean_invstd[C + c];
+    s1[j] = 0.f; s2[j] = 0.f;
+  }
+#pragma unroll 2
+  for (int64_t r = (int64_t)split * RL + rl; r < rows; r += (int64_t)nsplit * RL) {
+    float dq[8], v[8];
+    pooled_dq8<T>(g, r, C, c0, HW, dq);
+    load8<T>(x + r * C + c0, v);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float dy = dq[j] * act_mask<ACT>(fmaf(sc[j], v[j], sh[j]));
+      s1[j] += dy;
+      s2[j] = fmaf(dy, (v[j] - mu[j]) * is[j], s2[j]);
+    }
+  }
+  bn_wave_reduce8<0>(s1, CG); bn_wave_reduce8<0>(s2, CG);
+  bn_lds_put<0>(s1, 0, 2, CG, lds); bn_lds_put<0>(s2, 1, 2, CG, lds);
+  __syncthreads();
+  float* out = partial + (int64_t)split * 2 * C + slab * slabC;
+  bn_lds_finish<0>(0, 2, slabC, lds, out);
+  bn_lds_finish<0>(1, 2, slabC, lds, out + C);
+}
+
+template <typename T, int ACT>
+__global__ __launch_bounds__(PF_THREADS) void k_bn_bwd_stats_generic_pooled(const T* __restrict__ g, const T* __restrict__ x,
+                                                                            int64_t rows, int C,
+                                                                            const float* __restrict__ scale_shift,
+                                                                            const float* __restrict__ mean_invstd,
+                                                                            float* __restrict__ partial, int HW) {
+  const int c = blockIdx.x * PF_THREADS + threadIdx.x;
+  if (c >= C) return;
+  const float sc = scale_shift[c], sh = scale_shift[C + c], mu = mean_invstd[c], is = mean_invstd[C + c];
+  float s1 = 0.f, s2 = 0.f;
+  for (int64_t r = blockIdx.y; r < rows; r += gridDim.y) {
+    const float v = load_one<T>(x + r * C + c);
+    const float dy = pooled_dq1<T>(g, r, C, c, HW) * act_mask<ACT>(fmaf(sc, v, sh));
+    s1 += dy;
+    s2 = fmaf(dy, (v - mu) * is, s2);
+  }
+  float* out = partial + (int64_t)blockIdx.y * 2 * C;
+  out[c] = s1; out[C + c] = s2;
+}
+
+static inline bool bn_pooled_ok(int64_t rows, int HW) {
+  return HW > 0 && rows > 0 && rows < ((int64_t)1 << 31) && rows % HW == 0;
+}
+
+template <typename T>
+static int launch_bn_bwd_stats_pooled(const T* g, const T* x, int64_t rows, int C, int HW, const float* ss,
+                                      const float* mi, int act, float* partial, int n_blocks, hipStream_t st) {
+  const bool fast = bn_fast_ok(C) && pf_aligned16(x) && pf_aligned16(g);
+  const int CG = (C / 8) < 8 ? (C / 8) : 8;
+  const int nslab = fast ? C / (CG * 8) : 1;
+  dim3 ggrid((C + PF_THREADS - 1) / PF_THREADS, n_blocks);
+#define PF_BS(ACTV)                                                                                                       \
+  do {                                                                                                                    \
+    if (fast) k_bn_bwd_stats_fast_pooled<T, ACTV><<<nslab * n_blocks, BN_BIG, 0, st>>>(g, x, rows, C, ss, mi, partial, nslab, n_blocks, HW);  \
+    else k_bn_bwd_stats_generic_pooled<T, ACTV><<<ggrid, PF_THREADS, 0, st>>>(g, x, rows, C, ss, mi, partial, HW);        \
+  } while (0)
+  if (act == PF_ACT_RELU) PF_BS(PF_ACT_RELU);
+  else if (act == PF_ACT_RELU6) PF_BS(PF_ACT_RELU6);
+  else PF_BS(PF_ACT_NONE);
+#undef PF_BS
+  PF_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int pf_bn_bwd_stats_pooled(const void* g, const void* x, int dtype, int64_t rows, int C, int HW,
+                                      const float* scale_shift, const float* mean_invstd, int act,
+                                      float* partial, int n_blocks, void* stream) {
+  if (C <= 0 || n_blocks <= 0 || !bn_pooled_ok(rows, HW)) return (int)hipErrorInvalidValue;
+  if (dtype == PF_F32) return launch_bn_bwd_stats_pooled<float>((const float*)g, (const float*)x, rows, C, HW, scale_shift, mean_invstd, act, partial, n_blocks, (hipStream_t)stream);
+  if (dtype == PF_BF16) return launch_bn_bwd_stats_pooled<bf16_t>((const bf16_t*)g, (const bf16_t*)x, rows, C, HW, scale_shift, mean_invstd, act, partial, n_blocks, (hipStream_t)stream);
+  return (int)hipErrorInvalidValue;
+}
+
+template <typename T, int ACT, bool FAST>
+__global__ __launch_bounds__(PF_THREADS) void k_bn_bwd_apply_pooled(const T* __restrict__ g, const T* __restrict__ x,
+                                                                    T* __restrict__ dx, int64_t rows, int C,
+                                                                    const float* __restrict__ scale_shift,
+                                                                    const float* __restrict__ mean_invstd,
+                                                                    const float* __restrict__ dgamma,
+                                                                    const float* __restrict__ dbeta, int HW) {
+  const float inv_n = 1.0f / (float)rows;
+  if (FAST) {
+    const int G = C >> 3, RPS = PF_THREADS / G;
+    const int cg = threadIdx.x % G, rsub = threadIdx.x / G;
+    float sc[8], sh[8], mu[8], is[8], a[8], b[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int c = (cg << 3) + j;
+      sc[j] = scale_shift[c]; sh[j] = scale_shift[C + c];
+      mu[j] = mean_invstd[c]; is[j] = mean_invstd[C + c];
+      a[j] = dbeta[c] * inv_n; b[j] = dgamma[c] * inv_n;
+    }
+#pragma unroll 2
+    for (int64_t r = (int64_t)blockIdx.x * RPS + rsub; r < rows; r += (int64_t)gridDim.x * RPS) {
+      float dq[8], v[8];
+      const int64_t off = r * C + (cg << 3);
+      pooled_dq8<T>(g, r, C, cg << 3, HW, dq);
+      load8<T>(x + off, v);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float dy = dq[j] * act_mask<ACT>(fmaf(sc[j], v[j], sh[j]));
+        const float xh = (v[j] - mu[j]) * is[j];
+        dq[j] = sc[j] * (dy - a[j] - xh * b[j]);
+      }
+      store8<T>(dx + off, dq);
+    }
+  } else {
+    const int64_t n = rows * C;
+    for (int64_t e = (int64_t)blockIdx.x * PF_THREADS + threadIdx.x; e < n;
+         e += (int64_t)gridDim.x * PF_THREADS) {
+      const int c = (int)(e % C);
+      const float v = load_one<T>(x + e);
+      const float sc = scale_shift[c];
+      const float dy = pooled_dq1<T>(g, e / C, C, c, HW) * act_mask<ACT>(fmaf(sc, v, scale_shift[C + c]));
+      const float xh = (v - mean_invstd[c]) * mean_invstd[C + c];
+      store_one<T>(dx + e, sc * (dy - dbeta[c] * inv_n - xh * (dgamma[c] * inv_n)));
+    }
+  }
+}
+
+template <typename T>
+static int launch_bn_bwd_apply_pooled(const T* g, const T* x, T* dx, int64_t rows, int C, int HW, const float* ss,
+                                      const float* mi, const float* dgamma, const float* dbeta, int act, hipStream_t st) {
+  const bool fast = bn_fast_ok(C) && pf_aligned16(x) && pf_aligned16(g) && pf_aligned16(dx);
+  const int grid = fast ? pf_grid_for(rows, (PF_THREADS / (C / 8)) * 2) : pf_grid_for(rows * C, PF_THREADS * 4);
+#define PF_BB(ACTV)                                                                                                    \
+  do {                                                                                                                 \
+    if (fast) k_bn_bwd_apply_pooled<T, ACTV, true><<<grid, PF_THREADS, 0, st>>>(g, x, dx, rows, C, ss, mi, dgamma, dbeta, HW);   \
+    else k_bn_bwd_apply_pooled<T, ACTV, false><<<grid, PF_THREADS, 0, st>>>(g, x, dx, rows, C, ss, mi, dgamma, dbeta, HW);       \
+  } while (0)
+  if (act == PF_ACT_RELU) PF_BB(PF_ACT_RELU);
+  else if (act == PF_ACT_RELU6) PF_BB(PF_ACT_RELU6);
+  else PF_BB(PF_ACT_NONE);
+#undef PF_BB
+  PF_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int pf_bn_bwd_apply_pooled(const void* g, const void* x, void* dx, int dtype, int64_t rows, int C, int HW,
+                                      const float* scale_shift, const float* mean_invstd, const float* dgamma,
+                                      const float* dbeta, int act, void* stream) {
+  if (C <= 0 || !bn_pooled_ok(rows, HW)) return (int)hipErrorInvalidValue;
+  if (dtype == PF_F32) return launch_bn_bwd_apply_pooled<float>((const float*)g, (const float*)x, (float*)dx, rows, C, HW, scale_shift, mean_invstd, dgamma, dbeta, act, (hipStream_t)stream);
+  if (dtype == PF_BF16) return launch_bn_bwd_apply_pooled<bf16_t>((const bf16_t*)g, (const bf16_t*)x, (bf16_t*)dx, rows, C, HW, scale_shift, mean_invstd, dgamma, dbeta, act, (hipStream_t)stream);
+  return (int)hipErrorInvalidValue;
 }

@@ -54,6 +54,11 @@ __device__ __forceinline__ bf16_t f32_to_bf16(float f) {
   return (bf16_t)(u >> 16);
 }
 
+// a float32 value rounded to the storage type T and back: what a store + load of T would make of it
+template <typename T> __device__ __forceinline__ float round_to(float v);
+template <> __device__ __forceinline__ float round_to<float>(float v) { return v; }
+template <> __device__ __forceinline__ float round_to<bf16_t>(float v) { return bf16_to_f32(f32_to_bf16(v)); }
+
 // ---- 16-byte vector access: 4 x f32 or 8 x bf16 per lane -------------------------------------
 template <typename T> struct VecTraits;
 template <> struct VecTraits<float> { static constexpr int N = 4; };

@@ -47,6 +47,10 @@ from pocketflow_amd.profiling import region
 ALIGN = 64  # elements; keeps every tensor 256-byte aligned inside the flat buffers
 # reduce the BN-backward statistics inside the backward-data kernel of the single consuming 1x1 convolution
 FUSE_BN_BWD_STATS = os.environ.get('PF_FUSE_BN_BWD_STATS', '1') != '0'
+# the network head in fused launches: the last BN reduced to its spatial mean in pass 2 and never written (pf_bn_act_quant_pool, both
+# backward passes rebuilt from the pooled gradient), the step's two losses + metrics in one launch (losses.py).  0: the separate chain.
+HEAD_FUSE = os.environ.get('PF_HEAD_FUSE', '1') != '0'
+HEAD_FUSE_ANY_DEVICE = False     # tests: run the head plumbing on CPU tensors (the HIP entry points are emulated there)
 
 
 def _align(n: int) -> int:
@@ -664,6 +668,56 @@ class _BnEvalAct(torch.autograd.Function):
     return dx, dgamma, dbeta, None, None
 
 
+class _BnActPool(torch.autograd.Function):
+  """The network head: BN -> act -> activation fake-quant -> mean over H, W, without the activated map in between
+  (pf_bn_act_quant_pool; x.float().mean(dim=(2, 3)).to(x.dtype) of the q _BnActQuant / _BnEvalAct would have written).
+  `training`: batch statistics (from the producing convolution's epilogue when it left them), else inference mode WITH
+  gradients (_BnEvalAct's case: moving statistics, backward with zero sums).  Returns [B][C]; backward takes its gradient
+  and runs the pooled forms of the two BN-backward passes, dgamma / dbeta straight into the flat gradient views."""
+
+  @staticmethod
+  def forward(ctx, x, gamma, beta, layer, graph, training, slot, bits, stats=None):
+    x = _nhwc(x)
+    C = gamma.numel()
+    rows = x.numel() // C
+    hw = rows // x.shape[0]
+    quantize = bits is not None
+    scale_shift = torch.empty((2, C), dtype=torch.float32, device=x.device)
+    if training:
+      mean_invstd = torch.empty((2, C), dtype=torch.float32, device=x.device)
+      partial, nblk, piv = _bn_statistics(x, rows, C, graph, stats)
+      hip.bn_finalize(partial, nblk, rows, C, piv, gamma, beta, layer.moving_mean.tensor, layer.moving_var.tensor,
+                      layer.momentum, layer.eps, True, layer.act, scale_shift, mean_invstd, slot if quantize else None)
+    else:
+      hip.bn_eval_scale_shift(gamma.detach(), beta.detach(), layer.moving_mean.tensor, layer.moving_var.tensor,
+                              layer.eps, scale_shift)
+      mean_invstd = torch.stack([layer.moving_mean.tensor.float(),
+                                 torch.rsqrt(layer.moving_var.tensor.float() + layer.eps)]).contiguous()
+    pooled = torch.empty((x.shape[0], C), dtype=x.dtype, device=x.device)
+    with region('bn_act_quant_pool', float(x.numel() * x.element_size())):   # 1 read of x
+      hip.bn_act_quant_pool(x, pooled, rows, C, hw, scale_shift, layer.act, slot, bits if quantize else 8, quantize)
+    ctx.save_for_backward(x, scale_shift, mean_invstd)
+    ctx.meta = (layer.act, graph, rows, C, hw, not training)
+    ctx.params = (gamma, beta)
+    return pooled
+
+  @staticmethod
+  def backward(ctx, g):
+    x, scale_shift, mean_invstd = ctx.saved_tensors
+    act, graph, rows, C, hw, frozen = ctx.meta
+    dx, dgamma, dbeta = _bn_backward(g.contiguous(), x, scale_shift, mean_invstd, act, graph, rows, C, params=ctx.params,
+                                     frozen=frozen, pool_hw=hw)
+    return dx, dgamma, dbeta, None, None, None, None, None, None
+
+
+def head_fuse_ok(graph, x) -> bool:
+  """The fused head takes this tensor: switch on, no taps, a float32 / bf16 GPU tensor and a library (or test double) with the
+  entry points."""
+  return (HEAD_FUSE and graph.taps is None and isinstance(x, torch.Tensor) and (x.is_cuda or HEAD_FUSE_ANY_DEVICE)
+          and x.dtype in (torch.float32, torch.bfloat16)
+          and hasattr(hip, 'bn_act_quant_pool') and hasattr(hip, 'bn_bwd_stats_pooled') and hasattr(hip, 'bn_bwd_apply_pooled'))
+
+
 class _ActQuant(torch.autograd.Function):
   """act -> per-tensor fake-quant (pf_minmax_tensor + pf_uq_apply); backward = STE o act'."""
 
@@ -819,12 +873,13 @@ def _grad_view(t: Optional[torch.Tensor], n: int):
 
 
 def _bn_backward(dq, x, scale_shift, mean_invstd, act, graph, rows, C, addend=None, params=None, pre=None,
-                 frozen=False):
+                 frozen=False, pool_hw=None):
   """Returns (dx, dgamma, dbeta); when `params` = (gamma leaf, beta leaf) carry flat-buffer gradient views,
   dgamma / dbeta are written there by pf_bn_bwd_finalize and None is returned for them (no accumulation
   kernels; every BN layer is applied once per step and the buffers are zeroed by the optimiser).
   `frozen`: inference-mode BN (moving statistics are constants): the batch-statistics terms of dx vanish,
-  dx = scale * dy -- the same apply kernel fed with zero sums."""
+  dx = scale * dy -- the same apply kernel fed with zero sums.
+  `pool_hw`: dq is the [B][C] gradient of the POOLED tensor (_BnActPool); both passes rebuild the per-pixel value from it."""
   dq = _nhwc(dq)
   if dq.dtype != x.dtype:
     dq = dq.to(x.dtype)
@@ -838,8 +893,12 @@ def _bn_backward(dq, x, scale_shift, mean_invstd, act, graph, rows, C, addend=No
   else:
     nblk = _bn_blocks(rows, C)
     partial = graph.scratch(nblk * 2 * C)
-    with region('bn_bwd_stats', 2 * nbytes):       # reads dq and x
-      hip.bn_bwd_stats(dq, x, rows, C, scale_shift, mean_invstd, act, partial, nblk)
+    if pool_hw is not None:
+      with region('bn_bwd_stats_pooled', nbytes):  # reads x (and the small pooled gradient)
+        hip.bn_bwd_stats_pooled(dq, x, rows, C, pool_hw, scale_shift, mean_invstd, act, partial, nblk)
+    else:
+      with region('bn_bwd_stats', 2 * nbytes):     # reads dq and x
+        hip.bn_bwd_stats(dq, x, rows, C, scale_shift, mean_invstd, act, partial, nblk)
   gview = _grad_view(params[0], C) if params is not None else None
   bview = _grad_view(params[1], C) if params is not None else None
   direct = gview is not None and bview is not None
@@ -847,8 +906,13 @@ def _bn_backward(dq, x, scale_shift, mean_invstd, act, graph, rows, C, addend=No
   dbeta = bview if direct else torch.empty(C, dtype=torch.float32, device=x.device)
   hip.bn_bwd_finalize(partial, nblk, C, dgamma, dbeta)
   dx = torch.empty_like(x)
+  zero = graph.zero_row(C)[:C] if frozen else None
+  if pool_hw is not None:
+    with region('bn_bwd_apply_pooled', 2 * nbytes):                         # reads x, writes dx
+      hip.bn_bwd_apply_pooled(dq, x, dx, rows, C, pool_hw, scale_shift, mean_invstd, zero if frozen else dgamma,
+                              zero if frozen else dbeta, act)
+    return (dx, None, None) if direct else (dx, dgamma, dbeta)
   with region('bn_bwd_apply', (4 if addend is not None else 3) * nbytes):   # reads dq, x [, addend], writes dx
-    zero = graph.zero_row(C)[:C] if frozen else None
     hip.bn_bwd_apply(dq, x, dx, rows, C, scale_shift, mean_invstd, zero if frozen else dgamma,
                      zero if frozen else dbeta, act, addend)
   return (dx, None, None) if direct else (dx, dgamma, dbeta)
@@ -1848,6 +1912,39 @@ class BatchNormAct:
     if g.taps is not None and isinstance(y, torch.Tensor):
       y = _pass_tag(x, y)
     return (y, skip) if with_skip else y
+
+  def pooled(self, x: torch.Tensor):
+    """mean over H, W of this layer's output as [B][C], in the fused head launches (_BnActPool; the activated map is never written)
+    -- or None where the caller has to take the separate chain: PF_HEAD_FUSE=0, taps, no GPU tensor, a library without the
+    entry points, a layer already applied in the producing convolution's epilogue."""
+    g = self.graph
+    if not head_fuse_ok(g, x) or x.dim() != 4 or getattr(x, '_pf_bn_done', None) is self:
+      return None
+    bits = self.op.bits if self.op is not None else None
+    slot = g.act_slots[self.op.index] if (self.op is not None and bits is not None) else None
+    if g.training and torch.is_grad_enabled():
+      return _BnActPool.apply(x, self.gamma.tensor, self.beta.tensor, self, g, True, slot, bits, getattr(x, '_pf_stats', None))
+    if torch.is_grad_enabled() and not g.frozen and (x.requires_grad or self.gamma.tensor.requires_grad):
+      if bits is not None:
+        raise NotImplementedError('inference-mode BN with gradients and activation quantisation (no learner needs it)')
+      return _BnActPool.apply(x, self.gamma.tensor, self.beta.tensor, self, g, False, None, None)
+    x = _nhwc(x)
+    C = self.C
+    rows = x.numel() // C
+    pooled = torch.empty((x.shape[0], C), dtype=x.dtype, device=x.device)
+    if bits is None:
+      hip.bn_act_quant_pool(x, pooled, rows, C, rows // x.shape[0], self._eval_scale_shift(x), self.act, None, 8, False)
+      return pooled
+    with torch.no_grad():                          # eval graph of a quantising learner, as _inference
+      nblk = _bn_blocks(rows, C)
+      partial = g.scratch(nblk * 4 * C)
+      ss = torch.empty((2, C), dtype=torch.float32, device=x.device)
+      mi = torch.empty((2, C), dtype=torch.float32, device=x.device)
+      hip.bn_stats(x, rows, C, partial, nblk)
+      hip.bn_finalize(partial, nblk, rows, C, x, self.gamma.tensor, self.beta.tensor, self.moving_mean.tensor,
+                      self.moving_var.tensor, self.momentum, self.eps, g.training, self.act, ss, mi, slot)
+      hip.bn_act_quant_pool(x, pooled, rows, C, rows // x.shape[0], ss, self.act, slot, bits, True)
+    return pooled
 
   def _inference(self, x, slot, bits, lazy):
     """Inference mode without gradients, x in NHWC memory."""

@@ -55,6 +55,7 @@ SYMBOLS = [
     'pf_cpr_gather', 'pf_cpr_gram_ws', 'pf_cpr_gram', 'pf_cpr_ista', 'pf_cpr_lstsq_splits', 'pf_cpr_lstsq_step', 'pf_cpr_lstsq_resid',
     'pf_conv_gather_fwd',
     'pf_conv1x1_join_plan', 'pf_conv1x1_bwd_data_join',
+    'pf_bn_act_quant_pool', 'pf_bn_bwd_stats_pooled', 'pf_bn_bwd_apply_pooled', 'pf_ce_distill_head', 'pf_ce_combine',
 ]
 
 
@@ -410,6 +411,20 @@ def ce_distill_fwd_bwd(z_s, labels, z_t, tempr: float, loss_w: float, losses, dz
                                     c_int(dtype_code(dz_s)), _ptr(row_ws), _stream()), 'pf_ce_distill_fwd_bwd')
 
 
+def ce_distill_head(z_s, labels, z_t, tempr: float, loss_w: float, losses, dz_hard, dz_soft, row_ws) -> None:
+  """One launch for the step's whole loss: losses[4] = (L_model, L_dst, top-1, top-5), the two terms of dz_s stored apart."""
+  B, C = z_s.shape
+  _check(_lib.pf_ce_distill_head(_ptr(z_s), c_int(dtype_code(z_s)), _ptr(labels), _ptr(z_t),
+                                 c_int(dtype_code(z_t) if z_t is not None else 0), c_int(B), c_int(C),
+                                 c_float(tempr), c_float(loss_w), _ptr(losses), _ptr(dz_hard), _ptr(dz_soft),
+                                 c_int(dtype_code(dz_hard)), _ptr(row_ws), _stream()), 'pf_ce_distill_head')
+
+
+def ce_combine(dz_hard, dz_soft, g0, g1, dz) -> None:
+  _check(_lib.pf_ce_combine(_ptr(dz_hard), _ptr(dz_soft), _ptr(g0), _ptr(g1), _ptr(dz), c_int(dtype_code(dz)),
+                            c_int64(dz.numel()), _stream()), 'pf_ce_combine')
+
+
 # ------------------------------------------------------------------------------------------------
 # fused BN + act + fake-quant
 # ------------------------------------------------------------------------------------------------
@@ -431,6 +446,24 @@ def bn_act_quant_apply(x, q, rows, C, scale_shift, act, slot, bits: int, quantiz
   _check(_lib.pf_bn_act_quant_apply(_ptr(x), _ptr(q), c_int(dtype_code(x)), c_int64(rows), c_int(C),
                                     _ptr(scale_shift), c_int(ACT_CODES[act]), _ptr(slot), c_int(int(bits)),
                                     c_int(1 if quantize else 0), _stream()), 'pf_bn_act_quant_apply')
+
+
+def bn_act_quant_pool(x, pooled, rows, C, hw: int, scale_shift, act, slot, bits: int, quantize: bool) -> None:
+  _check(_lib.pf_bn_act_quant_pool(_ptr(x), _ptr(pooled), c_int(dtype_code(x)), c_int64(rows), c_int(C),
+                                   _ptr(scale_shift), c_int(ACT_CODES[act]), _ptr(slot), c_int(int(bits)),
+                                   c_int(1 if quantize else 0), c_int(hw), _stream()), 'pf_bn_act_quant_pool')
+
+
+def bn_bwd_stats_pooled(g, x, rows, C, hw: int, scale_shift, mean_invstd, act, partial, n_blocks) -> None:
+  _check(_lib.pf_bn_bwd_stats_pooled(_ptr(g), _ptr(x), c_int(dtype_code(x)), c_int64(rows), c_int(C), c_int(hw),
+                                     _ptr(scale_shift), _ptr(mean_invstd), c_int(ACT_CODES[act]), _ptr(partial),
+                                     c_int(n_blocks), _stream()), 'pf_bn_bwd_stats_pooled')
+
+
+def bn_bwd_apply_pooled(g, x, dx, rows, C, hw: int, scale_shift, mean_invstd, dgamma, dbeta, act) -> None:
+  _check(_lib.pf_bn_bwd_apply_pooled(_ptr(g), _ptr(x), _ptr(dx), c_int(dtype_code(x)), c_int64(rows), c_int(C),
+                                     c_int(hw), _ptr(scale_shift), _ptr(mean_invstd), _ptr(dgamma), _ptr(dbeta),
+                                     c_int(ACT_CODES[act]), _stream()), 'pf_bn_bwd_apply_pooled')
 
 
 def bn_bwd_stats(dq, x, rows, C, scale_shift, mean_invstd, act, partial, n_blocks) -> None:

@@ -309,6 +309,8 @@ class ChannelPrunedLearner(AbstractLearner):  # pylint: disable=too-many-instanc
       if FLAGS.enbl_dst and logits_dst is None:
         logits_dst = self.learner_dst.calc_logits(None, x)
       logits = self.forward_train(x)
+      if FLAGS.enbl_dst:
+        self.learner_dst.prime(logits, logits_dst)           # both losses out of calc_loss's one kernel launch
       loss, metrics = self.calc_loss(y, logits, self.trainable_vars)
       if FLAGS.enbl_dst:
         loss = loss + self.learner_dst.calc_loss(logits, logits_dst)

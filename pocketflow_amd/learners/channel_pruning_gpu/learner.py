@@ -186,6 +186,8 @@ class ChannelPrunedGpuLearner(AbstractLearner):  # pylint: disable=too-many-inst
     with g.as_default():
       logits_dst = self.helper_dst.calc_logits(None, x) if FLAGS.enbl_dst else None
       logits = self.forward_train(x)
+      if FLAGS.enbl_dst:
+        self.helper_dst.prime(logits, logits_dst)           # both losses out of calc_loss's one kernel launch
       loss, metrics = self.calc_loss(y, logits, self.vars_prnd['trainable'])
       if FLAGS.enbl_dst:
         loss = loss + self.helper_dst.calc_loss(logits, logits_dst)

@@ -3,7 +3,7 @@
 A frozen full-precision teacher (scope `distilled_model`, weights copied from ./models with the first
 path component renamed, :122-145) produces `logits_dst`; `calc_loss` is the temperature-softened
 soft-label cross-entropy times `loss_w_dst` (:86-103) -- computed, with its gradient, by ONE fused HIP
-kernel (pocketflow_amd.losses.distillation_loss -> pf_ce_distill_fwd_bwd).
+kernel (pocketflow_amd.losses.distillation_loss -> pf_ce_distill_fwd_bwd; after `prime`, by the model loss's own launch).
 """
 from __future__ import annotations
 
@@ -49,6 +49,12 @@ class DistillationHelper(object):
       with g.as_default():
         logits = self.learner.forward_eval(images)
     return logits.detach()
+
+  @classmethod
+  def prime(cls, logits_pri, logits_dst):
+    """Before ModelHelper.calc_loss(labels, logits_pri, ...) when calc_loss(logits_pri, logits_dst) follows: both losses then come
+    out of the model loss's one kernel launch (losses.prime_distillation).  Optional; signatures stay the reference's."""
+    losses.prime_distillation(logits_pri, logits_dst, FLAGS.tempr_dst, FLAGS.loss_w_dst)
 
   @classmethod
   def calc_loss(cls, logits_pri, logits_dst):

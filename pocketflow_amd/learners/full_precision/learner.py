@@ -64,6 +64,8 @@ class FullPrecLearner(AbstractLearner):  # pylint: disable=too-many-instance-att
     with g.as_default():
       logits_dst = self.helper_dst.calc_logits(None, x) if self.enbl_dst else None
       logits = self.forward_train(x)
+      if self.enbl_dst:
+        self.helper_dst.prime(logits, logits_dst)           # both losses out of calc_loss's one kernel launch
       loss, metrics = self.calc_loss(y, logits, self.trainable_vars)
       if self.enbl_dst:
         loss = loss + self.helper_dst.calc_loss(logits, logits_dst)

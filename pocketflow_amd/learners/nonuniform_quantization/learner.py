@@ -99,6 +99,8 @@ class NonUniformQuantLearner(AbstractLearner):
       if FLAGS.enbl_dst and logits_dst is None:
         logits_dst = self.helper_dst.calc_logits(None, x)
       logits = self.forward_train(x)
+      if FLAGS.enbl_dst:
+        self.helper_dst.prime(logits, logits_dst)           # both losses out of calc_loss's one kernel launch
       model_loss, metrics = self.calc_loss(y, logits, self.trainable_vars)
       loss, dst_loss = model_loss, None
       if FLAGS.enbl_dst:

@@ -104,6 +104,8 @@ class UniformQuantLearner(AbstractLearner):
       if FLAGS.enbl_dst and logits_dst is None:
         logits_dst = self.helper_dst.calc_logits(None, x)
       logits = self.forward_train(x)
+      if FLAGS.enbl_dst:
+        self.helper_dst.prime(logits, logits_dst)           # both losses out of calc_loss's one kernel launch
       model_loss, metrics = self.calc_loss(y, logits, self.trainable_vars)
       loss = model_loss
       dst_loss = None

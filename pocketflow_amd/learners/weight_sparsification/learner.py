@@ -85,6 +85,8 @@ class WeightSparseLearner(AbstractLearner):  # pylint: disable=too-many-instance
       if FLAGS.enbl_dst and logits_dst is None:
         logits_dst = self.helper_dst.calc_logits(None, x)
       logits = self.forward_train(x)
+      if FLAGS.enbl_dst:
+        self.helper_dst.prime(logits, logits_dst)           # both losses out of calc_loss's one kernel launch
       loss, metrics = self.calc_loss(y, logits, self.trainable_vars)
       if FLAGS.enbl_dst:
         loss = loss + self.helper_dst.calc_loss(logits, logits_dst)

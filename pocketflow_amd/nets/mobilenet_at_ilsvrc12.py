@@ -60,9 +60,7 @@ class ModelHelper(AbstractModelHelper):
     loss = losses.softmax_cross_entropy(labels, outputs)
     loss_filter = lambda var: 'batch_normalization' not in var.name
     loss = loss + losses.l2_regularization(trainable_vars, loss_filter, FLAGS.loss_w_dcy)
-    targets = labels.argmax(dim=1)
-    acc_top1 = losses.in_top_k(outputs, targets, 1).float().mean()
-    acc_top5 = losses.in_top_k(outputs, targets, 5).float().mean()
+    acc_top1, acc_top5 = losses.top_k_accuracies(labels, outputs, (1, 5))
     metrics = {'accuracy': acc_top5, 'acc_top1': acc_top1, 'acc_top5': acc_top5}
     return loss, metrics
 
