@@ -26,6 +26,13 @@ static inline bool bn_fast_ok(int C) {
   return (C % 64) == 0 && G <= 256 && (256 % G) == 0;    // streaming kernels keep the (256 % G) map
 }
 
+// The storage type of an extern "C" entry: f is called with a null T* (T = float / bf16_t) and returns the entry's status.
+template <typename F> static inline int bn_with_dtype(int dtype, F&& f) {
+  if (dtype == PF_F32) return f((float*)nullptr);
+  if (dtype == PF_BF16) return f((bf16_t*)nullptr);
+  return (int)hipErrorInvalidValue;
+}
+
 // ---------------------------------------------------------------------------------------------
 // forward pass 1
 // ---------------------------------------------------------------------------------------------
@@ -34,7 +41,7 @@ static inline bool bn_fast_ok(int C) {
 // 1024/CG row-lanes walk the rows.  Per-workgroup partials are only 4 x 64 floats, so the partial
 // buffer [nsplit][4][C] stays ~1000x smaller than the tensor and the finalize pass is a few us.
 #define BN_BIG 1024
-__device__ __forceinline__ int bn_cg_of(int C) { return (C >> 3) < 8 ? (C >> 3) : 8; }
+__host__ __device__ __forceinline__ int bn_cg_of(int C) { return (C >> 3) < 8 ? (C >> 3) : 8; }
 
 // KIND per statistic: 0 = sum, 1 = min, 2 = max
 template <int KIND> __device__ __forceinline__ float bn_comb(float a, float b) {
@@ -126,20 +133,18 @@ extern "C" int pf_bn_stats(const void* x, int dtype, int64_t rows, int C, float*
                            int n_blocks, void* stream) {
   if (rows <= 0 || C <= 0 || n_blocks <= 0) return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
-  if (bn_fast_ok(C) && pf_aligned16(x)) {
-    const int CG = (C / 8) < 8 ? (C / 8) : 8;
-    const int nslab = C / (CG * 8);
-    if (dtype == PF_F32) k_bn_stats_fast<float><<<nslab * n_blocks, BN_BIG, 0, st>>>((const float*)x, rows, C, partial, nslab, n_blocks);
-    else if (dtype == PF_BF16) k_bn_stats_fast<bf16_t><<<nslab * n_blocks, BN_BIG, 0, st>>>((const bf16_t*)x, rows, C, partial, nslab, n_blocks);
-    else return (int)hipErrorInvalidValue;
-  } else {
-    dim3 grid((C + PF_THREADS - 1) / PF_THREADS, n_blocks);
-    if (dtype == PF_F32) k_bn_stats_generic<float><<<grid, PF_THREADS, 0, st>>>((const float*)x, rows, C, partial);
-    else if (dtype == PF_BF16) k_bn_stats_generic<bf16_t><<<grid, PF_THREADS, 0, st>>>((const bf16_t*)x, rows, C, partial);
-    else return (int)hipErrorInvalidValue;
-  }
-  PF_LAUNCH_CHECK();
-  return 0;
+  return bn_with_dtype(dtype, [&](auto* t) {
+    using T = std::remove_pointer_t<decltype(t)>;
+    if (bn_fast_ok(C) && pf_aligned16(x)) {
+      const int nslab = C / (bn_cg_of(C) * 8);
+      k_bn_stats_fast<T><<<nslab * n_blocks, BN_BIG, 0, st>>>((const T*)x, rows, C, partial, nslab, n_blocks);
+    } else {
+      dim3 grid((C + PF_THREADS - 1) / PF_THREADS, n_blocks);
+      k_bn_stats_generic<T><<<grid, PF_THREADS, 0, st>>>((const T*)x, rows, C, partial);
+    }
+    PF_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -328,15 +333,11 @@ static int launch_bn_apply(const T* x, T* q, int64_t rows, int C, const float* s
                            const uint32_t* slot, float k, int quantize, hipStream_t st) {
   const bool fast = bn_fast_ok(C) && pf_aligned16(x) && pf_aligned16(q);
   const int grid = fast ? pf_grid_for(rows, (PF_THREADS / (C / 8)) * 2) : pf_grid_for(rows * C, PF_THREADS * 4);
-#define PF_BA(ACTV)                                                                                     \
-  do {                                                                                                  \
-    if (fast) k_bn_apply<T, ACTV, true><<<grid, PF_THREADS, 0, st>>>(x, q, rows, C, ss, slot, k, quantize);   \
-    else k_bn_apply<T, ACTV, false><<<grid, PF_THREADS, 0, st>>>(x, q, rows, C, ss, slot, k, quantize);       \
-  } while (0)
-  if (act == PF_ACT_RELU) PF_BA(PF_ACT_RELU);
-  else if (act == PF_ACT_RELU6) PF_BA(PF_ACT_RELU6);
-  else PF_BA(PF_ACT_NONE);
-#undef PF_BA
+  pf_with_act(act, [&](auto A) {
+    pf_with_bool(fast, [&](auto F) {
+      k_bn_apply<T, decltype(A)::value, decltype(F)::value><<<grid, PF_THREADS, 0, st>>>(x, q, rows, C, ss, slot, k, quantize);
+    });
+  });
   PF_LAUNCH_CHECK();
   return 0;
 }
@@ -347,9 +348,10 @@ extern "C" int pf_bn_act_quant_apply(const void* x, void* q, int dtype, int64_t 
   if (rows <= 0 || C <= 0) return (int)hipErrorInvalidValue;
   if (quantize && (bits < 1 || bits > 32 || slot == nullptr)) return (int)hipErrorInvalidValue;
   const float k = uq_k_of_bits(quantize ? bits : 8);
-  if (dtype == PF_F32) return launch_bn_apply<float>((const float*)x, (float*)q, rows, C, scale_shift, act, slot, k, quantize, (hipStream_t)stream);
-  if (dtype == PF_BF16) return launch_bn_apply<bf16_t>((const bf16_t*)x, (bf16_t*)q, rows, C, scale_shift, act, slot, k, quantize, (hipStream_t)stream);
-  return (int)hipErrorInvalidValue;
+  return bn_with_dtype(dtype, [&](auto* t) {
+    using T = std::remove_pointer_t<decltype(t)>;
+    return launch_bn_apply<T>((const T*)x, (T*)q, rows, C, scale_shift, act, slot, k, quantize, (hipStream_t)stream);
+  });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -414,15 +416,11 @@ static int launch_bn_apply_pool(const T* x, T* pooled, int64_t rows, int C, int 
   const int64_t items = fast ? B * (C / 8) : B * C;
   const int64_t grid = (items + PF_THREADS - 1) / PF_THREADS;
   if (grid > 0x7FFFFFFF) return (int)hipErrorInvalidValue;
-#define PF_BP(ACTV)                                                                                                          \
-  do {                                                                                                                       \
-    if (fast) k_bn_apply_pool<T, ACTV, true><<<(int)grid, PF_THREADS, 0, st>>>(x, pooled, (int)B, HW, C, ss, slot, k, quantize);   \
-    else k_bn_apply_pool<T, ACTV, false><<<(int)grid, PF_THREADS, 0, st>>>(x, pooled, (int)B, HW, C, ss, slot, k, quantize);       \
-  } while (0)
-  if (act == PF_ACT_RELU) PF_BP(PF_ACT_RELU);
-  else if (act == PF_ACT_RELU6) PF_BP(PF_ACT_RELU6);
-  else PF_BP(PF_ACT_NONE);
-#undef PF_BP
+  pf_with_act(act, [&](auto A) {
+    pf_with_bool(fast, [&](auto F) {
+      k_bn_apply_pool<T, decltype(A)::value, decltype(F)::value><<<(int)grid, PF_THREADS, 0, st>>>(x, pooled, (int)B, HW, C, ss, slot, k, quantize);
+    });
+  });
   PF_LAUNCH_CHECK();
   return 0;
 }
@@ -433,17 +431,46 @@ extern "C" int pf_bn_act_quant_pool(const void* x, void* pooled, int dtype, int6
   if (rows <= 0 || C <= 0 || HW <= 0 || rows % HW != 0 || rows / HW > 0x7FFFFFFF) return (int)hipErrorInvalidValue;
   if (quantize && (bits < 1 || bits > 32 || slot == nullptr)) return (int)hipErrorInvalidValue;
   const float k = uq_k_of_bits(quantize ? bits : 8);
-  if (dtype == PF_F32) return launch_bn_apply_pool<float>((const float*)x, (float*)pooled, rows, C, HW, scale_shift, act, slot, k, quantize, (hipStream_t)stream);
-  if (dtype == PF_BF16) return launch_bn_apply_pool<bf16_t>((const bf16_t*)x, (bf16_t*)pooled, rows, C, HW, scale_shift, act, slot, k, quantize, (hipStream_t)stream);
-  return (int)hipErrorInvalidValue;
+  return bn_with_dtype(dtype, [&](auto* t) {
+    using T = std::remove_pointer_t<decltype(t)>;
+    return launch_bn_apply_pool<T>((const T*)x, (T*)pooled, rows, C, HW, scale_shift, act, slot, k, quantize, (hipStream_t)stream);
+  });
+}
+
+// ---------------------------------------------------------------------------------------------
+// backward: where dq comes from
+// ---------------------------------------------------------------------------------------------
+// The two backward passes below are templates over POOLED.  false: dq is the [rows][C] gradient of this BN's output, read as it
+// is.  true (the network head, HW > 0): this BN's output feeds nothing but the spatial mean (pf_bn_act_quant_pool), so `dq` is the
+// [B][C] gradient of the POOLED tensor and the value of row r = (b, p) is rebuilt on the fly,
+// T(float(dq[b][c]) * float32(1 / HW)) -- bit for bit what autograd's cast / mean / cast chain writes into the expanded
+// [B * HW][C] tensor on the device (aten divides a tensor by a host scalar as a product with the rounded reciprocal), which is then
+// never stored or read.  Only the dq load depends on POOLED (and the head has no shortcut: the pooled apply pass drops the addend
+// test): row order, splits and the partial layout are shared, so every sum and dx of the pooled form are bit-identical to the
+// plain pass over the expanded tensor.  HW sits in the 4 bytes of padding behind C, which leaves every other kernel argument at
+// its offset, and the plain instantiations never load it.  b = r / HW is a 32-bit division (a 64-bit one is a long software
+// sequence per row in the loop): the pooled entry points require rows < 2^31 (bn_pooled_ok).
+template <typename T>
+__device__ __forceinline__ void pooled_dq8(const T* __restrict__ g, int64_t r, int C, int c0, int HW, float (&out)[8]) {
+  const float inv_hw = 1.0f / (float)HW;
+  load8<T>(g + (int64_t)((uint32_t)r / (uint32_t)HW) * C + c0, out);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) out[j] = round_to<T>(out[j] * inv_hw);
+}
+template <typename T>
+__device__ __forceinline__ float pooled_dq1(const T* __restrict__ g, int64_t r, int C, int c, int HW) {
+  return round_to<T>(load_one<T>(g + (int64_t)((uint32_t)r / (uint32_t)HW) * C + c) * (1.0f / (float)HW));
+}
+static inline bool bn_pooled_ok(int64_t rows, int HW) {
+  return HW > 0 && rows > 0 && rows < ((int64_t)1 << 31) && rows % HW == 0;
 }
 
 // ---------------------------------------------------------------------------------------------
 // backward pass 1: per-channel sum(dy), sum(dy * xhat),  dy = dq * act'(scale*x+shift)
 // ---------------------------------------------------------------------------------------------
-template <typename T, int ACT>
+template <typename T, int ACT, bool POOLED>
 __global__ __launch_bounds__(BN_BIG) void k_bn_bwd_stats_fast(const T* __restrict__ dq, const T* __restrict__ x,
-                                                              int64_t rows, int C,
+                                                              int64_t rows, int C, int HW,
                                                               const float* __restrict__ scale_shift,
                                                               const float* __restrict__ mean_invstd,
                                                               float* __restrict__ partial, int nslab, int nsplit) {
@@ -464,7 +491,8 @@ __global__ __launch_bounds__(BN_BIG) void k_bn_bwd_stats_fast(const T* __restric
   for (int64_t r = (int64_t)split * RL + rl; r < rows; r += (int64_t)nsplit * RL) {
     float g[8], v[8];
     const int64_t off = r * C + c0;
-    load8<T>(dq + off, g);
+    if (POOLED) pooled_dq8<T>(dq, r, C, c0, HW, g);
+    else load8<T>(dq + off, g);
     load8<T>(x + off, v);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -481,9 +509,9 @@ __global__ __launch_bounds__(BN_BIG) void k_bn_bwd_stats_fast(const T* __restric
   bn_lds_finish<0>(1, 2, slabC, lds, out + C);
 }
 
-template <typename T, int ACT>
+template <typename T, int ACT, bool POOLED>
 __global__ __launch_bounds__(PF_THREADS) void k_bn_bwd_stats_generic(const T* __restrict__ dq, const T* __restrict__ x,
-                                                                     int64_t rows, int C,
+                                                                     int64_t rows, int C, int HW,
                                                                      const float* __restrict__ scale_shift,
                                                                      const float* __restrict__ mean_invstd,
                                                                      float* __restrict__ partial) {
@@ -493,7 +521,8 @@ __global__ __launch_bounds__(PF_THREADS) void k_bn_bwd_stats_generic(const T* __
   float s1 = 0.f, s2 = 0.f;
   for (int64_t r = blockIdx.y; r < rows; r += gridDim.y) {
     const float v = load_one<T>(x + r * C + c);
-    const float dy = load_one<T>(dq + r * C + c) * act_mask<ACT>(fmaf(sc, v, sh));
+    const float g = POOLED ? pooled_dq1<T>(dq, r, C, c, HW) : load_one<T>(dq + r * C + c);
+    const float dy = g * act_mask<ACT>(fmaf(sc, v, sh));
     s1 += dy;
     s2 = fmaf(dy, (v - mu) * is, s2);
   }
@@ -501,33 +530,44 @@ __global__ __launch_bounds__(PF_THREADS) void k_bn_bwd_stats_generic(const T* __
   out[c] = s1; out[C + c] = s2;
 }
 
+// HW = 0: dq is dense; HW > 0: the pooled gradient of HW pixels per image
 template <typename T>
-static int launch_bn_bwd_stats(const T* dq, const T* x, int64_t rows, int C, const float* ss,
+static int launch_bn_bwd_stats(const T* dq, const T* x, int64_t rows, int C, int HW, const float* ss,
                                const float* mi, int act, float* partial, int n_blocks, hipStream_t st) {
   const bool fast = bn_fast_ok(C) && pf_aligned16(x) && pf_aligned16(dq);
-  const int CG = (C / 8) < 8 ? (C / 8) : 8;
-  const int nslab = fast ? C / (CG * 8) : 1;
+  const int nslab = fast ? C / (bn_cg_of(C) * 8) : 1;
   dim3 ggrid((C + PF_THREADS - 1) / PF_THREADS, n_blocks);
-#define PF_BS(ACTV)                                                                                                       \
-  do {                                                                                                                    \
-    if (fast) k_bn_bwd_stats_fast<T, ACTV><<<nslab * n_blocks, BN_BIG, 0, st>>>(dq, x, rows, C, ss, mi, partial, nslab, n_blocks);  \
-    else k_bn_bwd_stats_generic<T, ACTV><<<ggrid, PF_THREADS, 0, st>>>(dq, x, rows, C, ss, mi, partial);                  \
-  } while (0)
-  if (act == PF_ACT_RELU) PF_BS(PF_ACT_RELU);
-  else if (act == PF_ACT_RELU6) PF_BS(PF_ACT_RELU6);
-  else PF_BS(PF_ACT_NONE);
-#undef PF_BS
+  pf_with_act(act, [&](auto A) {
+    pf_with_bool(HW > 0, [&](auto P) {
+      if (fast) k_bn_bwd_stats_fast<T, decltype(A)::value, decltype(P)::value><<<nslab * n_blocks, BN_BIG, 0, st>>>(dq, x, rows, C, HW, ss, mi, partial, nslab, n_blocks);
+      else k_bn_bwd_stats_generic<T, decltype(A)::value, decltype(P)::value><<<ggrid, PF_THREADS, 0, st>>>(dq, x, rows, C, HW, ss, mi, partial);
+    });
+  });
   PF_LAUNCH_CHECK();
   return 0;
+}
+
+static int bn_bwd_stats_entry(const void* dq, const void* x, int dtype, int64_t rows, int C, int HW,
+                              const float* scale_shift, const float* mean_invstd, int act, float* partial,
+                              int n_blocks, void* stream) {
+  return bn_with_dtype(dtype, [&](auto* t) {
+    using T = std::remove_pointer_t<decltype(t)>;
+    return launch_bn_bwd_stats<T>((const T*)dq, (const T*)x, rows, C, HW, scale_shift, mean_invstd, act, partial, n_blocks, (hipStream_t)stream);
+  });
 }
 
 extern "C" int pf_bn_bwd_stats(const void* dq, const void* x, int dtype, int64_t rows, int C,
                                const float* scale_shift, const float* mean_invstd, int act,
                                float* partial, int n_blocks, void* stream) {
   if (rows <= 0 || C <= 0 || n_blocks <= 0) return (int)hipErrorInvalidValue;
-  if (dtype == PF_F32) return launch_bn_bwd_stats<float>((const float*)dq, (const float*)x, rows, C, scale_shift, mean_invstd, act, partial, n_blocks, (hipStream_t)stream);
-  if (dtype == PF_BF16) return launch_bn_bwd_stats<bf16_t>((const bf16_t*)dq, (const bf16_t*)x, rows, C, scale_shift, mean_invstd, act, partial, n_blocks, (hipStream_t)stream);
-  return (int)hipErrorInvalidValue;
+  return bn_bwd_stats_entry(dq, x, dtype, rows, C, 0, scale_shift, mean_invstd, act, partial, n_blocks, stream);
+}
+
+extern "C" int pf_bn_bwd_stats_pooled(const void* g, const void* x, int dtype, int64_t rows, int C, int HW,
+                                      const float* scale_shift, const float* mean_invstd, int act,
+                                      float* partial, int n_blocks, void* stream) {
+  if (C <= 0 || n_blocks <= 0 || !bn_pooled_ok(rows, HW)) return (int)hipErrorInvalidValue;
+  return bn_bwd_stats_entry(g, x, dtype, rows, C, HW, scale_shift, mean_invstd, act, partial, n_blocks, stream);
 }
 
 __global__ __launch_bounds__(PF_THREADS) void k_bn_bwd_finalize(const float* __restrict__ partial, int n_blocks,
@@ -566,16 +606,17 @@ extern "C" int pf_bn_bwd_finalize(const float* partial, int n_blocks, int C, flo
 // ---------------------------------------------------------------------------------------------
 // backward pass 2: dx = gamma*invstd * (dy - dbeta/n - xhat * dgamma/n)
 // ---------------------------------------------------------------------------------------------
-template <typename T, int ACT, bool FAST>
+template <typename T, int ACT, bool FAST, bool POOLED>
 __global__ __launch_bounds__(PF_THREADS) void k_bn_bwd_apply(const T* __restrict__ dq, const T* __restrict__ x,
-                                                             T* __restrict__ dx, int64_t rows, int C,
+                                                             T* __restrict__ dx, int64_t rows, int C, int HW,
                                                              const float* __restrict__ scale_shift,
                                                              const float* __restrict__ mean_invstd,
                                                              const float* __restrict__ dgamma,
                                                              const float* __restrict__ dbeta,
                                                              const T* __restrict__ addend) {
   // addend (optional): the gradient arriving through the block's identity shortcut, which shares x with
-  // this BN -- dx_total = dx_bn + addend in the same pass (autograd would add them in a separate kernel)
+  // this BN -- dx_total = dx_bn + addend in the same pass (autograd would add them in a separate kernel).
+  // Never with POOLED: tested at run time there, the dead branch costs the pooled loop 10 registers.
   const float inv_n = 1.0f / (float)rows;
   if (FAST) {
     const int G = C >> 3, RPS = PF_THREADS / G;
@@ -592,7 +633,8 @@ __global__ __launch_bounds__(PF_THREADS) void k_bn_bwd_apply(const T* __restrict
     for (int64_t r = (int64_t)blockIdx.x * RPS + rsub; r < rows; r += (int64_t)gridDim.x * RPS) {
       float g[8], v[8];
       const int64_t off = r * C + (cg << 3);
-      load8<T>(dq + off, g);
+      if (POOLED) pooled_dq8<T>(dq, r, C, cg << 3, HW, g);
+      else load8<T>(dq + off, g);
       load8<T>(x + off, v);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
@@ -600,7 +642,7 @@ __global__ __launch_bounds__(PF_THREADS) void k_bn_bwd_apply(const T* __restrict
         const float xh = (v[j] - mu[j]) * is[j];
         g[j] = sc[j] * (dy - a[j] - xh * b[j]);
       }
-      if (addend != nullptr) {
+      if (!POOLED && addend != nullptr) {
         float ad[8];
         load8<T>(addend + off, ad);
 #pragma unroll
@@ -615,41 +657,48 @@ __global__ __launch_bounds__(PF_THREADS) void k_bn_bwd_apply(const T* __restrict
       const int c = (int)(e % C);
       const float v = load_one<T>(x + e);
       const float sc = scale_shift[c];
-      const float dy = load_one<T>(dq + e) * act_mask<ACT>(fmaf(sc, v, scale_shift[C + c]));
+      const float g = POOLED ? pooled_dq1<T>(dq, e / C, C, c, HW) : load_one<T>(dq + e);
+      const float dy = g * act_mask<ACT>(fmaf(sc, v, scale_shift[C + c]));
       const float xh = (v - mean_invstd[c]) * mean_invstd[C + c];
       float o = sc * (dy - dbeta[c] * inv_n - xh * (dgamma[c] * inv_n));
-      if (addend != nullptr) o += load_one<T>(addend + e);
+      if (!POOLED && addend != nullptr) o += load_one<T>(addend + e);
       store_one<T>(dx + e, o);
     }
   }
 }
 
+// HW as in launch_bn_bwd_stats; addend may be null (which counts as aligned) and is null with HW > 0
 template <typename T>
-static int launch_bn_bwd_apply(const T* dq, const T* x, T* dx, int64_t rows, int C, const float* ss,
+static int launch_bn_bwd_apply(const T* dq, const T* x, T* dx, int64_t rows, int C, int HW, const float* ss,
                                const float* mi, const float* dgamma, const float* dbeta, int act,
                                const T* addend, hipStream_t st) {
   const bool fast = bn_fast_ok(C) && pf_aligned16(x) && pf_aligned16(dq) && pf_aligned16(dx) && pf_aligned16(addend);
   const int grid = fast ? pf_grid_for(rows, (PF_THREADS / (C / 8)) * 2) : pf_grid_for(rows * C, PF_THREADS * 4);
-#define PF_BB(ACTV)                                                                                                    \
-  do {                                                                                                                 \
-    if (fast) k_bn_bwd_apply<T, ACTV, true><<<grid, PF_THREADS, 0, st>>>(dq, x, dx, rows, C, ss, mi, dgamma, dbeta, addend);    \
-    else k_bn_bwd_apply<T, ACTV, false><<<grid, PF_THREADS, 0, st>>>(dq, x, dx, rows, C, ss, mi, dgamma, dbeta, addend);        \
-  } while (0)
-  if (act == PF_ACT_RELU) PF_BB(PF_ACT_RELU);
-  else if (act == PF_ACT_RELU6) PF_BB(PF_ACT_RELU6);
-  else PF_BB(PF_ACT_NONE);
-#undef PF_BB
+  pf_with_act(act, [&](auto A) {
+    pf_with_bool(fast, [&](auto F) {
+      pf_with_bool(HW > 0, [&](auto P) {
+        k_bn_bwd_apply<T, decltype(A)::value, decltype(F)::value, decltype(P)::value><<<grid, PF_THREADS, 0, st>>>(dq, x, dx, rows, C, HW, ss, mi, dgamma, dbeta, addend);
+      });
+    });
+  });
   PF_LAUNCH_CHECK();
   return 0;
+}
+
+static int bn_bwd_apply_entry(const void* dq, const void* x, const void* addend, void* dx, int dtype, int64_t rows, int C,
+                              int HW, const float* scale_shift, const float* mean_invstd, const float* dgamma,
+                              const float* dbeta, int act, void* stream) {
+  return bn_with_dtype(dtype, [&](auto* t) {
+    using T = std::remove_pointer_t<decltype(t)>;
+    return launch_bn_bwd_apply<T>((const T*)dq, (const T*)x, (T*)dx, rows, C, HW, scale_shift, mean_invstd, dgamma, dbeta, act, (const T*)addend, (hipStream_t)stream);
+  });
 }
 
 extern "C" int pf_bn_bwd_apply_add(const void* dq, const void* x, const void* addend, void* dx, int dtype,
                                    int64_t rows, int C, const float* scale_shift, const float* mean_invstd,
                                    const float* dgamma, const float* dbeta, int act, void* stream) {
   if (rows <= 0 || C <= 0) return (int)hipErrorInvalidValue;
-  if (dtype == PF_F32) return launch_bn_bwd_apply<float>((const float*)dq, (const float*)x, (float*)dx, rows, C, scale_shift, mean_invstd, dgamma, dbeta, act, (const float*)addend, (hipStream_t)stream);
-  if (dtype == PF_BF16) return launch_bn_bwd_apply<bf16_t>((const bf16_t*)dq, (const bf16_t*)x, (bf16_t*)dx, rows, C, scale_shift, mean_invstd, dgamma, dbeta, act, (const bf16_t*)addend, (hipStream_t)stream);
-  return (int)hipErrorInvalidValue;
+  return bn_bwd_apply_entry(dq, x, addend, dx, dtype, rows, C, 0, scale_shift, mean_invstd, dgamma, dbeta, act, stream);
 }
 
 extern "C" int pf_bn_bwd_apply(const void* dq, const void* x, void* dx, int dtype, int64_t rows, int C,
@@ -658,190 +707,9 @@ extern "C" int pf_bn_bwd_apply(const void* dq, const void* x, void* dx, int dtyp
   return pf_bn_bwd_apply_add(dq, x, nullptr, dx, dtype, rows, C, scale_shift, mean_invstd, dgamma, dbeta, act, stream);
 }
 
-// ---------------------------------------------------------------------------------------------
-// backward of the network head: the two passes above with the dq load replaced
-// ---------------------------------------------------------------------------------------------
-// This BN's output feeds nothing but the spatial mean (pf_bn_act_quant_pool), so `g` is the [B][C] gradient of the POOLED tensor
-// and the value of row r = (b, p) is rebuilt on the fly, dq[(b, p)][c] = T(float(g[b][c]) * float32(1 / HW)) -- bit for bit what
-// autograd's cast / mean / cast chain writes into the expanded [B * HW][C] tensor on the device (aten divides a tensor by a host
-// scalar as a product with the rounded reciprocal), which is then never stored or read.  Everything else is
-// a copy of the plain kernel (kept apart so that those compile to the instructions they had): row order, splits and the partial
-// layout are the same, so every sum and dx come out bit-identical.  rows < 2^31: the row -> image division is a 32-bit one.
-template <typename T>
-__device__ __forceinline__ void pooled_dq8(const T* __restrict__ g, int64_t r, int C, int c0, int HW, float (&out)[8]) {
-  const float inv_hw = 1.0f / (float)HW;
-  load8<T>(g + (int64_t)((uint32_t)r / (uint32_t)HW) * C + c0, out);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) out[j] = round_to<T>(out[j] * inv_hw);
-}
-template <typename T>
-__device__ __forceinline__ float pooled_dq1(const T* __restrict__ g, int64_t r, int C, int c, int HW) {
-  return round_to<T>(load_one<T>(g + (int64_t)((uint32_t)r / (uint32_t)HW) * C + c) * (1.0f / (float)HW));
-}
-
-template <typename T, int ACT>
-__global__ __launch_bounds__(BN_BIG) void k_bn_bwd_stats_fast_pooled(const T* __restrict__ g, const T* __restrict__ x,
-                                                                     int64_t rows, int C,
-                                                                     const float* __restrict__ scale_shift,
-                                                                     const float* __restrict__ mean_invstd,
-                                                                     float* __restrict__ partial, int nslab, int nsplit,
-                                                                     int HW) {
-  __shared__ float lds[(BN_BIG / 64) * 2 * 64];
-  const int CG = bn_cg_of(C), slabC = CG * 8, RL = BN_BIG / CG;
-  const int slab = blockIdx.x % nslab, split = blockIdx.x / nslab;
-  const int cg = threadIdx.x % CG, rl = threadIdx.x / CG;
-  const int c0 = slab * slabC + cg * 8;
-  float sc[8], sh[8], mu[8], is[8], s1[8], s2[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int c = c0 + j;
-    sc[j] = scale_shift[c]; sh[j] = scale_shift[C + c];
-    mu[j] = mean_invstd[c]; is[j] = mean_invstd[C + c];
-    s1[j] = 0.f; s2[j] = 0.f;
-  }
-#pragma unroll 2
-  for (int64_t r = (int64_t)split * RL + rl; r < rows; r += (int64_t)nsplit * RL) {
-    float dq[8], v[8];
-    pooled_dq8<T>(g, r, C, c0, HW, dq);
-    load8<T>(x + r * C + c0, v);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float dy = dq[j] * act_mask<ACT>(fmaf(sc[j], v[j], sh[j]));
-      s1[j] += dy;
-      s2[j] = fmaf(dy, (v[j] - mu[j]) * is[j], s2[j]);
-    }
-  }
-  bn_wave_reduce8<0>(s1, CG); bn_wave_reduce8<0>(s2, CG);
-  bn_lds_put<0>(s1, 0, 2, CG, lds); bn_lds_put<0>(s2, 1, 2, CG, lds);
-  __syncthreads();
-  float* out = partial + (int64_t)split * 2 * C + slab * slabC;
-  bn_lds_finish<0>(0, 2, slabC, lds, out);
-  bn_lds_finish<0>(1, 2, slabC, lds, out + C);
-}
-
-template <typename T, int ACT>
-__global__ __launch_bounds__(PF_THREADS) void k_bn_bwd_stats_generic_pooled(const T* __restrict__ g, const T* __restrict__ x,
-                                                                            int64_t rows, int C,
-                                                                            const float* __restrict__ scale_shift,
-                                                                            const float* __restrict__ mean_invstd,
-                                                                            float* __restrict__ partial, int HW) {
-  const int c = blockIdx.x * PF_THREADS + threadIdx.x;
-  if (c >= C) return;
-  const float sc = scale_shift[c], sh = scale_shift[C + c], mu = mean_invstd[c], is = mean_invstd[C + c];
-  float s1 = 0.f, s2 = 0.f;
-  for (int64_t r = blockIdx.y; r < rows; r += gridDim.y) {
-    const float v = load_one<T>(x + r * C + c);
-    const float dy = pooled_dq1<T>(g, r, C, c, HW) * act_mask<ACT>(fmaf(sc, v, sh));
-    s1 += dy;
-    s2 = fmaf(dy, (v - mu) * is, s2);
-  }
-  float* out = partial + (int64_t)blockIdx.y * 2 * C;
-  out[c] = s1; out[C + c] = s2;
-}
-
-static inline bool bn_pooled_ok(int64_t rows, int HW) {
-  return HW > 0 && rows > 0 && rows < ((int64_t)1 << 31) && rows % HW == 0;
-}
-
-template <typename T>
-static int launch_bn_bwd_stats_pooled(const T* g, const T* x, int64_t rows, int C, int HW, const float* ss,
-                                      const float* mi, int act, float* partial, int n_blocks, hipStream_t st) {
-  const bool fast = bn_fast_ok(C) && pf_aligned16(x) && pf_aligned16(g);
-  const int CG = (C / 8) < 8 ? (C / 8) : 8;
-  const int nslab = fast ? C / (CG * 8) : 1;
-  dim3 ggrid((C + PF_THREADS - 1) / PF_THREADS, n_blocks);
-#define PF_BS(ACTV)                                                                                                       \
-  do {                                                                                                                    \
-    if (fast) k_bn_bwd_stats_fast_pooled<T, ACTV><<<nslab * n_blocks, BN_BIG, 0, st>>>(g, x, rows, C, ss, mi, partial, nslab, n_blocks, HW);  \
-    else k_bn_bwd_stats_generic_pooled<T, ACTV><<<ggrid, PF_THREADS, 0, st>>>(g, x, rows, C, ss, mi, partial, HW);        \
-  } while (0)
-  if (act == PF_ACT_RELU) PF_BS(PF_ACT_RELU);
-  else if (act == PF_ACT_RELU6) PF_BS(PF_ACT_RELU6);
-  else PF_BS(PF_ACT_NONE);
-#undef PF_BS
-  PF_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int pf_bn_bwd_stats_pooled(const void* g, const void* x, int dtype, int64_t rows, int C, int HW,
-                                      const float* scale_shift, const float* mean_invstd, int act,
-                                      float* partial, int n_blocks, void* stream) {
-  if (C <= 0 || n_blocks <= 0 || !bn_pooled_ok(rows, HW)) return (int)hipErrorInvalidValue;
-  if (dtype == PF_F32) return launch_bn_bwd_stats_pooled<float>((const float*)g, (const float*)x, rows, C, HW, scale_shift, mean_invstd, act, partial, n_blocks, (hipStream_t)stream);
-  if (dtype == PF_BF16) return launch_bn_bwd_stats_pooled<bf16_t>((const bf16_t*)g, (const bf16_t*)x, rows, C, HW, scale_shift, mean_invstd, act, partial, n_blocks, (hipStream_t)stream);
-  return (int)hipErrorInvalidValue;
-}
-
-template <typename T, int ACT, bool FAST>
-__global__ __launch_bounds__(PF_THREADS) void k_bn_bwd_apply_pooled(const T* __restrict__ g, const T* __restrict__ x,
-                                                                    T* __restrict__ dx, int64_t rows, int C,
-                                                                    const float* __restrict__ scale_shift,
-                                                                    const float* __restrict__ mean_invstd,
-                                                                    const float* __restrict__ dgamma,
-                                                                    const float* __restrict__ dbeta, int HW) {
-  const float inv_n = 1.0f / (float)rows;
-  if (FAST) {
-    const int G = C >> 3, RPS = PF_THREADS / G;
-    const int cg = threadIdx.x % G, rsub = threadIdx.x / G;
-    float sc[8], sh[8], mu[8], is[8], a[8], b[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int c = (cg << 3) + j;
-      sc[j] = scale_shift[c]; sh[j] = scale_shift[C + c];
-      mu[j] = mean_invstd[c]; is[j] = mean_invstd[C + c];
-      a[j] = dbeta[c] * inv_n; b[j] = dgamma[c] * inv_n;
-    }
-#pragma unroll 2
-    for (int64_t r = (int64_t)blockIdx.x * RPS + rsub; r < rows; r += (int64_t)gridDim.x * RPS) {
-      float dq[8], v[8];
-      const int64_t off = r * C + (cg << 3);
-      pooled_dq8<T>(g, r, C, cg << 3, HW, dq);
-      load8<T>(x + off, v);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float dy = dq[j] * act_mask<ACT>(fmaf(sc[j], v[j], sh[j]));
-        const float xh = (v[j] - mu[j]) * is[j];
-        dq[j] = sc[j] * (dy - a[j] - xh * b[j]);
-      }
-      store8<T>(dx + off, dq);
-    }
-  } else {
-    const int64_t n = rows * C;
-    for (int64_t e = (int64_t)blockIdx.x * PF_THREADS + threadIdx.x; e < n;
-         e += (int64_t)gridDim.x * PF_THREADS) {
-      const int c = (int)(e % C);
-      const float v = load_one<T>(x + e);
-      const float sc = scale_shift[c];
-      const float dy = pooled_dq1<T>(g, e / C, C, c, HW) * act_mask<ACT>(fmaf(sc, v, scale_shift[C + c]));
-      const float xh = (v - mean_invstd[c]) * mean_invstd[C + c];
-      store_one<T>(dx + e, sc * (dy - dbeta[c] * inv_n - xh * (dgamma[c] * inv_n)));
-    }
-  }
-}
-
-template <typename T>
-static int launch_bn_bwd_apply_pooled(const T* g, const T* x, T* dx, int64_t rows, int C, int HW, const float* ss,
-                                      const float* mi, const float* dgamma, const float* dbeta, int act, hipStream_t st) {
-  const bool fast = bn_fast_ok(C) && pf_aligned16(x) && pf_aligned16(g) && pf_aligned16(dx);
-  const int grid = fast ? pf_grid_for(rows, (PF_THREADS / (C / 8)) * 2) : pf_grid_for(rows * C, PF_THREADS * 4);
-#define PF_BB(ACTV)                                                                                                    \
-  do {                                                                                                                 \
-    if (fast) k_bn_bwd_apply_pooled<T, ACTV, true><<<grid, PF_THREADS, 0, st>>>(g, x, dx, rows, C, ss, mi, dgamma, dbeta, HW);   \
-    else k_bn_bwd_apply_pooled<T, ACTV, false><<<grid, PF_THREADS, 0, st>>>(g, x, dx, rows, C, ss, mi, dgamma, dbeta, HW);       \
-  } while (0)
-  if (act == PF_ACT_RELU) PF_BB(PF_ACT_RELU);
-  else if (act == PF_ACT_RELU6) PF_BB(PF_ACT_RELU6);
-  else PF_BB(PF_ACT_NONE);
-#undef PF_BB
-  PF_LAUNCH_CHECK();
-  return 0;
-}
-
 extern "C" int pf_bn_bwd_apply_pooled(const void* g, const void* x, void* dx, int dtype, int64_t rows, int C, int HW,
                                       const float* scale_shift, const float* mean_invstd, const float* dgamma,
                                       const float* dbeta, int act, void* stream) {
   if (C <= 0 || !bn_pooled_ok(rows, HW)) return (int)hipErrorInvalidValue;
-  if (dtype == PF_F32) return launch_bn_bwd_apply_pooled<float>((const float*)g, (const float*)x, (float*)dx, rows, C, HW, scale_shift, mean_invstd, dgamma, dbeta, act, (hipStream_t)stream);
-  if (dtype == PF_BF16) return launch_bn_bwd_apply_pooled<bf16_t>((const bf16_t*)g, (const bf16_t*)x, (bf16_t*)dx, rows, C, HW, scale_shift, mean_invstd, dgamma, dbeta, act, (hipStream_t)stream);
-  return (int)hipErrorInvalidValue;
+  return bn_bwd_apply_entry(g, x, nullptr, dx, dtype, rows, C, HW, scale_shift, mean_invstd, dgamma, dbeta, act, stream);
 }

@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "../../include/pocketflow_hip.h"
 
 #define PF_WAVE 64
@@ -205,6 +206,19 @@ __device__ __forceinline__ float block_sum(float v, float* lds /*[4]*/) {
   v = (lds[0] + lds[1]) + (lds[2] + lds[3]);
   __syncthreads();
   return v;
+}
+
+// ---- host: a runtime choice -> a template argument of the launch ------------------------------
+// f(tag) is called with a std::integral_constant; the launch site reads decltype(tag)::value.  An unknown activation code is
+// PF_ACT_NONE, as in apply_act / act_mask.
+template <typename F> static inline void pf_with_act(int act, F&& f) {
+  if (act == PF_ACT_RELU) f(std::integral_constant<int, PF_ACT_RELU>{});
+  else if (act == PF_ACT_RELU6) f(std::integral_constant<int, PF_ACT_RELU6>{});
+  else f(std::integral_constant<int, PF_ACT_NONE>{});
+}
+template <typename F> static inline void pf_with_bool(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
 }
 
 static inline int pf_grid_for(int64_t n, int per_block) {

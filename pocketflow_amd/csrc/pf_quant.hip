@@ -185,15 +185,11 @@ template <typename T>
 static int launch_act_grad(const T* g, const T* u, T* dx, int64_t n, int act, hipStream_t st) {
   const int grid = pf_grid_for(n, PF_THREADS * 16);
   const bool vec = pf_aligned16(g) && pf_aligned16(u) && pf_aligned16(dx);
-#define PF_AG(ACTV)                                                                          \
-  do {                                                                                       \
-    if (vec) k_act_grad<T, ACTV, true><<<grid, PF_THREADS, 0, st>>>(g, u, dx, n);            \
-    else k_act_grad<T, ACTV, false><<<grid, PF_THREADS, 0, st>>>(g, u, dx, n);               \
-  } while (0)
-  if (act == PF_ACT_RELU) PF_AG(PF_ACT_RELU);
-  else if (act == PF_ACT_RELU6) PF_AG(PF_ACT_RELU6);
-  else PF_AG(PF_ACT_NONE);
-#undef PF_AG
+  pf_with_act(act, [&](auto A) {
+    pf_with_bool(vec, [&](auto V) {
+      k_act_grad<T, decltype(A)::value, decltype(V)::value><<<grid, PF_THREADS, 0, st>>>(g, u, dx, n);
+    });
+  });
   PF_LAUNCH_CHECK();
   return 0;
 }

@@ -604,14 +604,9 @@ class _BnActQuant(torch.autograd.Function):
     x = _nhwc(x)
     C = gamma.numel()
     rows = x.numel() // C
-    scale_shift = torch.empty((2, C), dtype=torch.float32, device=x.device)
-    mean_invstd = torch.empty((2, C), dtype=torch.float32, device=x.device)
     quantize = bits is not None
     nbytes = float(x.numel() * x.element_size())
-    partial, nblk, piv = _bn_statistics(x, rows, C, graph, stats)
-    hip.bn_finalize(partial, nblk, rows, C, piv, gamma, beta, layer.moving_mean.tensor, layer.moving_var.tensor,
-                    layer.momentum, layer.eps, training, layer.act, scale_shift, mean_invstd,
-                    slot if quantize else None)
+    scale_shift, mean_invstd = _bn_scale_shift(x, gamma, beta, layer, graph, training, slot if quantize else None, stats)
     q = torch.empty_like(x)
     with region('bn_act_quant_apply', 2 * nbytes):   # 1 read of x + 1 write of q
       hip.bn_act_quant_apply(x, q, rows, C, scale_shift, layer.act, slot, bits if quantize else 8, quantize)
@@ -648,11 +643,7 @@ class _BnEvalAct(torch.autograd.Function):
     x = _nhwc(x)
     C = gamma.numel()
     rows = x.numel() // C
-    ss = torch.empty((2, C), dtype=torch.float32, device=x.device)
-    hip.bn_eval_scale_shift(gamma.detach(), beta.detach(), layer.moving_mean.tensor, layer.moving_var.tensor,
-                            layer.eps, ss)
-    mi = torch.stack([layer.moving_mean.tensor.float(),
-                      torch.rsqrt(layer.moving_var.tensor.float() + layer.eps)]).contiguous()
+    ss, mi = _bn_scale_shift(x, gamma, beta, layer, graph, False, None)
     q = torch.empty_like(x)
     hip.bn_act_quant_apply(x, q, rows, C, ss, layer.act, None, 8, False)
     ctx.save_for_backward(x, ss, mi)
@@ -682,17 +673,7 @@ class _BnActPool(torch.autograd.Function):
     rows = x.numel() // C
     hw = rows // x.shape[0]
     quantize = bits is not None
-    scale_shift = torch.empty((2, C), dtype=torch.float32, device=x.device)
-    if training:
-      mean_invstd = torch.empty((2, C), dtype=torch.float32, device=x.device)
-      partial, nblk, piv = _bn_statistics(x, rows, C, graph, stats)
-      hip.bn_finalize(partial, nblk, rows, C, piv, gamma, beta, layer.moving_mean.tensor, layer.moving_var.tensor,
-                      layer.momentum, layer.eps, True, layer.act, scale_shift, mean_invstd, slot if quantize else None)
-    else:
-      hip.bn_eval_scale_shift(gamma.detach(), beta.detach(), layer.moving_mean.tensor, layer.moving_var.tensor,
-                              layer.eps, scale_shift)
-      mean_invstd = torch.stack([layer.moving_mean.tensor.float(),
-                                 torch.rsqrt(layer.moving_var.tensor.float() + layer.eps)]).contiguous()
+    scale_shift, mean_invstd = _bn_scale_shift(x, gamma, beta, layer, graph, training, slot if quantize else None, stats)
     pooled = torch.empty((x.shape[0], C), dtype=x.dtype, device=x.device)
     with region('bn_act_quant_pool', float(x.numel() * x.element_size())):   # 1 read of x
       hip.bn_act_quant_pool(x, pooled, rows, C, hw, scale_shift, layer.act, slot, bits if quantize else 8, quantize)
@@ -818,6 +799,26 @@ def _bn_statistics(x, rows, C, graph, st=None):
   return partial, nblk, x
 
 
+def _bn_scale_shift(x, gamma, beta, layer, graph, training, slot, stats=None):
+  """(scale_shift, mean_invstd) of `layer` applied to x, each [2][C] float32.  `training`: batch statistics (`stats` as in
+  _bn_statistics) finalized on the device, which also updates the moving statistics and, with a `slot`, leaves the activated
+  tensor's min / max there.  Otherwise inference mode with gradients: the moving statistics, gamma / beta as constants."""
+  C = gamma.numel()
+  scale_shift = torch.empty((2, C), dtype=torch.float32, device=x.device)
+  if training:
+    rows = x.numel() // C
+    mean_invstd = torch.empty((2, C), dtype=torch.float32, device=x.device)
+    partial, nblk, piv = _bn_statistics(x, rows, C, graph, stats)
+    hip.bn_finalize(partial, nblk, rows, C, piv, gamma, beta, layer.moving_mean.tensor, layer.moving_var.tensor,
+                    layer.momentum, layer.eps, True, layer.act, scale_shift, mean_invstd, slot)
+  else:
+    hip.bn_eval_scale_shift(gamma.detach(), beta.detach(), layer.moving_mean.tensor, layer.moving_var.tensor,
+                            layer.eps, scale_shift)
+    mean_invstd = torch.stack([layer.moving_mean.tensor.float(),
+                               torch.rsqrt(layer.moving_var.tensor.float() + layer.eps)]).contiguous()
+  return scale_shift, mean_invstd
+
+
 class _BnLazy(torch.autograd.Function):
   """BN statistics + finalize only; returns an alias of x that stands for q (see LazyAct)."""
 
@@ -825,12 +826,7 @@ class _BnLazy(torch.autograd.Function):
   def forward(ctx, x, gamma, beta, layer, graph, slot, bits, box, stats):
     C = gamma.numel()
     rows = x.numel() // C
-    partial, nblk, piv = _bn_statistics(x, rows, C, graph, stats)
-    scale_shift = torch.empty((2, C), dtype=torch.float32, device=x.device)
-    mean_invstd = torch.empty((2, C), dtype=torch.float32, device=x.device)
-    hip.bn_finalize(partial, nblk, rows, C, piv, gamma, beta, layer.moving_mean.tensor, layer.moving_var.tensor,
-                    layer.momentum, layer.eps, True, layer.act, scale_shift, mean_invstd,
-                    slot if bits is not None else None)
+    scale_shift, mean_invstd = _bn_scale_shift(x, gamma, beta, layer, graph, True, slot if bits is not None else None, stats)
     ctx.save_for_backward(x, scale_shift, mean_invstd)
     ctx.meta = (layer.act, graph, rows, C)
     ctx.params = (gamma, beta)
@@ -888,17 +884,22 @@ def _bn_backward(dq, x, scale_shift, mean_invstd, act, graph, rows, C, addend=No
     if addend.dtype != x.dtype:
       addend = addend.to(x.dtype)
   nbytes = float(x.numel() * x.element_size())
+  if pool_hw is not None:
+    # the pooled passes read x and the small pooled gradient; the apply pass also writes dx
+    stats_pass = ('bn_bwd_stats_pooled', nbytes, hip.bn_bwd_stats_pooled, (pool_hw,))
+    apply_pass = ('bn_bwd_apply_pooled', 2 * nbytes, hip.bn_bwd_apply_pooled, (pool_hw,), ())
+  else:
+    # the plain passes read dq and x; the apply pass also reads the addend and writes dx
+    stats_pass = ('bn_bwd_stats', 2 * nbytes, hip.bn_bwd_stats, ())
+    apply_pass = ('bn_bwd_apply', (4 if addend is not None else 3) * nbytes, hip.bn_bwd_apply, (), (addend,))
   if pre is not None:
     partial, nblk = pre
   else:
     nblk = _bn_blocks(rows, C)
     partial = graph.scratch(nblk * 2 * C)
-    if pool_hw is not None:
-      with region('bn_bwd_stats_pooled', nbytes):  # reads x (and the small pooled gradient)
-        hip.bn_bwd_stats_pooled(dq, x, rows, C, pool_hw, scale_shift, mean_invstd, act, partial, nblk)
-    else:
-      with region('bn_bwd_stats', 2 * nbytes):     # reads dq and x
-        hip.bn_bwd_stats(dq, x, rows, C, scale_shift, mean_invstd, act, partial, nblk)
+    name, traffic, launch, hw = stats_pass
+    with region(name, traffic):
+      launch(dq, x, rows, C, *hw, scale_shift, mean_invstd, act, partial, nblk)
   gview = _grad_view(params[0], C) if params is not None else None
   bview = _grad_view(params[1], C) if params is not None else None
   direct = gview is not None and bview is not None
@@ -907,14 +908,10 @@ def _bn_backward(dq, x, scale_shift, mean_invstd, act, graph, rows, C, addend=No
   hip.bn_bwd_finalize(partial, nblk, C, dgamma, dbeta)
   dx = torch.empty_like(x)
   zero = graph.zero_row(C)[:C] if frozen else None
-  if pool_hw is not None:
-    with region('bn_bwd_apply_pooled', 2 * nbytes):                         # reads x, writes dx
-      hip.bn_bwd_apply_pooled(dq, x, dx, rows, C, pool_hw, scale_shift, mean_invstd, zero if frozen else dgamma,
-                              zero if frozen else dbeta, act)
-    return (dx, None, None) if direct else (dx, dgamma, dbeta)
-  with region('bn_bwd_apply', (4 if addend is not None else 3) * nbytes):   # reads dq, x [, addend], writes dx
-    hip.bn_bwd_apply(dq, x, dx, rows, C, scale_shift, mean_invstd, zero if frozen else dgamma,
-                     zero if frozen else dbeta, act, addend)
+  name, traffic, launch, hw, tail = apply_pass
+  with region(name, traffic):
+    launch(dq, x, dx, rows, C, *hw, scale_shift, mean_invstd, zero if frozen else dgamma, zero if frozen else dbeta, act,
+           *tail)
   return (dx, None, None) if direct else (dx, dgamma, dbeta)
 
 
@@ -1935,15 +1932,8 @@ class BatchNormAct:
     if bits is None:
       hip.bn_act_quant_pool(x, pooled, rows, C, rows // x.shape[0], self._eval_scale_shift(x), self.act, None, 8, False)
       return pooled
-    with torch.no_grad():                          # eval graph of a quantising learner, as _inference
-      nblk = _bn_blocks(rows, C)
-      partial = g.scratch(nblk * 4 * C)
-      ss = torch.empty((2, C), dtype=torch.float32, device=x.device)
-      mi = torch.empty((2, C), dtype=torch.float32, device=x.device)
-      hip.bn_stats(x, rows, C, partial, nblk)
-      hip.bn_finalize(partial, nblk, rows, C, x, self.gamma.tensor, self.beta.tensor, self.moving_mean.tensor,
-                      self.moving_var.tensor, self.momentum, self.eps, g.training, self.act, ss, mi, slot)
-      hip.bn_act_quant_pool(x, pooled, rows, C, rows // x.shape[0], ss, self.act, slot, bits, True)
+    hip.bn_act_quant_pool(x, pooled, rows, C, rows // x.shape[0], self._calibrated_scale_shift(x, slot), self.act, slot, bits,
+                          True)
     return pooled
 
   def _inference(self, x, slot, bits, lazy):
@@ -1957,17 +1947,23 @@ class BatchNormAct:
       # inference BN + act only: y = act(scale*x + shift); the teacher's (frozen) scale/shift is cached
       hip.bn_act_quant_apply(x, q, rows, C, self._eval_scale_shift(x), self.act, None, 8, False)
       return q
-    # eval graph of a quantising learner: moving statistics + freshly calibrated activation range
+    hip.bn_act_quant_apply(x, q, rows, C, self._calibrated_scale_shift(x, slot), self.act, slot, bits, True)
+    return q
+
+  def _calibrated_scale_shift(self, x, slot):
+    """scale / shift of the eval graph of a quantising learner: the moving statistics, plus one statistics pass over x that
+    leaves the freshly calibrated activation range in `slot`."""
+    g, C = self.graph, self.C
+    rows = x.numel() // C
     with torch.no_grad():
       nblk = _bn_blocks(rows, C)
-      partial = self.graph.scratch(nblk * 4 * C)
+      partial = g.scratch(nblk * 4 * C)
       ss = torch.empty((2, C), dtype=torch.float32, device=x.device)
       mi = torch.empty((2, C), dtype=torch.float32, device=x.device)
       hip.bn_stats(x, rows, C, partial, nblk)
       hip.bn_finalize(partial, nblk, rows, C, x, self.gamma.tensor, self.beta.tensor, self.moving_mean.tensor,
-                      self.moving_var.tensor, self.momentum, self.eps, self.graph.training, self.act, ss, mi, slot)
-      hip.bn_act_quant_apply(x, q, rows, C, ss, self.act, slot, bits, True)
-    return q
+                      self.moving_var.tensor, self.momentum, self.eps, g.training, self.act, ss, mi, slot)
+    return ss
 
   def _eval_scale_shift(self, x):
     """Inference BN folded to scale/shift; the teacher's (frozen) pair is cached."""

@@ -115,6 +115,38 @@ def test_pooled_backward_is_bit_identical_to_the_expanded_gradient(dt, C):
           assert torch.equal(a, b), (what, name)
 
 
+@pytest.mark.parametrize('C', CHANNELS)
+def test_backward_apply_adds_the_shortcut_gradient(C):
+  """The addend of pf_bn_bwd_apply_add, which the dense and the pooled apply pass share a kernel with.
+  float32: dx with the addend == dx without it + addend in torch, bit for bit (the kernel adds the same two float32 values).
+  bf16: dx == the float32 kernel's dx on the same inputs upcast to float32, rounded to bf16, bit for bit: bf16 loads are exact,
+  the arithmetic is the same float32 expression (the library is built without contraction) and both stores round to nearest
+  even."""
+  from pocketflow_amd import hip
+  for rows in (12, 70):
+    for ai, act in enumerate(ACTS):
+      gen = torch.Generator(device='cpu').manual_seed(5000 + 10 * rows + ai)
+      x = (torch.randn(rows, C, generator=gen) * 1.5).to(torch.bfloat16)
+      dq = torch.randn(rows, C, generator=gen).to(torch.bfloat16)
+      a = torch.randn(rows, C, generator=gen).to(torch.bfloat16)
+      ss = torch.stack([0.5 + torch.rand(C, generator=gen), 0.5 * torch.randn(C, generator=gen)]).float().cuda().contiguous()
+      mi = torch.stack([0.3 * torch.randn(C, generator=gen), 0.5 + torch.rand(C, generator=gen)]).float().cuda().contiguous()
+      dgamma = torch.randn(C, generator=gen).cuda()
+      dbeta = torch.randn(C, generator=gen).cuda()
+      what = (C, rows, act)
+
+      def run(dtype, addend):
+        dx = torch.full((rows, C), float('nan'), dtype=dtype, device='cuda')
+        hip.bn_bwd_apply(dq.to(dtype).cuda(), x.to(dtype).cuda(), dx, rows, C, ss, mi, dgamma, dbeta, act, addend)
+        assert not bool(torch.isnan(dx.float()).any()), (what, dtype)
+        return dx
+
+      a32 = a.float().cuda()
+      with_addend = run(torch.float32, a32)
+      assert torch.equal(with_addend, run(torch.float32, None) + a32), what
+      assert torch.equal(run(torch.bfloat16, a.cuda()), with_addend.to(torch.bfloat16)), what
+
+
 def _loss_inputs(Bn, C, dtype, seed):
   gen = torch.Generator(device='cpu').manual_seed(seed)
   z = (2.0 * torch.randn(Bn, C, generator=gen)).to(dtype)
