@@ -475,6 +475,29 @@ int pf_conv_gather_fwd(const void* x, const void* w, const int32_t* gather, cons
                        const float* scale_shift, int act, void* y, int dtype, int imgs, int H, int W, int C, int Ck, int N, int R,
                        int S, int stride, int pad_h, int pad_w, int Ho, int Wo, void* stream);
 
+/* ---- int8 inference of a uniformly quantised convolution (pf_conv_i8.hip) -----------------------------------------------------------
+ * The reference quantises weights and activations to unsigned codes on affine grids (learners/uniform_quantization/utils.py:163-245:
+ * x_q = alpha * round((x - beta) / alpha * k) / k + beta, k = 2^bits - 1) and then multiplies the DECODED floats
+ * (utils.py:51-79 insert the quantisers in front of every Conv2D / MatMul); its integer deployment goes through TF-Lite
+ * (tools/conversion/export_quant_tflite_model.py:196-249).  These entries multiply the codes themselves on the i8 matrix cores:
+ *   y[m][n] = (alpha_a/k_a)(alpha_w[n]/k_w) P + (alpha_a/k_a) beta_w[n] Sc + beta_a ((alpha_w[n]/k_w) Dv + beta_w[n] V),
+ *   P = sum_window c d and Sc = sum_window c exact in integers (padding taps hold code 0), Dv = the sum of d[n] over the taps inside the
+ *   image, V = their count * C; the float32 terms are added in this order, then the residual, then one rounding to the output type.
+ * pf_bn_act_quant_codes: the twin of pf_bn_act_quant_apply that stores code = rint((act(scale * x + shift) - beta) / alpha * k) as
+ *   one byte per element (NHWC, bits <= 8) -- the same float32 arithmetic up to that rounding -- and the decoded (alpha, beta) of the
+ *   slot to alpha_beta[2].
+ * pf_conv_i8_fwd: x uint8 codes [imgs][H][W][C]; w signed bytes d - 128 as [N][Kp], Kp = R*S*C rounded up to 64, KRSC order, zero beyond
+ *   R*S*C; act_alpha_beta the pair the producer wrote; w_scale_beta [N][2] = (alpha_w/k_w, beta_w); w_tsum [N] = sum over the window of
+ *   (d - 128); w_tapsum [N][R*S] = per-tap sums of d (read only when beta_a != 0); res / y [imgs][Ho][Wo][N] of out_dtype (res may be
+ *   NULL); symmetric pads.  All pointers 16-byte aligned.  Deterministic: no atomics, fixed summation order.
+ * pf_conv_i8_supported (host): C % 16 == 0, N % 8 == 0, stride 1 or 2, R*S*C * 2^14 < 2^31 (the int32 accumulator).            */
+int pf_bn_act_quant_codes(const void* x, uint8_t* codes, int dtype, int64_t rows, int C, const float* scale_shift, int act,
+                          const uint32_t* slot, int bits, float* alpha_beta, void* stream);
+int pf_conv_i8_supported(int C, int N, int R, int S, int stride);
+int pf_conv_i8_fwd(const uint8_t* x, const int8_t* w, const float* act_alpha_beta, int act_bits, const float* w_scale_beta,
+                   const int32_t* w_tsum, const int32_t* w_tapsum, const void* res, void* y, int out_dtype, int imgs, int H, int W,
+                   int C, int N, int R, int S, int stride, int pad_h, int pad_w, int Ho, int Wo, void* stream);
+
 /* ---- R x S convolutions with few input channels (ResNet-20 @ CIFAR-10: resnet_model.py:156-199 with 16 / 32 filters) --------------
  * bf16, C % 8 == 0.  pf_im2col gathers Xcol[imgs*Ho*Wo][R*S*C] (taps outside the image: zeros) so that the convolution and its two
  * gradients are 1x1 products on pf_conv1x1_fwd / pf_conv1x1_wrw over Xcol and the [N][R*S*C] view of the KRSC kernel; pf_col2im is

@@ -384,6 +384,12 @@ class Graph:
     self._names: Dict[str, int] = {}
     self.reinflated: List[str] = []            # shrunk kernels a loader scattered back to full shape (gather_pays)
     self.kernel_params = self.kernel_params_kept = self.nb_gathered = 0   # set by inference.load_shrunk
+    # int8 inference (inference.load_int8): quantising BatchNormAct layers whose consumers are all Conv2D hand out CodesAct, and the
+    # Conv2D layers the loader packed multiply the codes on pf_conv_i8_fwd; `int8_ran` collects the layers that did
+    self.int8 = False
+    self.nb_int8 = 0
+    self.int8_ran: set = set()
+    self.conv_layers: List = []                # every Conv2D of the graph, in creation order (the loader finds a kernel's layer here)
 
   # -- naming like tf.layers (conv2d, conv2d_1, ...) ---------------------------------------------
   def unique_name(self, base: str) -> str:
@@ -770,6 +776,28 @@ class LazyAct(object):
 
 def materialize(x):
   return x.materialize() if isinstance(x, LazyAct) else x
+
+
+class CodesAct(LazyAct):
+  """The output of a quantising inference-mode BatchNormAct (bits <= 8) on a graph with `int8` set: a LazyAct that can also hand out
+  the activation as uint8 CODES plus the decoded (alpha, beta) pair on the device (one pf_bn_act_quant_codes launch, cached) -- what a
+  packed Conv2D multiplies on the i8 matrix cores.  `materialize()` is unchanged: the fake-quantised float tensor of the apply pass,
+  for every consumer that stays on the float kernels.  Inference only: there is no autograd node behind it."""
+
+  def __init__(self, x, scale_shift, act, slot, bits, rows, C):
+    super(CodesAct, self).__init__(x, scale_shift, act, slot, bits, rows, C)
+    self._codes = None
+    self.alpha_beta = None
+
+  def codes(self):
+    """(codes, alpha_beta): uint8 in x's NHWC memory order, float32[2] on the device (never read by the host)."""
+    if self._codes is None:
+      x = self.x
+      self._codes = torch.empty(x.shape, dtype=torch.uint8, device=x.device, memory_format=torch.channels_last)
+      self.alpha_beta = torch.empty(2, dtype=torch.float32, device=x.device)
+      with region('bn_act_quant_codes', float(x.numel() * (x.element_size() + 1))):
+        hip.bn_act_quant_codes(x, self._codes, self.rows, self.C, self.scale_shift, self.act, self.slot, self.bits, self.alpha_beta)
+    return self._codes, self.alpha_beta
 
 
 class _Materialize(torch.autograd.Function):
@@ -1555,6 +1583,21 @@ def gather_pays(k: int, cin: int, kept: int, cout: int, dtype) -> bool:
   return False
 
 
+def int8_pays(k: int, cin: int, cout: int, stride: int, dtype) -> bool:
+  """Should a loader send an eligible k x k convolution to pf_conv_i8_fwd (True) or leave it on the float kernels (False)?
+
+  profiles/int8_conv_layers.txt (every eligible ResNet-50 convolution and every MobileNet-v1 pointwise convolution at B = 256 / 224 x
+  224, bf16 output, the launches each route makes: fake-quant apply pass + bf16 kernel against codes pass + i8 kernel): the int8 route
+  loses on every row but one, float / int8 0.40 - 0.99 (ResNet-50 summed: 6.3 ms against 9.9 ms; MobileNet 1.16 against 2.01 ms).  The
+  codes pass is the cheaper producer (0.7 x the apply pass: it writes one byte per element), but the plain LDS-staged i8 kernel runs
+  at 0.07 - 0.40 of its bound where the bf16 kernels with their LDS-DMA fills and double buffering reach 0.23 - 0.58.  The one row it
+  wins is the 1 x 1, 256 -> 64 convolution at 56 x 56 (ResNet-50 stage 1 conv1: 314 against 289 us, 1.09), where the producer pass over
+  the 256-channel input dominates both routes; with those two layers on int8 the whole ResNet-50 pass takes 8.106 against 8.154 ms
+  (profiles/int8_inference_time.txt; every eligible layer on int8: 12.40 ms).  float32 output has not been timed.  (inference.load_int8(int8='on') still runs every
+  eligible layer on the kernel.)"""
+  return dtype == torch.bfloat16 and k == 1 and stride == 1 and cin == 256 and cout == 64
+
+
 class Conv2D:
   """tf.layers.conv2d / slim.conv2d: NHWC, kernel HWIO (stored KRSC), padding 'SAME' | 'VALID'."""
 
@@ -1568,6 +1611,8 @@ class Conv2D:
     self.bias = (graph.store.add(name + '/' + bias_name, (cout,), 'bias', True, l2, constant_init((cout,), 0.0))
                  if use_bias else None)
     self.op = graph.add_matmul_op('Conv2D', name + '/Conv2D', self.kernel)
+    self.int8 = None                             # the packed layer on the device (inference.load_int8): dict of int8.pack_layer's tables
+    graph.conv_layers.append(self)
 
   def __call__(self, x, residual: Optional[torch.Tensor] = None, want_stats: bool = False, out_bn=None) -> torch.Tensor:
     """`residual`: tensor added to the output (the block's shortcut); `want_stats`: the consumer is a
@@ -1581,6 +1626,13 @@ class Conv2D:
       return _tapped(self, materialize(x), residual)
     if self.kernel.gather_host is not None:      # a physically shrunk layer (Graph.apply_gathers): inference on pf_conv_gather.hip
       return self._call_gathered(x, residual, out_bn)
+    if self.int8 is not None and torch.is_grad_enabled() and (w.requires_grad or (x.x if isinstance(x, LazyAct) else x).requires_grad):
+      raise RuntimeError('%s: a convolution packed for int8 runs in inference only: call it under torch.no_grad() on a graph '
+                         'finalised with requires_grad=False' % self.kernel.name)
+    if isinstance(x, CodesAct):
+      if self.int8 is not None and self._int8_geometry(x.x) is not None:
+        return self._call_int8(x, residual)
+      x = x.materialize()                        # every other consumer: the fake-quantised tensor of the apply pass, as without int8
     if fused_conv1x1_ok(x, self):                # 1x1 on pf_conv.hip: the producer BN's normalise / act / fake-quant in the prologue
       lazy = x if isinstance(x, LazyAct) else None
       if lazy is not None:
@@ -1669,6 +1721,32 @@ class Conv2D:
                           bias=bias, residual=res, scale_shift=ss, act=out_bn.act if out_bn is not None else None)
     if out_bn is not None:
       y._pf_bn_done = out_bn
+    return y
+
+  def _int8_geometry(self, x):
+    """(pad_h, pad_w, Ho, Wo) where pf_conv_i8_fwd takes this layer on the input x, else None: symmetric pads only (it has no padded
+    copy to fall back on), no bias, a 4-D device tensor."""
+    if self.bias is not None or x.dim() != 4 or not x.is_cuda or x.shape[1] != self.kernel.ref_shape[2]:
+      return None
+    ph, pw, (Ho, Wo) = self._geometry(x)
+    if ph[0] != ph[1] or pw[0] != pw[1]:
+      return None
+    return ph[0], pw[0], Ho, Wo
+
+  def _call_int8(self, x: 'CodesAct', residual) -> torch.Tensor:
+    """The packed layer on the i8 matrix cores: the producer's codes times the signed weights, scales and offsets in the epilogue
+    (pocketflow_amd/int8.py states the formula), the residual added before the one rounding to the compute dtype."""
+    p = self.int8
+    pad_h, pad_w, Ho, Wo = self._int8_geometry(x.x)
+    codes, ab = x.codes()
+    B, C, H, Wd = codes.shape
+    N = self.kernel.ref_shape[3]
+    y = torch.empty((B, N, Ho, Wo), dtype=x.dtype, device=codes.device, memory_format=torch.channels_last)
+    res = None if residual is None else _nhwc(residual).to(y.dtype)
+    with region('conv_i8_fwd', float(codes.numel() + y.numel() * y.element_size() * (2 if res is not None else 1))):
+      hip.conv_i8_fwd(codes, p['w'], ab, x.bits, p['scale_beta'], p['tsum'], p['tapsum'], y, B, H, Wd, C, N, self.k, self.k, self.stride,
+                      pad_h, pad_w, Ho, Wo, residual=res)
+    self.graph.int8_ran.add(self.kernel.name)
     return y
 
   def plain(self, x: torch.Tensor) -> torch.Tensor:
@@ -1854,9 +1932,13 @@ class BatchNormAct:
 
   def __init__(self, graph: Graph, name: str, channels: int, act: Optional[str], momentum: float, eps: float,
                l2: bool = False, act_name: Optional[str] = None, names=('gamma', 'beta', 'moving_mean',
-                                                                       'moving_variance'), lazy_ok: bool = False):
+                                                                       'moving_variance'), lazy_ok: bool = False,
+               codes_ok: Optional[bool] = None):
     self.graph, self.act, self.momentum, self.eps, self.C = graph, act, momentum, eps, channels
     self.lazy_ok = lazy_ok                    # every consumer is a Conv2D: the output may stay un-materialised
+    # every consumer is a Conv2D, as above, for the int8 inference route alone (CodesAct): also set where the training path keeps
+    # the output materialised (a BN in front of a 3x3 convolution)
+    self.codes_ok = lazy_ok if codes_ok is None else codes_ok
     st = graph.store
     self.gamma = st.add(name + '/' + names[0], (channels,), 'bn_gamma', True, l2, constant_init((channels,), 1.0))
     self.beta = st.add(name + '/' + names[1], (channels,), 'bn_beta', True, l2, constant_init((channels,), 0.0))
@@ -1942,6 +2024,8 @@ class BatchNormAct:
     rows = x.numel() // C
     if bits is None and lazy:
       return LazyAct(x, self._eval_scale_shift(x), self.act, None, None, rows, C)
+    if bits is not None and bits <= 8 and self.graph.int8 and self.codes_ok and x.is_cuda and x.dim() == 4:
+      return CodesAct(x, self._calibrated_scale_shift(x, slot), self.act, slot, bits, rows, C)
     q = torch.empty_like(x)
     if bits is None:
       # inference BN + act only: y = act(scale*x + shift); the teacher's (frozen) scale/shift is cached

@@ -56,6 +56,7 @@ SYMBOLS = [
     'pf_conv_gather_fwd',
     'pf_conv1x1_join_plan', 'pf_conv1x1_bwd_data_join',
     'pf_bn_act_quant_pool', 'pf_bn_bwd_stats_pooled', 'pf_bn_bwd_apply_pooled', 'pf_ce_distill_head', 'pf_ce_combine',
+    'pf_bn_act_quant_codes', 'pf_conv_i8_supported', 'pf_conv_i8_fwd',
 ]
 
 
@@ -745,6 +746,49 @@ def conv_gather_fwd(X, Wk, gather, Y, B: int, H: int, Wd: int, C: int, N: int, R
                                  c_int(ACT_CODES[act]), _ptr(Y), c_int(dtype_code(X)), c_int(B), c_int(H), c_int(Wd), c_int(C),
                                  c_int(Ck), c_int(N), c_int(R), c_int(S), c_int(stride), c_int(pad_h), c_int(pad_w), c_int(Ho),
                                  c_int(Wo), _stream()), 'pf_conv_gather_fwd')
+
+
+# ------------------------------------------------------------------------------------------------
+# int8 inference (pf_conv_i8.hip): uint8 activation codes x signed prepacked weights on the i8 matrix cores
+# ------------------------------------------------------------------------------------------------
+
+def bn_act_quant_codes(x, codes, rows: int, C: int, scale_shift, act, slot, bits: int, alpha_beta) -> None:
+  """codes[rows][C] (uint8) = the rounding decision of bn_act_quant_apply on x; alpha_beta[2] (float32) = the slot decoded."""
+  _dev(x)
+  if codes.dtype != torch.uint8 or alpha_beta.dtype != torch.float32 or scale_shift.dtype != torch.float32:
+    raise TypeError('bn_act_quant_codes: codes are uint8, alpha_beta and scale_shift float32')
+  if x.numel() != rows * C or codes.numel() != rows * C or alpha_beta.numel() < 2 or scale_shift.numel() != 2 * C or not 1 <= int(bits) <= 8:
+    raise ValueError('bn_act_quant_codes: operand sizes do not match rows=%d C=%d bits=%d' % (rows, C, bits))
+  _check(_lib.pf_bn_act_quant_codes(_ptr(x), _ptr(codes), c_int(dtype_code(x)), c_int64(rows), c_int(C), _ptr(scale_shift),
+                                    c_int(ACT_CODES[act]), _ptr(slot), c_int(int(bits)), _ptr(alpha_beta), _stream()),
+         'pf_bn_act_quant_codes')
+
+
+def conv_i8_supported(C: int, N: int, R: int, S: int, stride: int) -> bool:
+  return bool(_lib.pf_conv_i8_supported(c_int(C), c_int(N), c_int(R), c_int(S), c_int(stride)))
+
+
+def conv_i8_fwd(X, Wp, alpha_beta, act_bits: int, w_scale_beta, w_tsum, w_tapsum, Y, B: int, H: int, Wd: int, C: int, N: int, R: int,
+                S: int, stride: int, pad_h: int, pad_w: int, Ho: int, Wo: int, residual=None) -> None:
+  """Y[B][Ho][Wo][N] (float32 / bf16) = the convolution of the DECODED operands, from X uint8 codes [B][H][Wd][C] and the packed
+  layer of int8.pack_layer (Wp int8 [N][Kp], w_scale_beta [N][2], w_tsum [N], w_tapsum [N][R*S]) (+ residual of Y's type)."""
+  _dev(X)
+  Kp = -(-(R * S * C) // 64) * 64
+  if X.dtype != torch.uint8 or Wp.dtype != torch.int8 or alpha_beta.dtype != torch.float32 or w_scale_beta.dtype != torch.float32 or (
+      w_tsum.dtype != torch.int32 or w_tapsum.dtype != torch.int32) or (residual is not None and residual.dtype != Y.dtype):
+    raise TypeError('conv_i8_fwd: X uint8, Wp int8, tables float32 / int32, residual of the output type')
+  if not conv_i8_supported(C, N, R, S, stride):
+    raise ValueError('conv_i8_fwd: C=%d N=%d R=%d S=%d stride=%d is not eligible (pf_conv_i8_supported)' % (C, N, R, S, stride))
+  if X.numel() != B * H * Wd * C or Wp.numel() != N * Kp or Y.numel() != B * Ho * Wo * N or alpha_beta.numel() < 2 or (
+      w_scale_beta.numel() != 2 * N or w_tsum.numel() != N or w_tapsum.numel() != N * R * S) or (
+      residual is not None and residual.numel() != Y.numel()):
+    raise ValueError('conv_i8_fwd: operand sizes do not match B=%d H=%d W=%d C=%d N=%d R=%d S=%d Ho=%d Wo=%d'
+                     % (B, H, Wd, C, N, R, S, Ho, Wo))
+  if (Ho - 1) * stride + R - 2 * pad_h > H or (Wo - 1) * stride + S - 2 * pad_w > Wd:
+    raise ValueError('conv_i8_fwd: the output extends beyond the symmetrically padded input')
+  _check(_lib.pf_conv_i8_fwd(_ptr(X), _ptr(Wp), _ptr(alpha_beta), c_int(int(act_bits)), _ptr(w_scale_beta), _ptr(w_tsum), _ptr(w_tapsum),
+                             _ptr(residual), _ptr(Y), c_int(dtype_code(Y)), c_int(B), c_int(H), c_int(Wd), c_int(C), c_int(N), c_int(R),
+                             c_int(S), c_int(stride), c_int(pad_h), c_int(pad_w), c_int(Ho), c_int(Wo), _stream()), 'pf_conv_i8_fwd')
 
 
 def convg_bwd_data(dY, Wk, dX, B: int, H: int, Wd: int, C: int, N: int, R: int, S: int, stride: int, pad_h: int, pad_w: int,

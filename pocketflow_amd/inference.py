@@ -8,6 +8,9 @@ tools/conversion/export_chn_pruned_model.py (`model_shrunk.npz`: Conv2D kernels 
 A shrunk convolution runs on hip.conv_gather_fwd (pf_conv_gather.hip): its reduction covers the kept input channels only.  Layers for
 which `graph.gather_pays` says the gather kernel loses to the dense inference kernel are re-inflated at load time (the kept slices are
 scattered back into a zero kernel of full shape) and run exactly as in the fake-pruned checkpoint; `graph.reinflated` lists them.
+
+`load_int8` does the same for the integer artefact of tools/conversion/export_quant_int8_model.py (`model_int8.npz`): the learner's
+activation quantisers on, and the eligible convolutions on hip.conv_i8_fwd, which multiplies the integer codes themselves.
 """
 from __future__ import annotations
 
@@ -89,5 +92,71 @@ def load_shrunk(model_helper, path: str, device='cuda', compute_dtype=torch.floa
 
   def forward(images) -> torch.Tensor:
     with torch.no_grad(), graph.as_default():
+      return model_helper.forward_eval(G.to_device_images(images, graph))
+  return graph, forward
+
+
+def load_int8(model_helper, path: str, device='cuda', compute_dtype=torch.float32, activation_bits: int = 8, int8: str = 'auto'):
+  """The integer artefact of tools/conversion/export_quant_int8_model.py (`model_int8.npz`) as an inference graph with the learner's
+  activation quantisers on (`activation_bits` for every Relu / Relu6, as UniformQuantLearner feeds them).  Returns (graph, forward)
+  like load_shrunk.  `int8`:
+    'off'   every kernel decoded to float and run on the float kernels: what restoring the artefact into the learner evaluates;
+    'on'    every eligible Conv2D on hip.conv_i8_fwd: a kernel with at most 8 bits in tensor or channel buckets that
+            pf_conv_i8_supported takes.  It multiplies codes only where its input arrives as codes (a quantising BatchNormAct with
+            at most 8 activation bits whose consumers are all Conv2D); anywhere else it runs on its decoded kernel;
+    'auto'  of those, the layers `graph.int8_pays` accepts.
+  `graph.nb_int8`: layers packed for the int8 route; `graph.int8_ran`: names of the kernels that took it in the forward passes so
+  far.  Everything else -- the stem, Dense, depthwise, split buckets, wider kernels -- is untouched.  A malformed entry is a
+  ValueError that names the variable."""
+  from pocketflow_amd import int8 as I8
+  from pocketflow_amd.learners.abstract_learner import input_spec
+  from pocketflow_amd.tools.conversion.export_quant_int8_model import MODE_SPLIT, load_codes
+  if int8 not in ('auto', 'on', 'off'):
+    raise ValueError("int8 must be 'auto', 'on' or 'off'")
+  if not 1 <= int(activation_bits) <= 32:
+    raise ValueError('activation_bits must lie in 1..32 (got %s)' % activation_bits)
+  if not os.path.isfile(path):
+    raise FileNotFoundError(path)
+  variables, raw = load_codes(path)
+  graph = G.Graph(_scope_of(variables), device, compute_dtype)
+  graph.fuse_conv1x1 = bool(FLAGS.fuse_conv1x1)
+  with graph.as_default():
+    model_helper.forward_eval(input_spec(model_helper))
+  layers = {conv.kernel.name: conv for conv in graph.conv_layers}
+  packed = {}
+  for name in sorted(raw):
+    var = graph.store.by_name.get(name)
+    if var is None:
+      raise ValueError('%s: codes for a variable this graph does not have' % name)
+    meta = np.asarray(raw[name]['meta'])
+    if meta.ndim != 1 or meta.size < 4 or tuple(int(v) for v in meta[3:]) != tuple(var.ref_shape):
+      raise ValueError('%s: codes of shape %s, the graph has %s' % (name, tuple(int(v) for v in meta[3:]), tuple(var.ref_shape)))
+    conv = layers.get(name)
+    if int8 == 'off' or conv is None or conv.bias is not None or int(meta[0]) > 8 or int(meta[1]) == MODE_SPLIT:
+      continue
+    kh, kw, cin, cout = var.ref_shape
+    if not I8.supported(cin, cout, kh, kw, conv.stride):
+      continue
+    if int8 == 'auto' and not G.int8_pays(kh, cin, cout, conv.stride, compute_dtype):
+      continue
+    try:
+      packed[name] = I8.pack_layer(raw[name]['codes'], raw[name]['alpha'], raw[name]['beta'], meta)
+    except ValueError as e:
+      raise ValueError('%s: %s' % (name, e))
+  for op in graph.activation_ops:
+    if op.type in ('Relu', 'Relu6'):
+      op.bits = int(activation_bits)
+  graph.finalize(requires_grad=False)
+  graph.store.load_numpy(variables, strict=True)
+  graph.training = False
+  graph.frozen = True                            # the weights are fixed from here on
+  graph.int8 = bool(packed)
+  graph.nb_int8 = len(packed)
+  for name, p in packed.items():
+    layers[name].int8 = {k: torch.from_numpy(np.ascontiguousarray(p[k])).to(graph.device) for k in ('w', 'scale_beta', 'tsum', 'tapsum')}
+
+  def forward(images) -> torch.Tensor:
+    with torch.no_grad(), graph.as_default():
+      graph.begin_step()                         # the activation quantisers calibrate on every batch
       return model_helper.forward_eval(G.to_device_images(images, graph))
   return graph, forward

@@ -1,0 +1,126 @@
+"""Host side of the int8 inference path: packing an exported layer for `pf_conv_i8_fwd` and the NumPy statement of what
+that kernel computes.  No device work here.
+
+The artefact of tools/conversion/export_quant_int8_model.py keeps every quantised kernel as unsigned codes d in [0, k_w] with
+per-bucket (alpha, beta): w = beta + alpha * d / k_w.  A quantising BatchNormAct produces unsigned activation codes c in [0, k_a] with
+one (alpha_a, beta_a) per tensor: a = beta_a + alpha_a * c / k_a.  Their convolution, taps outside the image contributing a = 0, is
+
+    y[m][n] = (alpha_a/k_a)(alpha_w[n]/k_w) P + (alpha_a/k_a) beta_w[n] Sc + beta_a ((alpha_w[n]/k_w) Dv + beta_w[n] V)
+    P  = sum_window c d        (padding positions hold code 0)
+    Sc = sum_window c
+    Dv = sum of d[n] over the positions INSIDE the image,  V = their number (valid taps * C)
+
+`conv_reference` evaluates exactly this in int64 / float64 and is the executable definition of the layer.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional
+
+import numpy as np
+
+from pocketflow_amd.tools.conversion.export_quant_int8_model import MODE_CHANNEL, MODE_SPLIT, MODE_TENSOR, unpack_codes
+
+K_STEP = 64          # bytes of the window one matrix instruction consumes: packed rows are padded to a multiple of it
+
+
+def supported(C: int, N: int, R: int, S: int, stride: int) -> bool:
+  """The rule of pf_conv_i8_supported, restated for hosts without the library (the tests compare the two over a grid)."""
+  if min(C, N, R, S) <= 0 or stride not in (1, 2):
+    return False
+  return C % 16 == 0 and N % 8 == 0 and R * S * C * 2 ** 14 < 2 ** 31
+
+
+def pack_layer(codes: np.ndarray, alpha: np.ndarray, beta: np.ndarray, meta: np.ndarray) -> Dict[str, np.ndarray]:
+  """One exported Conv2D kernel (`<name>/codes|alpha|beta|meta` of the artefact; HWIO = [R][S][C][N]) in the form pf_conv_i8_fwd reads:
+    w          int8  [N][Kp]   t = d - 128 in KRSC order, Kp = R*S*C rounded up to 64, zeros beyond R*S*C
+    scale_beta f32   [N][2]    (alpha_w[n] / k_w, beta_w[n]); one bucket per tensor is repeated for every channel
+    tsum       int32 [N]       sum over the window of t
+    tapsum     int32 [N][R*S]  sum over the channels of d, per tap
+    d          uint8 [N][R][S][C]  the unsigned codes (for conv_reference; not sent to the device)
+  plus bits and the shape.  Raises ValueError for what the path does not cover: split buckets, more than 8 bits, a kernel that is
+  not 4-D."""
+  bits, mode = int(meta[0]), int(meta[1])
+  shape = tuple(int(v) for v in meta[3:])
+  if len(shape) != 4:
+    raise ValueError('pack_layer: a Conv2D kernel is [R][S][C][N], got shape %s' % (shape,))
+  if not 1 <= bits <= 8:
+    raise ValueError('pack_layer: 1..8 bit codes only (got %d)' % bits)
+  if mode == MODE_SPLIT:
+    raise ValueError('pack_layer: split buckets cut across output channels and are not eligible')
+  if mode not in (MODE_TENSOR, MODE_CHANNEL):
+    raise ValueError('pack_layer: unknown bucket mode %d' % mode)
+  R, S, C, N = shape
+  alpha, beta = np.asarray(alpha, np.float32).reshape(-1), np.asarray(beta, np.float32).reshape(-1)
+  nb = 1 if mode == MODE_TENSOR else N
+  if alpha.size != nb or beta.size != nb:
+    raise ValueError('pack_layer: %d (alpha, beta) pairs for %d buckets' % (alpha.size, nb))
+  k = np.float32(2 ** bits - 1)
+  d = unpack_codes(np.asarray(codes, np.uint8), bits, R * S * C * N).reshape(R, S, C, N)
+  if int(d.max(initial=0)) > int(k):
+    raise ValueError('pack_layer: a code exceeds 2^bits - 1')
+  d = np.ascontiguousarray(np.transpose(d, (3, 0, 1, 2)))                       # KRSC
+  K = R * S * C
+  Kp = -(-K // K_STEP) * K_STEP
+  w = np.zeros((N, Kp), np.int8)
+  w[:, :K] = (d.reshape(N, K).astype(np.int16) - 128).astype(np.int8)
+  scale_beta = np.empty((N, 2), np.float32)
+  scale_beta[:, 0] = np.broadcast_to((alpha / k).astype(np.float32), (N,))
+  scale_beta[:, 1] = np.broadcast_to(beta, (N,))
+  return dict(w=w, scale_beta=scale_beta, tsum=w.astype(np.int32).sum(axis=1).astype(np.int32),
+              tapsum=d.reshape(N, R * S, C).astype(np.int32).sum(axis=2).astype(np.int32), d=d, bits=bits,
+              alpha=np.broadcast_to(alpha, (N,)).copy(), beta=np.broadcast_to(beta, (N,)).copy(), shape=(R, S, C, N))
+
+
+def unpack_layer(p: Dict[str, np.ndarray]) -> np.ndarray:
+  """The unsigned KRSC codes back from the signed padded rows of a packed layer."""
+  R, S, C, N = p['shape']
+  return (p['w'][:, :R * S * C].astype(np.int16) + 128).astype(np.uint8).reshape(N, R, S, C)
+
+
+def out_size(H: int, R: int, stride: int, pad: int) -> int:
+  return (H + 2 * pad - R) // stride + 1
+
+
+def conv_reference(c: np.ndarray, alpha_a: float, beta_a: float, bits_a: int, d: np.ndarray, alpha_w: np.ndarray, beta_w: np.ndarray,
+                   bits_w: int, stride: int, pad_h: int, pad_w: int, residual: Optional[np.ndarray] = None, terms: bool = False):
+  """y[B][Ho][Wo][N] in float64 from activation codes c uint8 [B][H][W][C] and weight codes d uint8 [N][R][S][C], by the formula of the
+  module docstring: P, Sc, Dv, V in int64, everything else float64.  alpha_w / beta_w: [N].  With terms=True also returns
+  sum |terms| per output (the scale of the float32 rounding error of an implementation)."""
+  c = np.asarray(c)
+  d = np.asarray(d)
+  B, H, W, C = c.shape
+  N, R, S, Cd = d.shape
+  assert C == Cd
+  Ho, Wo = out_size(H, R, stride, pad_h), out_size(W, S, stride, pad_w)
+  ka, kw = float(2 ** bits_a - 1), float(2 ** bits_w - 1)
+  cp = np.zeros((B, H + 2 * pad_h, W + 2 * pad_w, C), np.int64)               # padding positions hold code 0
+  cp[:, pad_h:pad_h + H, pad_w:pad_w + W] = c
+  inside = np.zeros((H + 2 * pad_h, W + 2 * pad_w), np.int64)
+  inside[pad_h:pad_h + H, pad_w:pad_w + W] = 1
+  d64 = d.astype(np.int64)
+  df = d.astype(np.float64)                                                    # products of integers below 2^53: a float64 matmul is exact
+  dtap = d64.sum(axis=3)                                                       # [N][R][S]
+  P = np.zeros((B, Ho, Wo, N), np.int64)
+  Sc = np.zeros((B, Ho, Wo), np.int64)
+  Dv = np.zeros((Ho, Wo, N), np.int64)
+  V = np.zeros((Ho, Wo), np.int64)
+  for r in range(R):
+    for s in range(S):
+      win = cp[:, r:r + (Ho - 1) * stride + 1:stride, s:s + (Wo - 1) * stride + 1:stride]       # [B][Ho][Wo][C]
+      P += (win.astype(np.float64) @ df[:, r, s].T).astype(np.int64)
+      Sc += win.sum(axis=3)
+      ok = inside[r:r + (Ho - 1) * stride + 1:stride, s:s + (Wo - 1) * stride + 1:stride]     # [Ho][Wo]
+      Dv += ok[:, :, None] * dtap[None, None, :, r, s]
+      V += ok * C
+  sa = float(alpha_a) / ka
+  sw = np.asarray(alpha_w, np.float64).reshape(-1) / kw
+  bw = np.asarray(beta_w, np.float64).reshape(-1)
+  t1 = sa * sw * P
+  t2 = sa * bw * Sc[..., None]
+  t3a, t3b = float(beta_a) * (sw * Dv)[None], float(beta_a) * (bw * V[..., None])[None]
+  y = t1 + t2 + (t3a + t3b)
+  mag = np.abs(t1) + np.abs(t2) + np.abs(t3a) + np.abs(t3b)
+  if residual is not None:
+    y = y + np.asarray(residual, np.float64)
+    mag = mag + np.abs(np.asarray(residual, np.float64))
+  return (y, mag) if terms else y

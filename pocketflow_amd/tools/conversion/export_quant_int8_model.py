@@ -151,6 +151,18 @@ def load_exported(path: str) -> Dict[str, np.ndarray]:
   return out
 
 
+def load_codes(path: str):
+  """(variables, raw): `variables` as load_exported returns them; `raw` = {kernel name: dict(codes, alpha, beta, meta)} exactly as
+  stored, for consumers that multiply the integers themselves (pocketflow_amd.int8.pack_layer)."""
+  z = np.load(path)
+  raw = {}
+  for key in z.files:
+    if key.endswith('/codes'):
+      name = key[:-len('/codes')]
+      raw[name] = dict(codes=z[key], alpha=z[name + '/alpha'], beta=z[name + '/beta'], meta=z[name + '/meta'])
+  return load_exported(path), raw
+
+
 def main(argv=None):
   import sys
   from pocketflow_amd.flags import FLAGS, flags

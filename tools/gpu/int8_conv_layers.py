@@ -1,0 +1,104 @@
+"""Int8 layers one by one: every eligible convolution shape of ResNet-50 (v2 bottleneck) and every pointwise convolution of
+MobileNet-v1 1.0 at B = 256 / 224 x 224, bf16 output, 8-bit activations and weights: GPU time of the launches the graph makes for
+the layer on each route of inference.load_int8,
+
+  float  pf_bn_act_quant_apply (the producer BN's normalise / ReLU / fake-quant pass, bf16 -> bf16) + the bf16 kernel Conv2D
+         dispatches the shape to (pf_conv1x1_fwd / pf_conv2d_fwd), on the decoded kernel: int8 = 'off'
+  int8   pf_bn_act_quant_codes (bf16 -> uint8 codes) + pf_conv_i8_fwd on the packed kernel: int8 = 'on'
+
+alternating inside one process, and their ratio.  A producer pass that feeds two convolutions (bn1 of a projection block) is counted
+with each of them on both routes.  Bounds: max(FLOPs / peak, bytes / 8 TB/s) with the bf16 MFMA peak 2.5 PFLOP/s for the float
+route and twice that for int8; bytes = pre-BN input read + intermediate written and read + output written + kernel.
+
+  python tools/gpu/int8_conv_layers.py > profiles/int8_conv_layers.txt
+"""
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import numpy as np
+import torch
+from _timing import gpu_time_us
+from pocketflow_amd import hip, int8
+from pocketflow_amd.tools.conversion import export_quant_int8_model as ex
+from gather_conv_layers import MOBILENET, RESNET50
+
+B = int(os.environ.get('B', 256))
+MFMA_PEAK, HBM_PEAK = 2.5e15, 8.0e12
+
+
+def main():
+  print('# B = %d, bf16 activations, 8-bit codes; us per layer (best of 2 alternating rounds, each the best of 3 replays of 20 captured '
+        'launches); bound = max(FLOPs / peak, bytes / 8 TB/s)' % B)
+  print('%-10s %-20s %-22s %2s | %9s %9s %9s | %9s %9s %9s | %7s | %7s %7s' % (
+      'net', 'layer', 'H,C,N,k,stride', 'n', 'apply us', 'bf16 us', 'float us', 'codes us', 'i8 us', 'int8 us', 'f / i8', 'f bound', 'i bound'))
+  for net, layers in (('resnet50', RESNET50), ('mobilenet', MOBILENET)):
+    tot_f = tot_i = 0.0
+    for name, H, C, N, k, stride, pad, _lazy, cnt in layers:
+      if not hip.conv_i8_supported(C, N, k, k, stride) or (k > 1 and C % 64):
+        print('%-10s %-20s %-22s %2d | not eligible' % (net, name, '%d,%d,%d,%d,%d' % (H, C, N, k, stride), cnt))
+        continue
+      Ho = (H + 2 * pad - k) // stride + 1
+      M = B * Ho * Ho
+      rows = B * H * H
+      g = torch.Generator(device='cuda').manual_seed(H + C + N + k)
+      x = torch.randn((B, C, H, H), device='cuda', generator=g).bfloat16().contiguous(memory_format=torch.channels_last)
+      ss = torch.stack([torch.rand(C, device='cuda') + 0.5, torch.randn(C, device='cuda')]).contiguous()
+      xq = torch.empty_like(x)
+      codes = torch.empty(x.shape, dtype=torch.uint8, device='cuda').contiguous(memory_format=torch.channels_last)
+      ab = torch.empty(2, device='cuda')
+      slot = torch.empty((1, 2), dtype=torch.int32, device='cuda')
+      hip.minmax_slots_init(slot)
+      hip.bn_act_quant_apply(x, xq, rows, C, ss, 'Relu', None, 8, False)
+      hip.minmax_tensor(xq, slot[0])
+      rng = np.random.RandomState(C + N)
+      d = rng.randint(0, 256, size=(k, k, C, N)).astype(np.uint8)
+      alpha, beta = rng.uniform(0.05, 0.6, N).astype(np.float32), -rng.uniform(0.02, 0.3, N).astype(np.float32)
+      meta = np.array([8, ex.MODE_CHANNEL, 0, k, k, C, N], np.int64)
+      p = int8.pack_layer(ex.pack_codes(d.reshape(-1), 8), alpha, beta, meta)
+      wdec = ex.decode_tensor(ex.pack_codes(d.reshape(-1), 8), alpha, beta, meta)
+      wfull = torch.from_numpy(np.ascontiguousarray(wdec.transpose(3, 0, 1, 2))).cuda().bfloat16()
+      pw, psb, pts, ptp = (torch.from_numpy(np.ascontiguousarray(p[key])).cuda() for key in ('w', 'scale_beta', 'tsum', 'tapsum'))
+      y = torch.empty((B, N, Ho, Ho), dtype=torch.bfloat16, device='cuda').contiguous(memory_format=torch.channels_last)
+      if k == 1:
+        geom = None if stride == 1 else (Ho, Ho, H, H, stride)
+        w2 = wfull.reshape(N, C)
+        conv_f = lambda: hip.conv1x1_fwd(xq, w2, y, M, N, C, geom=geom)
+      else:
+        conv_f = lambda: hip.conv2d_fwd(xq, wfull, y, B, H, H, C, N, k, k, stride, pad, pad, Ho, Ho)
+      apply_f = lambda: hip.bn_act_quant_apply(x, xq, rows, C, ss, 'Relu', slot[0], 8, True)
+      codes_f = lambda: hip.bn_act_quant_codes(x, codes, rows, C, ss, 'Relu', slot[0], 8, ab)
+      conv_i = lambda: hip.conv_i8_fwd(codes, pw, ab, 8, psb, pts, ptp, y, B, H, H, C, N, k, k, stride, pad, pad, Ho, Ho)
+
+      def route_f():
+        apply_f()
+        conv_f()
+
+      def route_i():
+        codes_f()
+        conv_i()
+      t = {key: [] for key in ('apply', 'bf16', 'float', 'codes', 'i8', 'int8')}
+      for _ in range(2):                          # alternate the two routes
+        for key, fn in (('apply', apply_f), ('bf16', conv_f), ('float', route_f), ('codes', codes_f), ('i8', conv_i), ('int8', route_i)):
+          t[key].append(gpu_time_us(fn))
+      t = {key: min(v) for key, v in t.items()}
+      flops = 2.0 * M * N * k * k * C
+      read = rows * C // (stride * stride if k == 1 else 1)
+      bytes_f = rows * C * 4 + read * 2 + M * N * 2 + N * k * k * C * 2
+      bytes_i = rows * C * 3 + read + M * N * 2 + N * k * k * C
+      bound_f = max(flops / MFMA_PEAK, bytes_f / HBM_PEAK) * 1e6
+      bound_i = max(flops / (2 * MFMA_PEAK), bytes_i / HBM_PEAK) * 1e6
+      print('%-10s %-20s %-22s %2d | %9.1f %9.1f %9.1f | %9.1f %9.1f %9.1f | %7.2f | %7.2f %7.2f' % (
+          net, name, '%d,%d,%d,%d,%d' % (H, C, N, k, stride), cnt, t['apply'], t['bf16'], t['float'], t['codes'], t['i8'], t['int8'],
+          t['float'] / t['int8'], bound_f / t['float'], bound_i / t['int8']))
+      tot_f += cnt * t['float']
+      tot_i += cnt * t['int8']
+      del x, xq, y, codes
+    print('%-10s eligible convolutions of one forward pass (with their producer passes)  float %.2f ms   int8 %.2f ms   float / int8 %.2f'
+          % (net, tot_f / 1e3, tot_i / 1e3, tot_f / max(tot_i, 1e-9)))
+
+
+if __name__ == '__main__':
+  main()

@@ -1,0 +1,72 @@
+"""Whole-model inference time of an exported quantised model on the three routes of inference.load_int8: a synthetic ResNet-50
+checkpoint goes through the UniformQuantLearner (8-bit weights in channel buckets, 8-bit activations) and
+tools/conversion/export_quant_int8_model.py, then tools/benchmark/calc_inference_time runs on the artefact with --int8 off | auto | on,
+B = 256 / 224 x 224, bf16, in ROUNDS alternating rounds inside one process.  Prints every run and, per route, the median and the
+spread (max - min) over the rounds.
+
+  python tools/gpu/int8_inference_time.py > profiles/int8_inference_time.txt
+"""
+import io
+import json
+import os
+import sys
+import tempfile
+from contextlib import redirect_stdout
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+import torch
+
+B = int(os.environ.get('B', 256))
+IMAGE = int(os.environ.get('IMAGE', 224))
+ROUNDS = int(os.environ.get('ROUNDS', 3))
+REPTS = int(os.environ.get('REPTS', 20))
+
+
+def main():
+  from pocketflow_amd.flags import FLAGS
+  import pocketflow_amd.nets.resnet_at_ilsvrc12 as net
+  from pocketflow_amd.learners.learner_utils import create_synthetic_checkpoint
+  from pocketflow_amd.learners.uniform_quantization.learner import UniformQuantLearner
+  from pocketflow_amd.tools.benchmark import calc_inference_time as T
+  from pocketflow_amd.tools.conversion import export_quant_int8_model as E
+  from pocketflow_amd.utils import checkpoint
+  with tempfile.TemporaryDirectory() as tmp:
+    FLAGS.save_path = os.path.join(tmp, 'models', 'model.ckpt')
+    FLAGS.uql_save_quant_model_path = os.path.join(tmp, 'uql', 'model.ckpt')
+    FLAGS.resnet_size, FLAGS.nb_classes, FLAGS.image_size, FLAGS.batch_size = 50, 1001, IMAGE, 8
+    FLAGS.compute_dtype, FLAGS.synthetic_pool = 'bfloat16', 2
+    FLAGS.uql_weight_bits = FLAGS.uql_activation_bits = 8
+    FLAGS.uql_use_buckets, FLAGS.uql_bucket_type = True, 'channel'
+    mh = net.ModelHelper()
+    create_synthetic_checkpoint(mh)
+    learner = UniformQuantLearner(None, mh)
+    learner.restore_vars(checkpoint.latest_checkpoint(os.path.dirname(FLAGS.save_path)))
+    path = os.path.join(tmp, 'uql', 'model_int8.npz')
+    E.export_from_learner(learner, path)
+    del learner
+    torch.cuda.empty_cache()
+    common = ['--net', 'resnet_at_ilsvrc12', '--resnet_size', '50', '--nb_classes', '1001', '--image_size', str(IMAGE), '--batch_size', str(B),
+              '--compute_dtype', 'bfloat16', '--nb_repts_warmup', '5', '--nb_repts', str(REPTS), '--json', '--model_file', path,
+              '--uql_activation_bits', '8']
+    print('# ResNet-50, B = %d, %d x %d, bf16, w8 (channel buckets) / a8; %d passes per run after 5 warm-up passes; %d alternating rounds'
+          % (B, IMAGE, IMAGE, REPTS, ROUNDS))
+    ms = {'off': [], 'auto': [], 'on': []}
+    for rnd in range(ROUNDS):
+      for mode in ('off', 'auto', 'on'):
+        buf = io.StringIO()
+        with redirect_stdout(buf):
+          T.main(common + ['--int8', mode])
+        line = json.loads([ln for ln in buf.getvalue().splitlines() if ln.startswith('{')][-1])
+        ms[mode].append(line['ms_per_batch'])
+        print('round %d  --int8 %-4s  %9.3f ms per batch  nb_int8_layers %3d (%d ran)'
+              % (rnd, mode, line['ms_per_batch'], line['nb_int8_layers'], line['nb_int8_layers_ran']))
+        torch.cuda.empty_cache()
+    for mode in ('off', 'auto', 'on'):
+      v = sorted(ms[mode])
+      print('--int8 %-4s  median %9.3f ms  spread %7.3f ms  (off / this %.3f)'
+            % (mode, v[len(v) // 2], v[-1] - v[0], sorted(ms['off'])[len(v) // 2] / v[len(v) // 2]))
+
+
+if __name__ == '__main__':
+  main()
