@@ -498,6 +498,22 @@ int pf_conv_i8_fwd(const uint8_t* x, const int8_t* w, const float* act_alpha_bet
                    const int32_t* w_tsum, const int32_t* w_tapsum, const void* res, void* y, int out_dtype, int imgs, int H, int W,
                    int C, int N, int R, int S, int stride, int pad_h, int pad_w, int Ho, int Wo, void* stream);
 
+/* ---- int8 inference of MobileNet-v1's depthwise 3x3 layers (pf_depthwise_i8.hip) -------------------------------------------------------
+ * slim.separable_conv2d(num_outputs=None) (utils/external/mobilenet_v1.py:264-292) behind a quantising BatchNorm + ReLU6, on the
+ * producer's uint8 CODES (pf_bn_act_quant_codes) and the exported kernel's codes d[c][r][s], one (alpha_w, beta_w) per kernel:
+ *   y[b][ho][wo][c] = (alpha_a/k_a)(alpha_w/k_w) P + (alpha_a/k_a) beta_w Sc + beta_a ((alpha_w/k_w) Dv + beta_w V),
+ *   P = sum over the taps inside the image of code * d[c][r][s], Sc = the sum of those codes, Dv = the sum of those d[c][r][s], V =
+ *   their number; P, Sc, Dv exact in int32 (v_dot4_u32_u8), the float32 terms added in this order, one rounding to the output type.
+ * pf_dw_i8_fwd: x uint8 codes [B][H][W][C]; w_cols uint32 [C][3], entry [c][s] = d[c][0][s] | d[c][1][s] << 8 | d[c][2][s] << 16;
+ *   w_scale_beta [2] = (alpha_w / k_w, beta_w); act_alpha_beta the pair the producer wrote (never read by the host); y [B][Ho][Wo][C]
+ *   of `dtype`; pad_h / pad_w are the FRONT pads of TensorFlow 'SAME' (0..2; positions outside the image on either side contribute
+ *   nothing).  x and y 16-byte aligned, fewer than 2^31 elements each.  Returns non-zero without launching for a shape
+ *   pf_dw_i8_supported rejects or a null pointer.  Deterministic: no atomics, no workspace.
+ * pf_dw_i8_supported (host): C % 16 == 0, k == 3, stride 1 or 2. */
+int pf_dw_i8_supported(int C, int k, int stride);
+int pf_dw_i8_fwd(const uint8_t* x, const uint32_t* w_cols, const float* w_scale_beta, const float* act_alpha_beta, int act_bits, void* y,
+                 int dtype, int B, int H, int W, int C, int stride, int pad_h, int pad_w, int Ho, int Wo, void* stream);
+
 /* ---- R x S convolutions with few input channels (ResNet-20 @ CIFAR-10: resnet_model.py:156-199 with 16 / 32 filters) --------------
  * bf16, C % 8 == 0.  pf_im2col gathers Xcol[imgs*Ho*Wo][R*S*C] (taps outside the image: zeros) so that the convolution and its two
  * gradients are 1x1 products on pf_conv1x1_fwd / pf_conv1x1_wrw over Xcol and the [N][R*S*C] view of the KRSC kernel; pf_col2im is

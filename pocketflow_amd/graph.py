@@ -384,12 +384,13 @@ class Graph:
     self._names: Dict[str, int] = {}
     self.reinflated: List[str] = []            # shrunk kernels a loader scattered back to full shape (gather_pays)
     self.kernel_params = self.kernel_params_kept = self.nb_gathered = 0   # set by inference.load_shrunk
-    # int8 inference (inference.load_int8): quantising BatchNormAct layers whose consumers are all Conv2D hand out CodesAct, and the
-    # Conv2D layers the loader packed multiply the codes on pf_conv_i8_fwd; `int8_ran` collects the layers that did
+    # int8 inference (inference.load_int8): quantising BatchNormAct layers whose consumers are all Conv2D / DepthwiseConv2D hand out
+    # CodesAct, and the layers the loader packed multiply the codes on pf_conv_i8_fwd / pf_dw_i8_fwd; `int8_ran` collects the layers that did
     self.int8 = False
     self.nb_int8 = 0
     self.int8_ran: set = set()
     self.conv_layers: List = []                # every Conv2D of the graph, in creation order (the loader finds a kernel's layer here)
+    self.depthwise_layers: List = []           # every DepthwiseConv2D, likewise
 
   # -- naming like tf.layers (conv2d, conv2d_1, ...) ---------------------------------------------
   def unique_name(self, base: str) -> str:
@@ -781,7 +782,7 @@ def materialize(x):
 class CodesAct(LazyAct):
   """The output of a quantising inference-mode BatchNormAct (bits <= 8) on a graph with `int8` set: a LazyAct that can also hand out
   the activation as uint8 CODES plus the decoded (alpha, beta) pair on the device (one pf_bn_act_quant_codes launch, cached) -- what a
-  packed Conv2D multiplies on the i8 matrix cores.  `materialize()` is unchanged: the fake-quantised float tensor of the apply pass,
+  packed Conv2D multiplies on the i8 matrix cores and a packed DepthwiseConv2D on pf_dw_i8_fwd.  `materialize()` is unchanged: the fake-quantised float tensor of the apply pass,
   for every consumer that stays on the float kernels.  Inference only: there is no autograd node behind it."""
 
   def __init__(self, x, scale_shift, act, slot, bits, rows, C):
@@ -1598,6 +1599,24 @@ def int8_pays(k: int, cin: int, cout: int, stride: int, dtype) -> bool:
   return dtype == torch.bfloat16 and k == 1 and stride == 1 and cin == 256 and cout == 64
 
 
+def int8_dw_pays(C: int, stride: int, dtype) -> bool:
+  """Should a loader send an eligible depthwise 3x3 layer to pf_dw_i8_fwd (True) or leave it on pf_depthwise_fwd (False)?
+
+  profiles/int8_depthwise_layers.txt (the 13 depthwise shapes of MobileNet-v1 1.0 at B = 256 / 224 x 224, bf16, the launches each route
+  makes: fake-quant apply pass + pf_depthwise_fwd against codes pass + pf_dw_i8_fwd, three alternating rounds): the int8 route wins on
+  EVERY row, float / int8 1.49 - 2.00 with spreads between rounds of at most 1.8 us on rows of 30 - 326 us (summed over one pass: 1.81
+  against 1.09 ms).  Both halves gain: the codes pass writes one byte per element instead of two (0.7 x the apply pass) and the
+  depthwise kernel reads one instead of two (0.36 - 0.75 x pf_depthwise_fwd).  Whole model (profiles/int8_mobilenet_inference_time.txt):
+  with the pointwise layers on pf_conv_i8_fwd as well the pass takes 4.033 against 4.704 ms without this route.  True for exactly the
+  measured (C, stride) pairs in bf16; float32 output and other widths have not been timed.  (inference.load_int8(depthwise='on') runs
+  every eligible layer on the kernel.)"""
+  return dtype == torch.bfloat16 and (C, stride) in _INT8_DW_PAYS
+
+
+# (C, stride) of the rows of profiles/int8_depthwise_layers.txt on which the int8 route won by more than the spread: all of them
+_INT8_DW_PAYS = frozenset([(32, 1), (64, 2), (128, 1), (128, 2), (256, 1), (256, 2), (512, 1), (512, 2), (1024, 1)])
+
+
 class Conv2D:
   """tf.layers.conv2d / slim.conv2d: NHWC, kernel HWIO (stored KRSC), padding 'SAME' | 'VALID'."""
 
@@ -1843,6 +1862,8 @@ class DepthwiseConv2D:
     init = init or truncated_normal_init(ref_shape, 0.09)
     self.kernel = graph.store.add(name + '/' + kernel_name, ref_shape, 'depthwise', True, l2, init)
     self.op = graph.add_matmul_op('DepthwiseConv2dNative', name + '/depthwise', self.kernel)
+    self.int8 = None                             # the packed kernel on the device (inference.load_int8): tables of int8.pack_depthwise
+    graph.depthwise_layers.append(self)
 
   def plain(self, x):
     taps, self.graph.taps = self.graph.taps, None
@@ -1853,7 +1874,13 @@ class DepthwiseConv2D:
 
   def __call__(self, x, want_stats: bool = False) -> torch.Tensor:
     """`want_stats`: the consumer is a BatchNormAct -- leave the per-channel statistics of the output on the tensor."""
-    x = materialize(x)
+    if self.int8 is not None and self.graph.taps is None:
+      if torch.is_grad_enabled() and (self.kernel.tensor.requires_grad or (x.x if isinstance(x, LazyAct) else x).requires_grad):
+        raise RuntimeError('%s: a depthwise convolution packed for int8 runs in inference only: call it under torch.no_grad() on a '
+                           'graph finalised with requires_grad=False' % self.kernel.name)
+      if isinstance(x, CodesAct) and x.x.dim() == 4 and x.x.is_cuda and x.x.shape[1] == self.channels:
+        return self._call_int8(x)
+    x = materialize(x)                           # a CodesAct too: the fake-quantised tensor of the apply pass, as without int8
     if self.graph.taps is not None:
       return _tapped(self, x)
     ph = _same_pads(x.shape[2], self.k, self.stride)
@@ -1870,6 +1897,21 @@ class DepthwiseConv2D:
       return _run_depthwise(_nhwc(x), w, self.stride, ph[0], pw[0], Ho, Wo, want_stats)
     x, pad = _symmetric_pads(x, ph, pw)
     return F.conv2d(x, self.kernel.tensor, None, stride=self.stride, padding=pad, groups=self.channels)
+
+  def _call_int8(self, x: 'CodesAct') -> torch.Tensor:
+    """The packed layer on pf_dw_i8_fwd: the producer's codes times the kernel's codes in integers, scales and offsets in the epilogue
+    (pocketflow_amd/int8.py states the formula), one rounding to the compute dtype.  The BatchNorm behind it makes its own statistics
+    pass (the output carries none)."""
+    p = self.int8
+    codes, ab = x.codes()
+    B, C, H, Wd = codes.shape
+    ph, pw = _same_pads(H, self.k, self.stride), _same_pads(Wd, self.k, self.stride)
+    Ho, Wo = -(-H // self.stride), -(-Wd // self.stride)
+    y = torch.empty((B, C, Ho, Wo), dtype=x.dtype, device=codes.device, memory_format=torch.channels_last)
+    with region('dw_i8_fwd', float(codes.numel() + y.numel() * y.element_size())):
+      hip.dw_i8_fwd(codes, p['wcol'], p['scale_beta'], ab, x.bits, y, B, H, Wd, C, self.stride, ph[0], pw[0], Ho, Wo)
+    self.graph.int8_ran.add(self.kernel.name)
+    return y
 
 
 class Dense:
@@ -1936,8 +1978,8 @@ class BatchNormAct:
                codes_ok: Optional[bool] = None):
     self.graph, self.act, self.momentum, self.eps, self.C = graph, act, momentum, eps, channels
     self.lazy_ok = lazy_ok                    # every consumer is a Conv2D: the output may stay un-materialised
-    # every consumer is a Conv2D, as above, for the int8 inference route alone (CodesAct): also set where the training path keeps
-    # the output materialised (a BN in front of a 3x3 convolution)
+    # every consumer is a Conv2D or a DepthwiseConv2D, for the int8 inference route alone (CodesAct): also set where the training path
+    # keeps the output materialised (a BN in front of a 3x3 or a depthwise convolution)
     self.codes_ok = lazy_ok if codes_ok is None else codes_ok
     st = graph.store
     self.gamma = st.add(name + '/' + names[0], (channels,), 'bn_gamma', True, l2, constant_init((channels,), 1.0))

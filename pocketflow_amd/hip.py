@@ -57,6 +57,7 @@ SYMBOLS = [
     'pf_conv1x1_join_plan', 'pf_conv1x1_bwd_data_join',
     'pf_bn_act_quant_pool', 'pf_bn_bwd_stats_pooled', 'pf_bn_bwd_apply_pooled', 'pf_ce_distill_head', 'pf_ce_combine',
     'pf_bn_act_quant_codes', 'pf_conv_i8_supported', 'pf_conv_i8_fwd',
+    'pf_dw_i8_supported', 'pf_dw_i8_fwd',
 ]
 
 
@@ -789,6 +790,28 @@ def conv_i8_fwd(X, Wp, alpha_beta, act_bits: int, w_scale_beta, w_tsum, w_tapsum
   _check(_lib.pf_conv_i8_fwd(_ptr(X), _ptr(Wp), _ptr(alpha_beta), c_int(int(act_bits)), _ptr(w_scale_beta), _ptr(w_tsum), _ptr(w_tapsum),
                              _ptr(residual), _ptr(Y), c_int(dtype_code(Y)), c_int(B), c_int(H), c_int(Wd), c_int(C), c_int(N), c_int(R),
                              c_int(S), c_int(stride), c_int(pad_h), c_int(pad_w), c_int(Ho), c_int(Wo), _stream()), 'pf_conv_i8_fwd')
+
+
+# depthwise 3x3 layers on codes (pf_depthwise_i8.hip): byte columns x v_dot4_u32_u8, HBM traffic of one byte per input element
+def dw_i8_supported(C: int, k: int, stride: int) -> bool:
+  return bool(_lib.pf_dw_i8_supported(c_int(C), c_int(k), c_int(stride)))
+
+
+def dw_i8_fwd(X, w_cols, w_scale_beta, alpha_beta, act_bits: int, Y, B: int, H: int, Wd: int, C: int, stride: int, pad_h: int, pad_w: int,
+              Ho: int, Wo: int) -> None:
+  """Y[B][Ho][Wo][C] (float32 / bf16) = the depthwise 3x3 convolution of the DECODED operands, from X uint8 codes [B][H][Wd][C] and the
+  tables of int8.pack_depthwise (w_cols uint32 [C][3] viewed as int32, w_scale_beta float32 [2]); pad_h / pad_w: the front pads."""
+  _dev(X)
+  if X.dtype != torch.uint8 or w_cols.dtype != torch.int32 or alpha_beta.dtype != torch.float32 or w_scale_beta.dtype != torch.float32:
+    raise TypeError('dw_i8_fwd: X uint8, w_cols int32, w_scale_beta and alpha_beta float32')
+  if not dw_i8_supported(C, 3, stride):
+    raise ValueError('dw_i8_fwd: C=%d stride=%d is not eligible (pf_dw_i8_supported)' % (C, stride))
+  if X.numel() != B * H * Wd * C or w_cols.numel() != 3 * C or Y.numel() != B * Ho * Wo * C or alpha_beta.numel() < 2 or (
+      w_scale_beta.numel() != 2):
+    raise ValueError('dw_i8_fwd: operand sizes do not match B=%d H=%d W=%d C=%d Ho=%d Wo=%d' % (B, H, Wd, C, Ho, Wo))
+  _check(_lib.pf_dw_i8_fwd(_ptr(X), _ptr(w_cols), _ptr(w_scale_beta), _ptr(alpha_beta), c_int(int(act_bits)), _ptr(Y),
+                           c_int(dtype_code(Y)), c_int(B), c_int(H), c_int(Wd), c_int(C), c_int(stride), c_int(pad_h), c_int(pad_w),
+                           c_int(Ho), c_int(Wo), _stream()), 'pf_dw_i8_fwd')
 
 
 def convg_bwd_data(dY, Wk, dX, B: int, H: int, Wd: int, C: int, N: int, R: int, S: int, stride: int, pad_h: int, pad_w: int,

@@ -10,7 +10,8 @@ which `graph.gather_pays` says the gather kernel loses to the dense inference ke
 scattered back into a zero kernel of full shape) and run exactly as in the fake-pruned checkpoint; `graph.reinflated` lists them.
 
 `load_int8` does the same for the integer artefact of tools/conversion/export_quant_int8_model.py (`model_int8.npz`): the learner's
-activation quantisers on, and the eligible convolutions on hip.conv_i8_fwd, which multiplies the integer codes themselves.
+activation quantisers on, and the eligible convolutions on hip.conv_i8_fwd (depthwise 3x3 layers: hip.dw_i8_fwd), which multiply the
+integer codes themselves.
 """
 from __future__ import annotations
 
@@ -96,7 +97,8 @@ def load_shrunk(model_helper, path: str, device='cuda', compute_dtype=torch.floa
   return graph, forward
 
 
-def load_int8(model_helper, path: str, device='cuda', compute_dtype=torch.float32, activation_bits: int = 8, int8: str = 'auto'):
+def load_int8(model_helper, path: str, device='cuda', compute_dtype=torch.float32, activation_bits: int = 8, int8: str = 'auto',
+              depthwise: str = 'off'):
   """The integer artefact of tools/conversion/export_quant_int8_model.py (`model_int8.npz`) as an inference graph with the learner's
   activation quantisers on (`activation_bits` for every Relu / Relu6, as UniformQuantLearner feeds them).  Returns (graph, forward)
   like load_shrunk.  `int8`:
@@ -105,14 +107,20 @@ def load_int8(model_helper, path: str, device='cuda', compute_dtype=torch.float3
             pf_conv_i8_supported takes.  It multiplies codes only where its input arrives as codes (a quantising BatchNormAct with
             at most 8 activation bits whose consumers are all Conv2D); anywhere else it runs on its decoded kernel;
     'auto'  of those, the layers `graph.int8_pays` accepts.
-  `graph.nb_int8`: layers packed for the int8 route; `graph.int8_ran`: names of the kernels that took it in the forward passes so
-  far.  Everything else -- the stem, Dense, depthwise, split buckets, wider kernels -- is untouched.  A malformed entry is a
-  ValueError that names the variable."""
+  `depthwise` (ignored when int8 = 'off') does the same for the depthwise 3x3 layers (MobileNet-v1) and hip.dw_i8_fwd:
+    'off'   none, the default: every depthwise layer runs on its decoded kernel (a producer's codes are materialised for it);
+    'on'    every eligible one: at most 8 bits, not in split buckets, `int8.depthwise_supported`;
+    'auto'  of those, the layers `graph.int8_dw_pays` accepts.
+  `graph.nb_int8`: layers packed for the int8 route, Conv2D and depthwise together; `graph.int8_ran`: names of the kernels that
+  took it in the forward passes so far.  Everything else -- the stem, Dense, split buckets, wider kernels -- is untouched.  A
+  malformed entry is a ValueError that names the variable."""
   from pocketflow_amd import int8 as I8
   from pocketflow_amd.learners.abstract_learner import input_spec
   from pocketflow_amd.tools.conversion.export_quant_int8_model import MODE_SPLIT, load_codes
   if int8 not in ('auto', 'on', 'off'):
     raise ValueError("int8 must be 'auto', 'on' or 'off'")
+  if depthwise not in ('auto', 'on', 'off'):
+    raise ValueError("depthwise must be 'auto', 'on' or 'off'")
   if not 1 <= int(activation_bits) <= 32:
     raise ValueError('activation_bits must lie in 1..32 (got %s)' % activation_bits)
   if not os.path.isfile(path):
@@ -123,7 +131,8 @@ def load_int8(model_helper, path: str, device='cuda', compute_dtype=torch.float3
   with graph.as_default():
     model_helper.forward_eval(input_spec(model_helper))
   layers = {conv.kernel.name: conv for conv in graph.conv_layers}
-  packed = {}
+  dw_layers = {dw.kernel.name: dw for dw in graph.depthwise_layers}
+  packed, packed_dw = {}, {}
   for name in sorted(raw):
     var = graph.store.by_name.get(name)
     if var is None:
@@ -131,6 +140,18 @@ def load_int8(model_helper, path: str, device='cuda', compute_dtype=torch.float3
     meta = np.asarray(raw[name]['meta'])
     if meta.ndim != 1 or meta.size < 4 or tuple(int(v) for v in meta[3:]) != tuple(var.ref_shape):
       raise ValueError('%s: codes of shape %s, the graph has %s' % (name, tuple(int(v) for v in meta[3:]), tuple(var.ref_shape)))
+    dw = dw_layers.get(name)
+    if dw is not None:
+      if (int8 == 'off' or depthwise == 'off' or int(meta[0]) > 8 or int(meta[1]) == MODE_SPLIT
+          or not I8.depthwise_supported(dw.channels, dw.k, dw.stride)):
+        continue
+      if depthwise == 'auto' and not G.int8_dw_pays(dw.channels, dw.stride, compute_dtype):
+        continue
+      try:
+        packed_dw[name] = I8.pack_depthwise(raw[name]['codes'], raw[name]['alpha'], raw[name]['beta'], meta)
+      except ValueError as e:
+        raise ValueError('%s: %s' % (name, e))
+      continue
     conv = layers.get(name)
     if int8 == 'off' or conv is None or conv.bias is not None or int(meta[0]) > 8 or int(meta[1]) == MODE_SPLIT:
       continue
@@ -150,10 +171,13 @@ def load_int8(model_helper, path: str, device='cuda', compute_dtype=torch.float3
   graph.store.load_numpy(variables, strict=True)
   graph.training = False
   graph.frozen = True                            # the weights are fixed from here on
-  graph.int8 = bool(packed)
-  graph.nb_int8 = len(packed)
+  graph.int8 = bool(packed) or bool(packed_dw)
+  graph.nb_int8 = len(packed) + len(packed_dw)
   for name, p in packed.items():
     layers[name].int8 = {k: torch.from_numpy(np.ascontiguousarray(p[k])).to(graph.device) for k in ('w', 'scale_beta', 'tsum', 'tapsum')}
+  for name, p in packed_dw.items():
+    dw_layers[name].int8 = {'wcol': torch.from_numpy(p['wcol'].view(np.int32)).to(graph.device),
+                            'scale_beta': torch.from_numpy(p['scale_beta']).to(graph.device)}
 
   def forward(images) -> torch.Tensor:
     with torch.no_grad(), graph.as_default():

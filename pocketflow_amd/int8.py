@@ -11,6 +11,9 @@ one (alpha_a, beta_a) per tensor: a = beta_a + alpha_a * c / k_a.  Their convolu
     Dv = sum of d[n] over the positions INSIDE the image,  V = their number (valid taps * C)
 
 `conv_reference` evaluates exactly this in int64 / float64 and is the executable definition of the layer.
+
+A depthwise 3x3 layer (MobileNet-v1; `pf_dw_i8_fwd`) is the same expansion channel by channel, with the one (alpha_w, beta_w) a depthwise
+kernel has and TensorFlow 'SAME' pads: `depthwise_reference`, `pack_depthwise`, `depthwise_supported`.
 """
 from __future__ import annotations
 
@@ -123,4 +126,94 @@ def conv_reference(c: np.ndarray, alpha_a: float, beta_a: float, bits_a: int, d:
   if residual is not None:
     y = y + np.asarray(residual, np.float64)
     mag = mag + np.abs(np.asarray(residual, np.float64))
+  return (y, mag) if terms else y
+
+
+# ---- depthwise 3x3 (pf_depthwise_i8.hip) ----------------------------------------------------------------------------------------
+
+def depthwise_supported(C: int, k: int, stride: int) -> bool:
+  """The rule of pf_dw_i8_supported, restated for hosts without the library (the tests compare the two over a grid)."""
+  return C > 0 and C % 16 == 0 and k == 3 and stride in (1, 2)
+
+
+def same_pads(size: int, k: int, stride: int):
+  """TensorFlow 'SAME' (front, back) pads, as graph._same_pads computes them: the odd pixel goes behind."""
+  out = -(-size // stride)
+  total = max((out - 1) * stride + k - size, 0)
+  return total // 2, total - total // 2
+
+
+def pack_depthwise(codes: np.ndarray, alpha: np.ndarray, beta: np.ndarray, meta: np.ndarray) -> Dict[str, np.ndarray]:
+  """One exported depthwise kernel (`<name>/codes|alpha|beta|meta`; reference shape [3][3][C][1]) in the form pf_dw_i8_fwd reads:
+    wcol       uint32 [C][3]   column s of channel c: d[c][0][s] | d[c][1][s] << 8 | d[c][2][s] << 16
+    scale_beta f32    [2]      (alpha_w / k_w, beta_w)
+    d          uint8  [C][3][3]  the unsigned codes (for depthwise_reference; not sent to the device)
+  plus bits, alpha, beta and the shape.  Raises ValueError for split buckets, more than 8 bits and a shape that is not (3, 3, C, 1)."""
+  bits, mode = int(meta[0]), int(meta[1])
+  shape = tuple(int(v) for v in meta[3:])
+  if len(shape) != 4 or shape[:2] != (3, 3) or shape[3] != 1 or shape[2] <= 0:
+    raise ValueError('pack_depthwise: a depthwise kernel is [3][3][C][1], got shape %s' % (shape,))
+  if not 1 <= bits <= 8:
+    raise ValueError('pack_depthwise: 1..8 bit codes only (got %d)' % bits)
+  if mode == MODE_SPLIT:
+    raise ValueError('pack_depthwise: split buckets are not eligible')
+  if mode not in (MODE_TENSOR, MODE_CHANNEL):
+    raise ValueError('pack_depthwise: unknown bucket mode %d' % mode)
+  alpha, beta = np.asarray(alpha, np.float32).reshape(-1), np.asarray(beta, np.float32).reshape(-1)
+  if alpha.size != 1 or beta.size != 1:                 # [3][3][C][1] has one output channel: one bucket in either mode
+    raise ValueError('pack_depthwise: %d (alpha, beta) pairs for the one bucket of a depthwise kernel' % alpha.size)
+  C = shape[2]
+  k = np.float32(2 ** bits - 1)
+  d = unpack_codes(np.asarray(codes, np.uint8), bits, 9 * C).reshape(3, 3, C)
+  if int(d.max(initial=0)) > int(k):
+    raise ValueError('pack_depthwise: a code exceeds 2^bits - 1')
+  d = np.ascontiguousarray(np.transpose(d, (2, 0, 1)))                          # [C][r][s]
+  d32 = d.astype(np.uint32)
+  wcol = np.ascontiguousarray(d32[:, 0, :] | (d32[:, 1, :] << 8) | (d32[:, 2, :] << 16))
+  return dict(wcol=wcol, scale_beta=np.array([alpha[0] / k, beta[0]], np.float32), d=d, bits=bits, alpha=float(alpha[0]),
+              beta=float(beta[0]), shape=shape)
+
+
+def unpack_depthwise(p: Dict[str, np.ndarray]) -> np.ndarray:
+  """The unsigned [C][3][3] codes back from the column table of a packed depthwise kernel."""
+  w = p['wcol']
+  return np.stack([(w >> (8 * r)) & 0xFF for r in range(3)], axis=1).astype(np.uint8)
+
+
+def depthwise_reference(c: np.ndarray, alpha_a: float, beta_a: float, bits_a: int, d: np.ndarray, alpha_w: float, beta_w: float,
+                        bits_w: int, stride: int, terms: bool = False):
+  """y[B][Ho][Wo][C] in float64 from activation codes c uint8 [B][H][W][C] and weight codes d uint8 [C][3][3] under TensorFlow 'SAME'
+  pads: P, Sc, Dv, V in int64 over the taps INSIDE the image, everything else float64,
+    y = (alpha_a/k_a)(alpha_w/k_w) P + (alpha_a/k_a) beta_w Sc + beta_a ((alpha_w/k_w) Dv + beta_w V).
+  With terms=True also returns sum |terms| per output, as conv_reference does."""
+  c = np.asarray(c)
+  d = np.asarray(d)
+  B, H, W, C = c.shape
+  assert d.shape == (C, 3, 3)
+  (ph, ph1), (pw, pw1) = same_pads(H, 3, stride), same_pads(W, 3, stride)
+  Ho, Wo = -(-H // stride), -(-W // stride)
+  ka, kw = float(2 ** bits_a - 1), float(2 ** bits_w - 1)
+  cp = np.zeros((B, H + ph + ph1, W + pw + pw1, C), np.int64)                   # a tap outside the image adds nothing to any sum
+  cp[:, ph:ph + H, pw:pw + W] = c
+  inside = np.zeros((H + ph + ph1, W + pw + pw1), np.int64)
+  inside[ph:ph + H, pw:pw + W] = 1
+  d64 = d.astype(np.int64)
+  P = np.zeros((B, Ho, Wo, C), np.int64)
+  Sc = np.zeros((B, Ho, Wo, C), np.int64)
+  Dv = np.zeros((Ho, Wo, C), np.int64)
+  V = np.zeros((Ho, Wo), np.int64)
+  for r in range(3):
+    for s in range(3):
+      win = cp[:, r:r + (Ho - 1) * stride + 1:stride, s:s + (Wo - 1) * stride + 1:stride]       # [B][Ho][Wo][C]
+      ok = inside[r:r + (Ho - 1) * stride + 1:stride, s:s + (Wo - 1) * stride + 1:stride]       # [Ho][Wo]
+      P += win * d64[:, r, s]
+      Sc += win
+      Dv += ok[:, :, None] * d64[None, None, :, r, s]
+      V += ok
+  sa, sw, bw = float(alpha_a) / ka, float(alpha_w) / kw, float(beta_w)
+  t1 = sa * sw * P
+  t2 = sa * bw * Sc
+  t3a, t3b = float(beta_a) * (sw * Dv)[None], float(beta_a) * (bw * V[..., None])[None]
+  y = t1 + t2 + (t3a + t3b)
+  mag = np.abs(t1) + np.abs(t2) + np.abs(t3a) + np.abs(t3b)
   return (y, mag) if terms else y

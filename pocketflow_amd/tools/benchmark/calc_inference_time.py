@@ -16,7 +16,8 @@ here the default is the dataset's training batch, 128 for CIFAR-10 and 64 for IL
 `--model_file` flag and is loaded with pocketflow_amd.inference.load_int8: `--int8 auto|on|off` chooses which eligible convolutions
 multiply integer codes on the i8 matrix cores ('off': every kernel decoded, the float kernels; the baseline), and the learner's own
 `--uql_activation_bits` (default 32: no codes, nothing runs on int8) sets the activation quantisers; the result line then carries
-`nb_int8_layers`.
+`nb_int8_layers`.  `--int8_depthwise off|on|auto` (default off) does the same for the depthwise 3x3 layers of a MobileNet
+(pf_dw_i8_fwd; 'auto' = the layers graph.int8_dw_pays accepts); packed depthwise layers count in `nb_int8_layers`.
 
     python -m pocketflow_amd.tools.benchmark.calc_inference_time --net resnet_at_ilsvrc12 --resnet_size 50 --batch_size 256 \\
         --compute_dtype bfloat16 --model_file ./models_uqtf_eval/model_int8.npz --int8 on --uql_activation_bits 8
@@ -46,6 +47,7 @@ flags.DEFINE_integer('nb_repts', 100, '# of repeated runs for elapsed time measu
 flags.DEFINE_string('net', 'resnet_at_ilsvrc12', 'ModelHelper module under pocketflow_amd.nets')
 flags.DEFINE_string('reinflate', 'auto', "'auto': re-inflate the layers graph.gather_pays rejects | 'none' | 'all' (full-shape baseline)")
 flags.DEFINE_string('int8', 'auto', "a model_int8.npz: 'auto' = the layers graph.int8_pays accepts on the int8 kernel | 'on' = every eligible layer | 'off' = none")
+flags.DEFINE_string('int8_depthwise', 'off', "a model_int8.npz: depthwise 3x3 layers on the int8 kernel: 'off' = none | 'on' = every eligible layer | 'auto' = the layers graph.int8_dw_pays accepts")
 flags.DEFINE_boolean('json', False, 'print one JSON result line')
 
 log = logging.getLogger('pocketflow_amd')
@@ -98,7 +100,8 @@ def main(argv=None) -> int:
   mh = mod.ModelHelper()
   int8 = is_int8_artefact(FLAGS.model_file)
   if int8:
-    graph, _ = load_int8(mh, FLAGS.model_file, device, AL.compute_dtype(), FLAGS.uql_activation_bits, int8=FLAGS.int8)
+    graph, _ = load_int8(mh, FLAGS.model_file, device, AL.compute_dtype(), FLAGS.uql_activation_bits, int8=FLAGS.int8,
+                         depthwise=FLAGS.int8_depthwise)
   else:
     graph, _ = load_shrunk(mh, FLAGS.model_file, device, AL.compute_dtype(), reinflate=FLAGS.reinflate)
   batch = int(mh.dataset_train.batch_size)
@@ -115,13 +118,13 @@ def main(argv=None) -> int:
           'nb_reinflated_layers': len(graph.reinflated),
           'kernel_params_kept_share': graph.kernel_params_kept / max(graph.kernel_params, 1)}
   if int8:
-    rslt.update({'int8': FLAGS.int8, 'nb_int8_layers': graph.nb_int8, 'nb_int8_layers_ran': len(graph.int8_ran),
+    rslt.update({'int8': FLAGS.int8, 'int8_depthwise': FLAGS.int8_depthwise, 'nb_int8_layers': graph.nb_int8, 'nb_int8_layers_ran': len(graph.int8_ran),
                  'activation_bits': FLAGS.uql_activation_bits})
   print('time consumption of %s: %.3f ms per batch of %d, %.4f ms per image (%d gathered layers, %d re-inflated)'
         % (FLAGS.model_file, rslt['ms_per_batch'], batch, rslt['ms_per_image'], graph.nb_gathered, len(graph.reinflated)))
   if int8:
-    print('int8 = %s: nb_int8_layers = %d (%d took the int8 kernel), %d activation bits'
-          % (FLAGS.int8, graph.nb_int8, len(graph.int8_ran), FLAGS.uql_activation_bits))
+    print('int8 = %s, int8_depthwise = %s: nb_int8_layers = %d (%d took the int8 kernel), %d activation bits'
+          % (FLAGS.int8, FLAGS.int8_depthwise, graph.nb_int8, len(graph.int8_ran), FLAGS.uql_activation_bits))
   if FLAGS.json:
     print(json.dumps(rslt))
   return 0

@@ -1,0 +1,126 @@
+"""pf_dw_i8_fwd (through hip.py, and the raw C entry for what it must refuse) against int8.depthwise_reference.
+
+The exact case pins the byte gathering and the dot products of the kernel: with integer-valued scales every term of the layer formula
+is an integer below 2^24, so the float32 output has to equal the reference bit for bit and the bf16 output its bf16 rounding."""
+from ctypes import c_int, c_void_p
+
+import numpy as np
+import pytest
+import torch
+
+from pocketflow_amd import int8
+from pocketflow_amd.tools.conversion import export_quant_int8_model as ex
+
+pytestmark = pytest.mark.gpu
+
+B = 2
+# (H, W, C): the four small images at one and at three channel groups; 28 x 28 x 64 makes several workgroups, full strips and (stride 2) a tail
+CASES = [(H, W, C) for (H, W) in ((1, 1), (5, 7), (8, 6), (9, 4)) for C in (16, 48)] + [(28, 28, 64)]
+
+
+@pytest.fixture(scope='module')
+def hip():
+  from pocketflow_amd import hip as h
+  assert torch.cuda.is_available(), 'gpu tests need a GPU'
+  return h
+
+
+def dev(a):
+  return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _kernel(rng, C, bits_w, alpha_w, beta_w):
+  d_hwio = rng.integers(0, 2 ** bits_w, size=(3, 3, C, 1)).astype(np.uint8)
+  d_hwio.reshape(-1)[0] = 2 ** bits_w - 1                      # both ends of the grid occur
+  d_hwio.reshape(-1)[1] = 0
+  meta = np.array([bits_w, ex.MODE_TENSOR, 0, 3, 3, C, 1], np.int64)
+  return int8.pack_depthwise(ex.pack_codes(d_hwio.reshape(-1), bits_w), np.array([alpha_w], np.float32), np.array([beta_w], np.float32),
+                             meta)
+
+
+def _run(hip, c, p, alpha_a, beta_a, stride, out_dtype):
+  _, H, W, C = c.shape
+  Ho, Wo = -(-H // stride), -(-W // stride)
+  y = torch.full((B, Ho, Wo, C), float('nan'), dtype=out_dtype, device='cuda')
+  ab = dev(np.array([alpha_a, beta_a], np.float32))
+  hip.dw_i8_fwd(dev(c), dev(p['wcol'].view(np.int32)), dev(p['scale_beta']), ab, 8, y, B, H, W, C, stride,
+                int8.same_pads(H, 3, stride)[0], int8.same_pads(W, 3, stride)[0], Ho, Wo)
+  torch.cuda.synchronize()
+  return y
+
+
+def _ref(c, p, alpha_a, beta_a, stride):
+  return int8.depthwise_reference(c, alpha_a, beta_a, 8, p['d'], p['alpha'], p['beta'], p['bits'], stride, terms=True)
+
+
+@pytest.mark.parametrize('beta_a', [0.0, 2.0])
+@pytest.mark.parametrize('stride', [1, 2])
+@pytest.mark.parametrize('H,W,C', CASES)
+def test_exact_case_is_bit_for_bit(hip, H, W, C, stride, beta_a):
+  """alpha_a = 255 (step 1), alpha_w = 15 * 2^e over 4-bit codes (step 2^e), integer beta_w and beta_a: every term an integer < 2^24."""
+  rng = np.random.default_rng(1000 * H + 100 * W + C + stride)
+  c = rng.integers(0, 256, size=(B, H, W, C)).astype(np.uint8)
+  c.reshape(-1)[:2] = (0, 255)
+  p = _kernel(rng, C, 4, 15.0 * 2.0 ** int(rng.integers(0, 2)), -float(rng.integers(1, 3)))
+  want, mag = _ref(c, p, 255.0, beta_a, stride)
+  assert mag.max() < 2 ** 24 and np.array_equal(want, np.rint(want))
+  got = _run(hip, c, p, 255.0, beta_a, stride, torch.float32).cpu().numpy()
+  bad = np.argwhere(got != want.astype(np.float32))
+  assert bad.size == 0, (len(bad), bad[:5], got[tuple(bad[0])], want[tuple(bad[0])])
+  got16 = _run(hip, c, p, 255.0, beta_a, stride, torch.bfloat16).cpu()
+  assert torch.equal(got16, torch.from_numpy(want.astype(np.float32)).to(torch.bfloat16))
+
+
+@pytest.mark.parametrize('stride', [1, 2])
+@pytest.mark.parametrize('H,W,C', CASES)
+def test_general_parameters_and_determinism(hip, H, W, C, stride):
+  """float32 output within 1e-5 * sum |terms| of the reference (a few float32 ulps of the summed term magnitudes); bf16 output
+  additionally 2^-8 |y| for its one rounding; two calls give the same bits."""
+  rng = np.random.default_rng(1000 * H + 100 * W + C * 7 + stride)
+  c = rng.integers(0, 256, size=(B, H, W, C)).astype(np.uint8)
+  p = _kernel(rng, C, 8, float(rng.uniform(0.05, 0.6)), -float(rng.uniform(0.02, 0.3)))
+  alpha_a = float(np.float32(rng.uniform(1.0, 6.0)))
+  for beta_a in (0.0, float(np.float32(0.37))):
+    want, mag = _ref(c, p, alpha_a, beta_a, stride)
+    y32 = _run(hip, c, p, alpha_a, beta_a, stride, torch.float32)
+    err = np.abs(y32.cpu().numpy().astype(np.float64) - want)
+    print('f32', H, W, C, stride, beta_a, float((err / mag).max()))
+    assert np.all(err <= 1e-5 * mag), (beta_a, float((err / mag).max()))
+    assert torch.equal(y32, _run(hip, c, p, alpha_a, beta_a, stride, torch.float32))
+    y16 = _run(hip, c, p, alpha_a, beta_a, stride, torch.bfloat16)
+    err = np.abs(y16.float().cpu().numpy().astype(np.float64) - want)
+    bar = 1e-5 * mag + 2.0 ** -8 * np.abs(want)
+    print('bf16', H, W, C, stride, beta_a, float((err / bar).max()))
+    assert np.all(err <= bar), (beta_a, float((err / bar).max()))
+    assert torch.equal(y16, _run(hip, c, p, alpha_a, beta_a, stride, torch.bfloat16))
+
+
+def test_entry_point_rejects_what_it_does_not_cover(hip):
+  """C = 24, stride 3 and a null pointer return non-zero from the C entry and leave a canary-filled output untouched; k = 5 is refused
+  by the predicate (the forward entry is 3 x 3 only and takes no k)."""
+  H = W = 6
+  lib = hip._lib
+
+  def call(x, wcol, wsb, ab, y, C, stride):
+    ptr = lambda t: c_void_p(0 if t is None else t.data_ptr())
+    return lib.pf_dw_i8_fwd(ptr(x), ptr(wcol), ptr(wsb), ptr(ab), c_int(8), ptr(y), c_int(hip.PF_F32), c_int(B), c_int(H), c_int(W),
+                            c_int(C), c_int(stride), c_int(1), c_int(1), c_int(H), c_int(W), c_void_p(0))
+  x = torch.zeros((B, H, W, 48), dtype=torch.uint8, device='cuda')
+  wcol = torch.zeros((48, 3), dtype=torch.int32, device='cuda')
+  wsb = torch.ones(2, device='cuda')
+  ab = torch.tensor([1.0, 0.0], device='cuda')
+  y = torch.full((B, H, W, 48), 12345.0, device='cuda')
+  assert call(x, wcol, wsb, ab, y, 24, 1) != 0
+  assert call(x, wcol, wsb, ab, y, 16, 3) != 0
+  assert not hip.dw_i8_supported(16, 5, 1) and not hip.dw_i8_supported(24, 3, 1) and not hip.dw_i8_supported(16, 3, 3)
+  for args in ((None, wcol, wsb, ab, y), (x, None, wsb, ab, y), (x, wcol, None, ab, y), (x, wcol, wsb, None, y), (x, wcol, wsb, ab, None)):
+    assert call(*args, 16, 1) != 0
+  torch.cuda.synchronize()
+  assert bool((y == 12345.0).all())
+  with pytest.raises(ValueError, match='not eligible'):
+    hip.dw_i8_fwd(x, wcol, wsb, ab, 8, y, B, H, W, 24, 1, 1, 1, H, W)
+  with pytest.raises(TypeError):
+    hip.dw_i8_fwd(x.float(), wcol, wsb, ab, 8, y, B, H, W, 48, 1, 1, 1, H, W)
+  assert call(x, wcol, wsb, ab, y, 48, 1) == 0                       # the same call with nothing wrong is taken
+  torch.cuda.synchronize()
+  assert bool((y == 0.0).all())

@@ -2,9 +2,12 @@
 checkpoint goes through the UniformQuantLearner (8-bit weights in channel buckets, 8-bit activations) and
 tools/conversion/export_quant_int8_model.py, then tools/benchmark/calc_inference_time runs on the artefact with --int8 off | auto | on,
 B = 256 / 224 x 224, bf16, in ROUNDS alternating rounds inside one process.  Prints every run and, per route, the median and the
-spread (max - min) over the rounds.
+spread (max - min) over the rounds.  NET=mobilenet does the same for MobileNet-v1 1.0 with the routes --int8 off, --int8 on,
+--int8 on --int8_depthwise on (the depthwise layers on pf_dw_i8_fwd as well) and --int8 auto --int8_depthwise auto (what
+graph.int8_pays and graph.int8_dw_pays accept).
 
   python tools/gpu/int8_inference_time.py > profiles/int8_inference_time.txt
+  NET=mobilenet python tools/gpu/int8_inference_time.py > profiles/int8_mobilenet_inference_time.txt
 """
 import io
 import json
@@ -21,11 +24,15 @@ B = int(os.environ.get('B', 256))
 IMAGE = int(os.environ.get('IMAGE', 224))
 ROUNDS = int(os.environ.get('ROUNDS', 3))
 REPTS = int(os.environ.get('REPTS', 20))
+NET = os.environ.get('NET', 'resnet50')
 
 
 def main():
   from pocketflow_amd.flags import FLAGS
-  import pocketflow_amd.nets.resnet_at_ilsvrc12 as net
+  if NET == 'mobilenet':
+    import pocketflow_amd.nets.mobilenet_at_ilsvrc12 as net
+  else:
+    import pocketflow_amd.nets.resnet_at_ilsvrc12 as net
   from pocketflow_amd.learners.learner_utils import create_synthetic_checkpoint
   from pocketflow_amd.learners.uniform_quantization.learner import UniformQuantLearner
   from pocketflow_amd.tools.benchmark import calc_inference_time as T
@@ -34,7 +41,16 @@ def main():
   with tempfile.TemporaryDirectory() as tmp:
     FLAGS.save_path = os.path.join(tmp, 'models', 'model.ckpt')
     FLAGS.uql_save_quant_model_path = os.path.join(tmp, 'uql', 'model.ckpt')
-    FLAGS.resnet_size, FLAGS.nb_classes, FLAGS.image_size, FLAGS.batch_size = 50, 1001, IMAGE, 8
+    FLAGS.nb_classes, FLAGS.image_size, FLAGS.batch_size = 1001, IMAGE, 8
+    if NET == 'mobilenet':
+      FLAGS.mobilenet_version, FLAGS.mobilenet_depth_mult = 1, 1.0
+      net_args, title = ['--net', 'mobilenet_at_ilsvrc12', '--mobilenet_depth_mult', '1.0'], 'MobileNet-v1 1.0'
+      routes = [('off', ['--int8', 'off']), ('on', ['--int8', 'on', '--int8_depthwise', 'off']),
+                ('on+dw', ['--int8', 'on', '--int8_depthwise', 'on']), ('auto+dw', ['--int8', 'auto', '--int8_depthwise', 'auto'])]
+    else:
+      FLAGS.resnet_size = 50
+      net_args, title = ['--net', 'resnet_at_ilsvrc12', '--resnet_size', '50'], 'ResNet-50'
+      routes = [(mode, ['--int8', mode]) for mode in ('off', 'auto', 'on')]
     FLAGS.compute_dtype, FLAGS.synthetic_pool = 'bfloat16', 2
     FLAGS.uql_weight_bits = FLAGS.uql_activation_bits = 8
     FLAGS.uql_use_buckets, FLAGS.uql_bucket_type = True, 'channel'
@@ -46,25 +62,25 @@ def main():
     E.export_from_learner(learner, path)
     del learner
     torch.cuda.empty_cache()
-    common = ['--net', 'resnet_at_ilsvrc12', '--resnet_size', '50', '--nb_classes', '1001', '--image_size', str(IMAGE), '--batch_size', str(B),
+    common = net_args + ['--nb_classes', '1001', '--image_size', str(IMAGE), '--batch_size', str(B),
               '--compute_dtype', 'bfloat16', '--nb_repts_warmup', '5', '--nb_repts', str(REPTS), '--json', '--model_file', path,
               '--uql_activation_bits', '8']
-    print('# ResNet-50, B = %d, %d x %d, bf16, w8 (channel buckets) / a8; %d passes per run after 5 warm-up passes; %d alternating rounds'
-          % (B, IMAGE, IMAGE, REPTS, ROUNDS))
-    ms = {'off': [], 'auto': [], 'on': []}
+    print('# %s, B = %d, %d x %d, bf16, w8 (channel buckets) / a8; %d passes per run after 5 warm-up passes; %d alternating rounds'
+          % (title, B, IMAGE, IMAGE, REPTS, ROUNDS))
+    ms = {mode: [] for mode, _ in routes}
     for rnd in range(ROUNDS):
-      for mode in ('off', 'auto', 'on'):
+      for mode, args in routes:
         buf = io.StringIO()
         with redirect_stdout(buf):
-          T.main(common + ['--int8', mode])
+          T.main(common + args)
         line = json.loads([ln for ln in buf.getvalue().splitlines() if ln.startswith('{')][-1])
         ms[mode].append(line['ms_per_batch'])
-        print('round %d  --int8 %-4s  %9.3f ms per batch  nb_int8_layers %3d (%d ran)'
+        print('round %d  --int8 %-7s  %9.3f ms per batch  nb_int8_layers %3d (%d ran)'
               % (rnd, mode, line['ms_per_batch'], line['nb_int8_layers'], line['nb_int8_layers_ran']))
         torch.cuda.empty_cache()
-    for mode in ('off', 'auto', 'on'):
+    for mode, _ in routes:
       v = sorted(ms[mode])
-      print('--int8 %-4s  median %9.3f ms  spread %7.3f ms  (off / this %.3f)'
+      print('--int8 %-7s  median %9.3f ms  spread %7.3f ms  (off / this %.3f)'
             % (mode, v[len(v) // 2], v[-1] - v[0], sorted(ms['off'])[len(v) // 2] / v[len(v) // 2]))
 
 
