@@ -50,7 +50,7 @@ def _close(got, ref, what, scale=None, frac_tol=0.0):
   err = (got - ref).abs()
   mag = ref.abs() if scale is None else torch.maximum(ref.abs(), scale.float().abs())
   tol = mag * 2 ** -7 + 2e-2 * float(ref.abs().mean() + 1e-6)
-  bad = float((err > tol).float().mean())
+  bad = float((~(err <= tol)).float().mean())             # not `err > tol`: a NaN in the output compares false either way
   assert bad <= frac_tol, '%s: %.3e of the elements differ by more than a bf16 ulp (max err %.3e, mean |ref| %.3e)' % (
       what, bad, float(err.max()), float(ref.abs().mean()))
 

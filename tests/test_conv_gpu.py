@@ -27,7 +27,7 @@ def _close_bf16(got, ref, frac_tol=0.0, what='', scale=None):
   err = (got - ref).abs()
   mag = ref.abs() if scale is None else torch.maximum(ref.abs(), scale.float().abs())
   tol = mag * 2 ** -7 + 1e-3
-  bad = float((err > tol).float().mean())
+  bad = float((~(err <= tol)).float().mean())             # not `err > tol`: a NaN in the output compares false either way
   assert bad <= frac_tol, '%s: %.3e of the elements differ by more than a bf16 ulp (max err %.3e)' % (
       what, bad, float(err.max()))
 

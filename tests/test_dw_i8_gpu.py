@@ -16,6 +16,32 @@ pytestmark = pytest.mark.gpu
 B = 2
 # (H, W, C): the four small images at one and at three channel groups; 28 x 28 x 64 makes several workgroups, full strips and (stride 2) a tail
 CASES = [(H, W, C) for (H, W) in ((1, 1), (5, 7), (8, 6), (9, 4)) for C in (16, 48)] + [(28, 28, 64)]
+# C = 4080: 255 channel groups in a workgroup of 256 lanes, one strip per workgroup and one lane that leaves at `sl >= a.spb`
+CASES += [(9, 4, 4080)]
+# stride -> (H, W, C) with more strips than one pass of the capped grid covers: every lane of k_dw_i8 walks its `strip += gridDim.x * spb`
+# loop a second time, the second pass ragged; a one-pixel tail strip in every output row (Wo = 5).  21 M and 84 M codes: the narrow
+# image keeps the tensors small.
+LOOP_CASES = {1: (2060, 5, 1024), 2: (4110, 10, 1024)}
+
+
+def _strips_and_strips_per_pass(H, W, C, stride):
+  """The launcher's arithmetic (pf_dw_i8_fwd, pf_depthwise_i8.hip): strips of 4 output pixels in the tensor, and how many of them the
+  grid takes in one pass -- 256 lanes = cgb channel groups x spb strips, gridDim.x capped at 2048 / gridDim.y."""
+  Ho, Wo = -(-H // stride), -(-W // stride)
+  total = B * Ho * -(-Wo // 4)
+  cgb = min(C // 16, 256)
+  spb = 256 // cgb
+  gy = -(-(C // 16) // cgb)
+  gx = min(-(-total // spb), max(2048 // gy, 1))
+  return total, gx * spb
+
+
+def _check_grid(H, W, C, stride):
+  total, per_pass = _strips_and_strips_per_pass(H, W, C, stride)
+  if (H, W, C) == LOOP_CASES[stride]:
+    assert per_pass == 8192 and per_pass < total < 2 * per_pass and -(-W // stride) % 4 == 1
+  else:
+    assert total <= per_pass
 
 
 @pytest.fixture(scope='module')
@@ -53,16 +79,69 @@ def _ref(c, p, alpha_a, beta_a, stride):
   return int8.depthwise_reference(c, alpha_a, beta_a, 8, p['d'], p['alpha'], p['beta'], p['bits'], stride, terms=True)
 
 
+def _ref_on_device(c, p, alpha_a, beta_a, stride):
+  """int8.depthwise_reference line by line in torch on the device (int64 sums, float64 terms in the same order), for the LOOP_CASES:
+  numpy needs 3.6 s per call at 21 M outputs, two calls per test.  Elementwise IEEE float64 in the same order: the same bits, which
+  `ref_large` asserts on every shape of CASES before a test relies on it."""
+  B_, H, W, C = c.shape
+  (ph, ph1), (pw, pw1) = int8.same_pads(H, 3, stride), int8.same_pads(W, 3, stride)
+  Ho, Wo = -(-H // stride), -(-W // stride)
+  ka, kw = float(2 ** 8 - 1), float(2 ** p['bits'] - 1)
+  cp = torch.zeros((B_, H + ph + ph1, W + pw + pw1, C), dtype=torch.int64, device='cuda')
+  cp[:, ph:ph + H, pw:pw + W] = dev(c)
+  inside = torch.zeros((H + ph + ph1, W + pw + pw1), dtype=torch.int64, device='cuda')
+  inside[ph:ph + H, pw:pw + W] = 1
+  d64 = dev(p['d']).to(torch.int64)
+  P = torch.zeros((B_, Ho, Wo, C), dtype=torch.int64, device='cuda')
+  Sc = torch.zeros_like(P)
+  Dv = torch.zeros((Ho, Wo, C), dtype=torch.int64, device='cuda')
+  V = torch.zeros((Ho, Wo), dtype=torch.int64, device='cuda')
+  for r in range(3):
+    for s in range(3):
+      win = cp[:, r:r + (Ho - 1) * stride + 1:stride, s:s + (Wo - 1) * stride + 1:stride]
+      ok = inside[r:r + (Ho - 1) * stride + 1:stride, s:s + (Wo - 1) * stride + 1:stride]
+      P += win * d64[:, r, s]
+      Sc += win
+      Dv += ok[:, :, None] * d64[None, None, :, r, s]
+      V += ok
+  sa, sw, bw = float(alpha_a) / ka, float(p['alpha']) / kw, float(p['beta'])
+  t1 = (sa * sw) * P.double()
+  t2 = (sa * bw) * Sc.double()
+  t3a, t3b = float(beta_a) * (sw * Dv.double())[None], float(beta_a) * (bw * V.double()[..., None])[None]
+  y = t1 + t2 + (t3a + t3b)
+  mag = t1.abs() + t2.abs() + t3a.abs() + t3b.abs()
+  return y.cpu().numpy(), mag.cpu().numpy()
+
+
+@pytest.fixture(scope='module')
+def ref_large(hip):
+  """_ref_on_device, after it has reproduced int8.depthwise_reference exactly on every small shape, stride and kind of parameters."""
+  rng = np.random.default_rng(7)
+  for H, W, C in CASES:
+    c = rng.integers(0, 256, size=(B, H, W, C)).astype(np.uint8)
+    for stride in (1, 2):
+      for p, alpha_a, beta_a in ((_kernel(rng, C, 4, 15.0, -2.0), 255.0, 2.0), (_kernel(rng, C, 8, 0.37, -0.11), 3.3, 0.0),
+                                 (_kernel(rng, C, 8, 0.21, -0.05), float(np.float32(1.7)), float(np.float32(0.37)))):
+        for got, want in zip(_ref_on_device(c, p, alpha_a, beta_a, stride), _ref(c, p, alpha_a, beta_a, stride)):
+          assert got.dtype == want.dtype == np.float64 and np.array_equal(got, want), (H, W, C, stride, alpha_a, beta_a)
+  return _ref_on_device
+
+
+# every (H, W, C) of CASES at both strides (test ids as before), and the loop-entering shape of each stride
+PARAMS = [(H, W, C, stride) for stride in (1, 2) for (H, W, C) in CASES] + [LOOP_CASES[stride] + (stride,) for stride in (1, 2)]
+
+
 @pytest.mark.parametrize('beta_a', [0.0, 2.0])
-@pytest.mark.parametrize('stride', [1, 2])
-@pytest.mark.parametrize('H,W,C', CASES)
-def test_exact_case_is_bit_for_bit(hip, H, W, C, stride, beta_a):
+@pytest.mark.parametrize('H,W,C,stride', PARAMS)
+def test_exact_case_is_bit_for_bit(hip, ref_large, H, W, C, stride, beta_a):
   """alpha_a = 255 (step 1), alpha_w = 15 * 2^e over 4-bit codes (step 2^e), integer beta_w and beta_a: every term an integer < 2^24."""
+  _check_grid(H, W, C, stride)
+  ref = ref_large if (H, W, C) == LOOP_CASES[stride] else _ref
   rng = np.random.default_rng(1000 * H + 100 * W + C + stride)
   c = rng.integers(0, 256, size=(B, H, W, C)).astype(np.uint8)
   c.reshape(-1)[:2] = (0, 255)
   p = _kernel(rng, C, 4, 15.0 * 2.0 ** int(rng.integers(0, 2)), -float(rng.integers(1, 3)))
-  want, mag = _ref(c, p, 255.0, beta_a, stride)
+  want, mag = ref(c, p, 255.0, beta_a, stride)
   assert mag.max() < 2 ** 24 and np.array_equal(want, np.rint(want))
   got = _run(hip, c, p, 255.0, beta_a, stride, torch.float32).cpu().numpy()
   bad = np.argwhere(got != want.astype(np.float32))
@@ -71,17 +150,18 @@ def test_exact_case_is_bit_for_bit(hip, H, W, C, stride, beta_a):
   assert torch.equal(got16, torch.from_numpy(want.astype(np.float32)).to(torch.bfloat16))
 
 
-@pytest.mark.parametrize('stride', [1, 2])
-@pytest.mark.parametrize('H,W,C', CASES)
-def test_general_parameters_and_determinism(hip, H, W, C, stride):
+@pytest.mark.parametrize('H,W,C,stride', PARAMS)
+def test_general_parameters_and_determinism(hip, ref_large, H, W, C, stride):
   """float32 output within 1e-5 * sum |terms| of the reference (a few float32 ulps of the summed term magnitudes); bf16 output
   additionally 2^-8 |y| for its one rounding; two calls give the same bits."""
+  _check_grid(H, W, C, stride)
+  ref = ref_large if (H, W, C) == LOOP_CASES[stride] else _ref
   rng = np.random.default_rng(1000 * H + 100 * W + C * 7 + stride)
   c = rng.integers(0, 256, size=(B, H, W, C)).astype(np.uint8)
   p = _kernel(rng, C, 8, float(rng.uniform(0.05, 0.6)), -float(rng.uniform(0.02, 0.3)))
   alpha_a = float(np.float32(rng.uniform(1.0, 6.0)))
   for beta_a in (0.0, float(np.float32(0.37))):
-    want, mag = _ref(c, p, alpha_a, beta_a, stride)
+    want, mag = ref(c, p, alpha_a, beta_a, stride)
     y32 = _run(hip, c, p, alpha_a, beta_a, stride, torch.float32)
     err = np.abs(y32.cpu().numpy().astype(np.float64) - want)
     print('f32', H, W, C, stride, beta_a, float((err / mag).max()))
