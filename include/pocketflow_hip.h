@@ -514,6 +514,28 @@ int pf_dw_i8_supported(int C, int k, int stride);
 int pf_dw_i8_fwd(const uint8_t* x, const uint32_t* w_cols, const float* w_scale_beta, const float* act_alpha_beta, int act_bits, void* y,
                  int dtype, int B, int H, int W, int C, int stride, int pad_h, int pad_w, int Ho, int Wo, void* stream);
 
+/* ---- fixed (calibrated) activation ranges for int8 inference (pf_act_static.hip, pf_conv_i8_q.hip, pf_depthwise_i8_q.hip) ----------
+ * The static quantiser: t = ((u - beta) / alpha) * k, t = min(max(t, 0), k), level = rint(t), value = alpha * (level / k) + beta --
+ * the float32 chain of pf_bn_act_quant_apply / _codes plus ONE clamp in front of the rounding -- against out_alpha_beta[2], a DEVICE
+ * pair (alpha, beta) = ((max - min) + 1e-10f, min) of a range calibrated once; it is never read by the host and no slot is written.
+ * out_kind: 0 = uint8 levels (bits <= 8), 1 = the value in float32, 2 = the value in bf16.
+ * pf_bn_act_quant_static: out[rows][C] = the static quantiser of act(scale * x + shift), x float32 / bf16 (`dtype`); bits 1..32 for
+ *   values.  The 8-channel vector map where C % 8 == 0 and C / 8 divides 256 and the pointers are aligned, a scalar loop otherwise.
+ * pf_conv_i8_fwd_q / pf_dw_i8_fwd_q: pf_conv_i8_fwd / pf_dw_i8_fwd whose epilogue applies the ONE consumer's folded BatchNorm
+ *   (out_scale_shift [2][N or C], 16-byte aligned), activation and static quantiser (out_bits <= 8) to the float32 output and stores
+ *   `out_kind`: bit for bit pf_bn_act_quant_static applied to the float32 output of the parent entry.  pf_conv_i8_fwd_q refuses a
+ *   residual (res must be NULL).  All three return non-zero without launching for a null pointer, an unknown out_kind or a shape
+ *   their parent rejects.  Deterministic. */
+int pf_bn_act_quant_static(const void* x, void* out, int dtype, int out_kind, int64_t rows, int C, const float* scale_shift, int act,
+                           const float* out_alpha_beta, int bits, void* stream);
+int pf_conv_i8_fwd_q(const uint8_t* x, const int8_t* w, const float* act_alpha_beta, int act_bits, const float* w_scale_beta,
+                     const int32_t* w_tsum, const int32_t* w_tapsum, const void* res, const float* out_scale_shift, int out_act,
+                     const float* out_alpha_beta, int out_bits, void* out, int out_kind, int imgs, int H, int W, int C, int N, int R,
+                     int S, int stride, int pad_h, int pad_w, int Ho, int Wo, void* stream);
+int pf_dw_i8_fwd_q(const uint8_t* x, const uint32_t* w_cols, const float* w_scale_beta, const float* act_alpha_beta, int act_bits,
+                   const float* out_scale_shift, int out_act, const float* out_alpha_beta, int out_bits, void* out, int out_kind, int B,
+                   int H, int W, int C, int stride, int pad_h, int pad_w, int Ho, int Wo, void* stream);
+
 /* ---- R x S convolutions with few input channels (ResNet-20 @ CIFAR-10: resnet_model.py:156-199 with 16 / 32 filters) --------------
  * bf16, C % 8 == 0.  pf_im2col gathers Xcol[imgs*Ho*Wo][R*S*C] (taps outside the image: zeros) so that the convolution and its two
  * gradients are 1x1 products on pf_conv1x1_fwd / pf_conv1x1_wrw over Xcol and the [N][R*S*C] view of the KRSC kernel; pf_col2im is

@@ -389,6 +389,12 @@ class Graph:
     self.int8 = False
     self.nb_int8 = 0
     self.int8_ran: set = set()
+    # fixed activation ranges (inference.load_int8(act_ranges='static')): every slot decoded ONCE to (alpha, beta) rows on the device.
+    # Quantising BatchNormAct / Activation layers then quantise against their row with the clamping kernels (pf_act_static.hip) and
+    # never touch the slots; a packed layer whose consumer BatchNormAct quantises applies it in its own epilogue (`requant_ran`).
+    self.act_static: Optional[torch.Tensor] = None
+    self.requant_ran: set = set()
+    self._identity_ss: Dict[int, torch.Tensor] = {}
     self.conv_layers: List = []                # every Conv2D of the graph, in creation order (the loader finds a kernel's layer here)
     self.depthwise_layers: List = []           # every DepthwiseConv2D, likewise
 
@@ -471,6 +477,13 @@ class Graph:
 
   def act_alpha_beta(self) -> torch.Tensor:
     return hip.minmax_decode(self.act_slots)
+
+  def identity_scale_shift(self, C: int) -> torch.Tensor:
+    """scale 1 / shift 0 as a [2][C] float32 pair: a stand-alone activation as the BN -> act -> quant pass sees it (fmaf(1, x, 0) = x)."""
+    ss = self._identity_ss.get(C)
+    if ss is None:
+      ss = self._identity_ss[C] = torch.cat([torch.ones(C, dtype=torch.float32), torch.zeros(C, dtype=torch.float32)]).view(2, C).to(self.device)
+    return ss
 
   def zero_row(self, C: int) -> torch.Tensor:
     """A float32 zero vector: the pivot row of BN statistics that were accumulated un-shifted."""
@@ -799,6 +812,44 @@ class CodesAct(LazyAct):
       with region('bn_act_quant_codes', float(x.numel() * (x.element_size() + 1))):
         hip.bn_act_quant_codes(x, self._codes, self.rows, self.C, self.scale_shift, self.act, self.slot, self.bits, self.alpha_beta)
     return self._codes, self.alpha_beta
+
+
+class StaticCodesAct(CodesAct):
+  """CodesAct on a graph with fixed activation ranges (`graph.act_static`): `alpha_beta` is the layer's row of that tensor, there is no
+  slot, and both forms come from the clamping pass pf_bn_act_quant_static.  Built either from the raw tensor `x` of a BatchNormAct
+  (codes / values made on demand, one launch each, cached) or from the CODES a requantising producer wrote (`codes=`; x is None):
+  then `materialize()` decodes them, alpha * (code / k) + beta in float32 and one rounding to `dtype` -- a cold path, for a consumer
+  that refuses the codes at call time."""
+
+  def __init__(self, x, scale_shift, act, alpha_beta, bits, rows, C, codes=None, dtype=None):
+    super(StaticCodesAct, self).__init__(x if x is not None else codes, scale_shift, act, None, bits, rows, C)
+    self._raw, self._codes, self.alpha_beta = x, codes, alpha_beta
+    self._dtype = dtype if dtype is not None else x.dtype
+
+  @property
+  def dtype(self):
+    return self._dtype
+
+  def codes(self):
+    if self._codes is None:
+      x = self._raw
+      self._codes = torch.empty(x.shape, dtype=torch.uint8, device=x.device, memory_format=torch.channels_last)
+      with region('bn_act_quant_static', float(x.numel() * (x.element_size() + 1))):
+        hip.bn_act_quant_static(x, self._codes, self.rows, self.C, self.scale_shift, self.act, self.alpha_beta, self.bits)
+    return self._codes, self.alpha_beta
+
+  def materialize(self) -> torch.Tensor:
+    if self._q is None:
+      x = self._raw
+      if x is not None:
+        self._q = torch.empty_like(x)
+        with region('bn_act_quant_static', float(2 * x.numel() * x.element_size())):
+          hip.bn_act_quant_static(x, self._q, self.rows, self.C, self.scale_shift, self.act, self.alpha_beta, self.bits)
+      else:
+        k = float(2 ** self.bits - 1)
+        ab = self.alpha_beta
+        self._q = (ab[0] * (self._codes.float() / k) + ab[1]).to(self._dtype).contiguous(memory_format=torch.channels_last)
+    return self._q
 
 
 class _Materialize(torch.autograd.Function):
@@ -1617,6 +1668,41 @@ def int8_dw_pays(C: int, stride: int, dtype) -> bool:
 _INT8_DW_PAYS = frozenset([(32, 1), (64, 2), (128, 1), (128, 2), (256, 1), (256, 2), (512, 1), (512, 2), (1024, 1)])
 
 
+def int8_pays_static(k: int, cin: int, cout: int, stride: int, dtype) -> bool:
+  """`int8_pays` for a graph with FIXED activation ranges (inference.load_int8(act_ranges='static')): should a loader send an eligible
+  Conv2D to the kernels on codes, where pf_conv_i8_fwd_q also applies the BatchNorm + activation + quantiser behind the layer?
+
+  The STATIC table of profiles/int8_conv_layers.txt (tools/gpu/int8_conv_layers.py with STATIC=1: every eligible ResNet-50 convolution
+  and every MobileNet-v1 pointwise convolution at B = 256 / 224 x 224, bf16, three alternating rounds; float = the bf16 kernel +
+  pf_bn_act_quant_static writing the consumer's codes, int8 = pf_conv_i8_fwd_q, codes in and codes out): the route on codes loses on
+  every row but one, float / int8 0.60 - 0.81 (ResNet-50 summed 5.22 against 7.37 ms, MobileNet 1.09 against 1.63 ms) -- the epilogue
+  removed the static pass from the int8 side, but pf_conv_i8_fwd itself is the slower kernel.  It wins on the 256 -> 64 1x1 convolution
+  at 56 x 56 (134.9 against 123.7 us, spreads 1.2 / 0.3 us), the row `int8_pays` accepts too.  Whole model
+  (profiles/int8_static_inference_time.txt): ResNet-50 with that layer on codes 6.578 ms against 6.696 ms on the float kernels (both
+  with static ranges), every eligible layer on codes 9.88 ms.  True for exactly that shape in bf16; float32 has not been timed."""
+  return dtype == torch.bfloat16 and (k, cin, cout, stride) in _INT8_PAYS_STATIC
+
+
+def int8_dw_pays_static(C: int, stride: int, dtype) -> bool:
+  """`int8_dw_pays` for a graph with FIXED activation ranges: pf_dw_i8_fwd_q (codes in, the consumer's codes out) against
+  pf_depthwise_fwd plus the static pass.
+
+  The STATIC table of profiles/int8_depthwise_layers.txt (tools/gpu/int8_depthwise_layers.py with STATIC=1: the 13 depthwise shapes of
+  MobileNet-v1 1.0 at B = 256 / 224 x 224, bf16, three alternating rounds; float = pf_depthwise_fwd + pf_bn_act_quant_static writing
+  the consumer's codes, int8 = pf_dw_i8_fwd_q): the route on codes wins on EVERY row, float / int8 1.80 - 2.99 with spreads of at most
+  4.0 us on rows of 15 - 228 us (summed over one pass 1.36 against 0.70 ms).  Whole model (profiles/int8_static_inference_time.txt):
+  the 13 depthwise layers on codes and the pointwise layers on the bf16 kernels take 2.289 ms per batch against 2.877 ms with static
+  ranges on the float kernels and 3.149 ms on the best per-batch route.  True for exactly the nine measured (C, stride) pairs in
+  bf16; float32 and other widths have not been timed."""
+  return dtype == torch.bfloat16 and (C, stride) in _INT8_DW_PAYS_STATIC
+
+
+# (k, cin, cout, stride) / (C, stride) of the rows of the STATIC tables of profiles/int8_conv_layers.txt and
+# profiles/int8_depthwise_layers.txt on which the route on codes won by more than the spread
+_INT8_PAYS_STATIC = frozenset([(1, 256, 64, 1)])
+_INT8_DW_PAYS_STATIC = frozenset([(32, 1), (64, 2), (128, 1), (128, 2), (256, 1), (256, 2), (512, 1), (512, 2), (1024, 1)])
+
+
 class Conv2D:
   """tf.layers.conv2d / slim.conv2d: NHWC, kernel HWIO (stored KRSC), padding 'SAME' | 'VALID'."""
 
@@ -1639,6 +1725,8 @@ class Conv2D:
     consumer is that BatchNormAct in inference mode (`out_bn.folds_into_producer()`): the MFMA kernels apply it in their
     epilogue and tag the output, which the layer then passes through; any other route ignores the hint."""
     w = self.kernel.tensor
+    # fixed activation ranges: a quantising consumer BatchNormAct goes into the epilogue of the kernel on codes (_call_int8) alone
+    requant = out_bn if (out_bn is not None and residual is None and out_bn.requantises()) else None
     if out_bn is not None and (residual is not None or not out_bn.folds_into_producer()):
       out_bn = None
     if self.graph.taps is not None:
@@ -1650,7 +1738,7 @@ class Conv2D:
                          'finalised with requires_grad=False' % self.kernel.name)
     if isinstance(x, CodesAct):
       if self.int8 is not None and self._int8_geometry(x.x) is not None:
-        return self._call_int8(x, residual)
+        return self._call_int8(x, residual, requant)
       x = x.materialize()                        # every other consumer: the fake-quantised tensor of the apply pass, as without int8
     if fused_conv1x1_ok(x, self):                # 1x1 on pf_conv.hip: the producer BN's normalise / act / fake-quant in the prologue
       lazy = x if isinstance(x, LazyAct) else None
@@ -1742,6 +1830,12 @@ class Conv2D:
       y._pf_bn_done = out_bn
     return y
 
+  def takes_codes(self, shape, is_cuda: bool) -> bool:
+    """This layer will multiply the CODES of an input of this NCHW shape: it is packed, and no route ahead of the int8 kernel in
+    __call__ (taps, a gather) takes the call."""
+    return (self.int8 is not None and self.graph.taps is None and self.kernel.gather_host is None
+            and self._int8_geometry(_ShapeOnly(tuple(shape), is_cuda)) is not None)
+
   def _int8_geometry(self, x):
     """(pad_h, pad_w, Ho, Wo) where pf_conv_i8_fwd takes this layer on the input x, else None: symmetric pads only (it has no padded
     copy to fall back on), no bias, a 4-D device tensor."""
@@ -1752,14 +1846,25 @@ class Conv2D:
       return None
     return ph[0], pw[0], Ho, Wo
 
-  def _call_int8(self, x: 'CodesAct', residual) -> torch.Tensor:
+  def _call_int8(self, x: 'CodesAct', residual, requant=None) -> torch.Tensor:
     """The packed layer on the i8 matrix cores: the producer's codes times the signed weights, scales and offsets in the epilogue
-    (pocketflow_amd/int8.py states the formula), the residual added before the one rounding to the compute dtype."""
+    (pocketflow_amd/int8.py states the formula), the residual added before the one rounding to the compute dtype.  `requant`: the
+    quantising BatchNormAct that alone consumes the output, on a graph with fixed ranges: applied in the epilogue (pf_conv_i8_fwd_q),
+    the output being that layer's output -- codes where ITS consumer multiplies codes, the fake-quantised tensor otherwise."""
     p = self.int8
     pad_h, pad_w, Ho, Wo = self._int8_geometry(x.x)
     codes, ab = x.codes()
     B, C, H, Wd = codes.shape
     N = self.kernel.ref_shape[3]
+    if requant is not None:
+      ss, oab, as_codes = requant.requant_plan((B, N, Ho, Wo), codes.is_cuda)
+      out = torch.empty((B, N, Ho, Wo), dtype=torch.uint8 if as_codes else x.dtype, device=codes.device, memory_format=torch.channels_last)
+      with region('conv_i8_fwd_q', float(codes.numel() + out.numel() * out.element_size())):
+        hip.conv_i8_fwd_q(codes, p['w'], ab, x.bits, p['scale_beta'], p['tsum'], p['tapsum'], ss, requant.act, oab, requant.op.bits, out,
+                          B, H, Wd, C, N, self.k, self.k, self.stride, pad_h, pad_w, Ho, Wo)
+      self.graph.int8_ran.add(self.kernel.name)
+      self.graph.requant_ran.add(self.kernel.name)
+      return requant.requant_result(out, ss, oab, x.dtype)
     y = torch.empty((B, N, Ho, Wo), dtype=x.dtype, device=codes.device, memory_format=torch.channels_last)
     res = None if residual is None else _nhwc(residual).to(y.dtype)
     with region('conv_i8_fwd', float(codes.numel() + y.numel() * y.element_size() * (2 if res is not None else 1))):
@@ -1776,6 +1881,16 @@ class Conv2D:
       return self(x)
     finally:
       self.graph.taps, self.graph.fuse_conv1x1 = taps, fuse
+
+
+class _ShapeOnly(object):
+  """What the geometry checks read of a tensor, for a tensor that does not exist yet."""
+
+  def __init__(self, shape, is_cuda):
+    self.shape, self.is_cuda = shape, is_cuda
+
+  def dim(self):
+    return len(self.shape)
 
 
 class TapStop(Exception):
@@ -1872,14 +1987,20 @@ class DepthwiseConv2D:
     finally:
       self.graph.taps = taps
 
-  def __call__(self, x, want_stats: bool = False) -> torch.Tensor:
-    """`want_stats`: the consumer is a BatchNormAct -- leave the per-channel statistics of the output on the tensor."""
+  def takes_codes(self, shape, is_cuda: bool) -> bool:
+    """This layer will multiply the CODES of an input of this NCHW shape (the test of __call__ below)."""
+    return self.int8 is not None and self.graph.taps is None and len(shape) == 4 and bool(is_cuda) and shape[1] == self.channels
+
+  def __call__(self, x, want_stats: bool = False, out_bn=None) -> torch.Tensor:
+    """`want_stats`: the consumer is a BatchNormAct -- leave the per-channel statistics of the output on the tensor.  `out_bn`: the
+    ONLY consumer is that BatchNormAct; on a graph with fixed activation ranges the packed layer applies it in its epilogue
+    (pf_dw_i8_fwd_q), any other route ignores the hint."""
     if self.int8 is not None and self.graph.taps is None:
       if torch.is_grad_enabled() and (self.kernel.tensor.requires_grad or (x.x if isinstance(x, LazyAct) else x).requires_grad):
         raise RuntimeError('%s: a depthwise convolution packed for int8 runs in inference only: call it under torch.no_grad() on a '
                            'graph finalised with requires_grad=False' % self.kernel.name)
       if isinstance(x, CodesAct) and x.x.dim() == 4 and x.x.is_cuda and x.x.shape[1] == self.channels:
-        return self._call_int8(x)
+        return self._call_int8(x, out_bn if (out_bn is not None and out_bn.requantises()) else None)
     x = materialize(x)                           # a CodesAct too: the fake-quantised tensor of the apply pass, as without int8
     if self.graph.taps is not None:
       return _tapped(self, x)
@@ -1898,15 +2019,24 @@ class DepthwiseConv2D:
     x, pad = _symmetric_pads(x, ph, pw)
     return F.conv2d(x, self.kernel.tensor, None, stride=self.stride, padding=pad, groups=self.channels)
 
-  def _call_int8(self, x: 'CodesAct') -> torch.Tensor:
+  def _call_int8(self, x: 'CodesAct', requant=None) -> torch.Tensor:
     """The packed layer on pf_dw_i8_fwd: the producer's codes times the kernel's codes in integers, scales and offsets in the epilogue
     (pocketflow_amd/int8.py states the formula), one rounding to the compute dtype.  The BatchNorm behind it makes its own statistics
-    pass (the output carries none)."""
+    pass (the output carries none).  `requant`: as in Conv2D._call_int8 (pf_dw_i8_fwd_q)."""
     p = self.int8
     codes, ab = x.codes()
     B, C, H, Wd = codes.shape
     ph, pw = _same_pads(H, self.k, self.stride), _same_pads(Wd, self.k, self.stride)
     Ho, Wo = -(-H // self.stride), -(-Wd // self.stride)
+    if requant is not None:
+      ss, oab, as_codes = requant.requant_plan((B, C, Ho, Wo), codes.is_cuda)
+      out = torch.empty((B, C, Ho, Wo), dtype=torch.uint8 if as_codes else x.dtype, device=codes.device, memory_format=torch.channels_last)
+      with region('dw_i8_fwd_q', float(codes.numel() + out.numel() * out.element_size())):
+        hip.dw_i8_fwd_q(codes, p['wcol'], p['scale_beta'], ab, x.bits, ss, requant.act, oab, requant.op.bits, out, B, H, Wd, C, self.stride,
+                        ph[0], pw[0], Ho, Wo)
+      self.graph.int8_ran.add(self.kernel.name)
+      self.graph.requant_ran.add(self.kernel.name)
+      return requant.requant_result(out, ss, oab, x.dtype)
     y = torch.empty((B, C, Ho, Wo), dtype=x.dtype, device=codes.device, memory_format=torch.channels_last)
     with region('dw_i8_fwd', float(codes.numel() + y.numel() * y.element_size())):
       hip.dw_i8_fwd(codes, p['wcol'], p['scale_beta'], ab, x.bits, y, B, H, Wd, C, self.stride, ph[0], pw[0], Ho, Wo)
@@ -1962,6 +2092,14 @@ class Activation:
     if self.op.bits is None:
       y = F.relu(x) if self.act == 'Relu' else F.relu6(x)
       return _pass_tag(x, y) if g.taps is not None else y
+    if g.act_static is not None and not torch.is_grad_enabled():
+      # fixed range: the clamping pass with scale 1 / shift 0 over [rows][C] of any rank (a Dense output is [B][C]); the slot is
+      # not touched
+      x = _nhwc(x)
+      C = x.shape[1] if x.dim() > 1 else x.numel()
+      y = torch.empty_like(x)
+      hip.bn_act_quant_static(x, y, x.numel() // C, C, g.identity_scale_shift(C), self.act, g.act_static[self.op.index], self.op.bits)
+      return y
     return _ActQuant.apply(x, self.act, g.act_slots[self.op.index], self.op.bits)
 
 
@@ -1990,6 +2128,34 @@ class BatchNormAct:
                              constant_init((channels,), 1.0))
     self.op = graph.add_activation_op(act, act_name or (name + '/' + act)) if act else None
     self._frozen_ss = None
+    # the ONE layer that reads this layer's output, where the network code names it (None: not named, or more than one): a packed
+    # producer that requantises for this layer writes codes exactly when that consumer multiplies codes
+    self.consumer = None
+
+  def _static(self) -> bool:
+    """Inference on a graph with fixed activation ranges, this layer quantising: the clamping kernels, no statistics pass."""
+    g = self.graph
+    return (g.act_static is not None and self.op is not None and self.op.bits is not None and g.taps is None
+            and not (g.training and torch.is_grad_enabled())
+            and not (torch.is_grad_enabled() and not g.frozen))
+
+  def requantises(self) -> bool:
+    """A packed producer may apply this layer in its epilogue: fixed ranges, at most 8 bits, no gradients."""
+    return self._static() and self.op.bits <= 8 and not torch.is_grad_enabled()
+
+  def requant_plan(self, shape, is_cuda: bool):
+    """(scale_shift, alpha_beta row, write codes?) for a producer that applies this layer to an output of NCHW `shape`."""
+    ss = self._eval_scale_shift(self.gamma.tensor)
+    as_codes = bool(self.graph.int8 and self.codes_ok and self.consumer is not None and self.consumer.takes_codes(shape, is_cuda))
+    return ss, self.graph.act_static[self.op.index], as_codes
+
+  def requant_result(self, out, ss, oab, dtype):
+    """What the producer returns: this layer's output, marked as already applied (__call__ passes it through)."""
+    if out.dtype == torch.uint8:
+      C = self.C
+      out = StaticCodesAct(None, ss, self.act, oab, self.op.bits, out.numel() // C, C, codes=out, dtype=dtype)
+    out._pf_bn_done = self
+    return out
 
   def folds_into_producer(self) -> bool:
     """This layer, in inference mode and without a quantiser (the distillation teacher's forward_eval; evaluation of a
@@ -2009,7 +2175,7 @@ class BatchNormAct:
     g = self.graph
     bits = self.op.bits if self.op is not None else None
     slot = g.act_slots[self.op.index] if (self.op is not None and bits is not None) else None
-    lazy = self.lazy_ok and g.fuse_conv1x1 and fusable_tensor(x)
+    lazy = self.lazy_ok and g.fuse_conv1x1 and isinstance(x, torch.Tensor) and fusable_tensor(x)
     skip = x
     if getattr(x, '_pf_bn_done', None) is self:   # applied in the epilogue of the producing convolution (Conv2D `out_bn`)
       y = x
@@ -2041,6 +2207,8 @@ class BatchNormAct:
     g = self.graph
     if not head_fuse_ok(g, x) or x.dim() != 4 or getattr(x, '_pf_bn_done', None) is self:
       return None
+    if self._static():
+      return None                                 # pf_bn_act_quant_pool has no clamp: the separate chain through the static pass
     bits = self.op.bits if self.op is not None else None
     slot = g.act_slots[self.op.index] if (self.op is not None and bits is not None) else None
     if g.training and torch.is_grad_enabled():
@@ -2066,6 +2234,13 @@ class BatchNormAct:
     rows = x.numel() // C
     if bits is None and lazy:
       return LazyAct(x, self._eval_scale_shift(x), self.act, None, None, rows, C)
+    if bits is not None and self._static():
+      ss, ab = self._eval_scale_shift(x), self.graph.act_static[self.op.index]
+      if bits <= 8 and self.graph.int8 and self.codes_ok and x.is_cuda and x.dim() == 4:
+        return StaticCodesAct(x, ss, self.act, ab, bits, rows, C)
+      q = torch.empty_like(x)
+      hip.bn_act_quant_static(x, q, rows, C, ss, self.act, ab, bits)
+      return q
     if bits is not None and bits <= 8 and self.graph.int8 and self.codes_ok and x.is_cuda and x.dim() == 4:
       return CodesAct(x, self._calibrated_scale_shift(x, slot), self.act, slot, bits, rows, C)
     q = torch.empty_like(x)

@@ -58,6 +58,7 @@ SYMBOLS = [
     'pf_bn_act_quant_pool', 'pf_bn_bwd_stats_pooled', 'pf_bn_bwd_apply_pooled', 'pf_ce_distill_head', 'pf_ce_combine',
     'pf_bn_act_quant_codes', 'pf_conv_i8_supported', 'pf_conv_i8_fwd',
     'pf_dw_i8_supported', 'pf_dw_i8_fwd',
+    'pf_bn_act_quant_static', 'pf_conv_i8_fwd_q', 'pf_dw_i8_fwd_q',
 ]
 
 
@@ -812,6 +813,85 @@ def dw_i8_fwd(X, w_cols, w_scale_beta, alpha_beta, act_bits: int, Y, B: int, H: 
   _check(_lib.pf_dw_i8_fwd(_ptr(X), _ptr(w_cols), _ptr(w_scale_beta), _ptr(alpha_beta), c_int(int(act_bits)), _ptr(Y),
                            c_int(dtype_code(Y)), c_int(B), c_int(H), c_int(Wd), c_int(C), c_int(stride), c_int(pad_h), c_int(pad_w),
                            c_int(Ho), c_int(Wo), _stream()), 'pf_dw_i8_fwd')
+
+
+# fixed activation ranges (pf_act_static.hip, pf_conv_i8_q.hip, pf_depthwise_i8_q.hip): the static, clamping quantiser
+OUT_CODES, OUT_F32, OUT_BF16 = 0, 1, 2
+
+
+def out_kind_of(t: torch.Tensor) -> int:
+  """What a static-quantiser entry stores into `t`: uint8 = codes, float32 / bfloat16 = the fake-quantised value."""
+  if t.dtype == torch.uint8:
+    return OUT_CODES
+  if t.dtype == torch.float32:
+    return OUT_F32
+  if t.dtype == torch.bfloat16:
+    return OUT_BF16
+  raise TypeError('static quantiser output is uint8, float32 or bfloat16 (got %s)' % t.dtype)
+
+
+def _static_operands(what: str, out, scale_shift, out_alpha_beta, n_out: int, C: int, bits: int) -> int:
+  kind = out_kind_of(out)
+  if scale_shift.dtype != torch.float32 or out_alpha_beta.dtype != torch.float32:
+    raise TypeError('%s: scale_shift and out_alpha_beta are float32' % what)
+  if out.numel() != n_out or scale_shift.numel() != 2 * C or out_alpha_beta.numel() < 2 or not 1 <= int(bits) <= (8 if kind == OUT_CODES else 32):
+    raise ValueError('%s: operand sizes do not match (%d outputs, C=%d, bits=%d)' % (what, n_out, C, bits))
+  _dev(out_alpha_beta)
+  return kind
+
+
+def bn_act_quant_static(x, out, rows: int, C: int, scale_shift, act, out_alpha_beta, bits: int) -> None:
+  """out[rows][C] = the STATIC quantiser of act(scale * x + shift) against the device pair out_alpha_beta = (alpha, beta): uint8
+  codes, or the fake-quantised value (float32 / bfloat16), by out's dtype.  No slot is read or written."""
+  _dev(x)
+  kind = _static_operands('bn_act_quant_static', out, scale_shift, out_alpha_beta, rows * C, C, bits)
+  if x.numel() != rows * C:
+    raise ValueError('bn_act_quant_static: x has %d elements, rows=%d C=%d' % (x.numel(), rows, C))
+  _check(_lib.pf_bn_act_quant_static(_ptr(x), _ptr(out), c_int(dtype_code(x)), c_int(kind), c_int64(rows), c_int(C), _ptr(scale_shift),
+                                     c_int(ACT_CODES[act]), _ptr(out_alpha_beta), c_int(int(bits)), _stream()), 'pf_bn_act_quant_static')
+
+
+def conv_i8_fwd_q(X, Wp, alpha_beta, act_bits: int, w_scale_beta, w_tsum, w_tapsum, out_scale_shift, out_act, out_alpha_beta, out_bits: int,
+                  Out, B: int, H: int, Wd: int, C: int, N: int, R: int, S: int, stride: int, pad_h: int, pad_w: int, Ho: int, Wo: int,
+                  residual=None) -> None:
+  """conv_i8_fwd whose epilogue applies the consumer's folded BatchNorm, activation and static quantiser: Out[B][Ho][Wo][N] as uint8
+  codes or as the fake-quantised value, by its dtype.  A residual is refused by the library."""
+  _dev(X)
+  Kp = -(-(R * S * C) // 64) * 64
+  if X.dtype != torch.uint8 or Wp.dtype != torch.int8 or alpha_beta.dtype != torch.float32 or w_scale_beta.dtype != torch.float32 or (
+      w_tsum.dtype != torch.int32 or w_tapsum.dtype != torch.int32):
+    raise TypeError('conv_i8_fwd_q: X uint8, Wp int8, tables float32 / int32')
+  if not conv_i8_supported(C, N, R, S, stride):
+    raise ValueError('conv_i8_fwd_q: C=%d N=%d R=%d S=%d stride=%d is not eligible (pf_conv_i8_supported)' % (C, N, R, S, stride))
+  kind = _static_operands('conv_i8_fwd_q', Out, out_scale_shift, out_alpha_beta, B * Ho * Wo * N, N, out_bits)
+  if X.numel() != B * H * Wd * C or Wp.numel() != N * Kp or alpha_beta.numel() < 2 or (
+      w_scale_beta.numel() != 2 * N or w_tsum.numel() != N or w_tapsum.numel() != N * R * S) or int(out_bits) > 8:
+    raise ValueError('conv_i8_fwd_q: operand sizes do not match B=%d H=%d W=%d C=%d N=%d R=%d S=%d Ho=%d Wo=%d'
+                     % (B, H, Wd, C, N, R, S, Ho, Wo))
+  if (Ho - 1) * stride + R - 2 * pad_h > H or (Wo - 1) * stride + S - 2 * pad_w > Wd:
+    raise ValueError('conv_i8_fwd_q: the output extends beyond the symmetrically padded input')
+  _check(_lib.pf_conv_i8_fwd_q(_ptr(X), _ptr(Wp), _ptr(alpha_beta), c_int(int(act_bits)), _ptr(w_scale_beta), _ptr(w_tsum), _ptr(w_tapsum),
+                               _ptr(residual), _ptr(out_scale_shift), c_int(ACT_CODES[out_act]), _ptr(out_alpha_beta), c_int(int(out_bits)),
+                               _ptr(Out), c_int(kind), c_int(B), c_int(H), c_int(Wd), c_int(C), c_int(N), c_int(R), c_int(S), c_int(stride),
+                               c_int(pad_h), c_int(pad_w), c_int(Ho), c_int(Wo), _stream()), 'pf_conv_i8_fwd_q')
+
+
+def dw_i8_fwd_q(X, w_cols, w_scale_beta, alpha_beta, act_bits: int, out_scale_shift, out_act, out_alpha_beta, out_bits: int, Out, B: int,
+                H: int, Wd: int, C: int, stride: int, pad_h: int, pad_w: int, Ho: int, Wo: int) -> None:
+  """dw_i8_fwd whose epilogue applies the consumer's folded BatchNorm, activation and static quantiser: Out[B][Ho][Wo][C] as uint8
+  codes or as the fake-quantised value, by its dtype."""
+  _dev(X)
+  if X.dtype != torch.uint8 or w_cols.dtype != torch.int32 or alpha_beta.dtype != torch.float32 or w_scale_beta.dtype != torch.float32:
+    raise TypeError('dw_i8_fwd_q: X uint8, w_cols int32, w_scale_beta and alpha_beta float32')
+  if not dw_i8_supported(C, 3, stride):
+    raise ValueError('dw_i8_fwd_q: C=%d stride=%d is not eligible (pf_dw_i8_supported)' % (C, stride))
+  kind = _static_operands('dw_i8_fwd_q', Out, out_scale_shift, out_alpha_beta, B * Ho * Wo * C, C, out_bits)
+  if X.numel() != B * H * Wd * C or w_cols.numel() != 3 * C or alpha_beta.numel() < 2 or w_scale_beta.numel() != 2 or int(out_bits) > 8:
+    raise ValueError('dw_i8_fwd_q: operand sizes do not match B=%d H=%d W=%d C=%d Ho=%d Wo=%d' % (B, H, Wd, C, Ho, Wo))
+  _check(_lib.pf_dw_i8_fwd_q(_ptr(X), _ptr(w_cols), _ptr(w_scale_beta), _ptr(alpha_beta), c_int(int(act_bits)), _ptr(out_scale_shift),
+                             c_int(ACT_CODES[out_act]), _ptr(out_alpha_beta), c_int(int(out_bits)), _ptr(Out), c_int(kind), c_int(B),
+                             c_int(H), c_int(Wd), c_int(C), c_int(stride), c_int(pad_h), c_int(pad_w), c_int(Ho), c_int(Wo), _stream()),
+         'pf_dw_i8_fwd_q')
 
 
 def convg_bwd_data(dY, Wk, dX, B: int, H: int, Wd: int, C: int, N: int, R: int, S: int, stride: int, pad_h: int, pad_w: int,

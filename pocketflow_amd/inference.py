@@ -98,7 +98,7 @@ def load_shrunk(model_helper, path: str, device='cuda', compute_dtype=torch.floa
 
 
 def load_int8(model_helper, path: str, device='cuda', compute_dtype=torch.float32, activation_bits: int = 8, int8: str = 'auto',
-              depthwise: str = 'off'):
+              depthwise: str = 'off', act_ranges: str = 'batch'):
   """The integer artefact of tools/conversion/export_quant_int8_model.py (`model_int8.npz`) as an inference graph with the learner's
   activation quantisers on (`activation_bits` for every Relu / Relu6, as UniformQuantLearner feeds them).  Returns (graph, forward)
   like load_shrunk.  `int8`:
@@ -113,7 +113,15 @@ def load_int8(model_helper, path: str, device='cuda', compute_dtype=torch.float3
     'auto'  of those, the layers `graph.int8_dw_pays` accepts.
   `graph.nb_int8`: layers packed for the int8 route, Conv2D and depthwise together; `graph.int8_ran`: names of the kernels that
   took it in the forward passes so far.  Everything else -- the stem, Dense, split buckets, wider kernels -- is untouched.  A
-  malformed entry is a ValueError that names the variable."""
+  malformed entry is a ValueError that names the variable.
+  `act_ranges`:
+    'batch'   the default: every activation quantiser recalibrates on every batch, as the learner's eval graph does;
+    'static'  the ranges the artefact carries (`<activation op name>/act_range`, written by the export tool's --calib_batches): each is
+              written into its slot once, decoded once (`graph.act_static`), and `forward` never resets or writes the slots.  Every
+              quantiser then runs on a clamping kernel (pf_act_static.hip), no statistics pass runs, and a packed layer whose one
+              consumer is a quantising BatchNormAct applies it in its epilogue and hands on codes or the fake-quantised tensor
+              (`graph.requant_ran`).  'auto' then means `graph.int8_pays_static` / `graph.int8_dw_pays_static`.  A file without
+              ranges, a missing or surplus entry, a non-finite range or min > max is a ValueError that names the file or the op."""
   from pocketflow_amd import int8 as I8
   from pocketflow_amd.learners.abstract_learner import input_spec
   from pocketflow_amd.tools.conversion.export_quant_int8_model import MODE_SPLIT, load_codes
@@ -123,9 +131,20 @@ def load_int8(model_helper, path: str, device='cuda', compute_dtype=torch.float3
     raise ValueError("depthwise must be 'auto', 'on' or 'off'")
   if not 1 <= int(activation_bits) <= 32:
     raise ValueError('activation_bits must lie in 1..32 (got %s)' % activation_bits)
+  if act_ranges not in ('batch', 'static'):
+    raise ValueError("act_ranges must be 'batch' or 'static'")
+  static = act_ranges == 'static'
   if not os.path.isfile(path):
     raise FileNotFoundError(path)
   variables, raw = load_codes(path)
+  ranges = None
+  if static:
+    from pocketflow_amd.tools.conversion.export_quant_int8_model import load_act_ranges
+    ranges = load_act_ranges(path)
+    if not ranges:
+      raise ValueError("%s: act_ranges='static' needs an artefact with activation ranges (export with --calib_batches)" % path)
+  pays = G.int8_pays_static if static else G.int8_pays
+  dw_pays = G.int8_dw_pays_static if static else G.int8_dw_pays
   graph = G.Graph(_scope_of(variables), device, compute_dtype)
   graph.fuse_conv1x1 = bool(FLAGS.fuse_conv1x1)
   with graph.as_default():
@@ -145,7 +164,7 @@ def load_int8(model_helper, path: str, device='cuda', compute_dtype=torch.float3
       if (int8 == 'off' or depthwise == 'off' or int(meta[0]) > 8 or int(meta[1]) == MODE_SPLIT
           or not I8.depthwise_supported(dw.channels, dw.k, dw.stride)):
         continue
-      if depthwise == 'auto' and not G.int8_dw_pays(dw.channels, dw.stride, compute_dtype):
+      if depthwise == 'auto' and not dw_pays(dw.channels, dw.stride, compute_dtype):
         continue
       try:
         packed_dw[name] = I8.pack_depthwise(raw[name]['codes'], raw[name]['alpha'], raw[name]['beta'], meta)
@@ -158,7 +177,7 @@ def load_int8(model_helper, path: str, device='cuda', compute_dtype=torch.float3
     kh, kw, cin, cout = var.ref_shape
     if not I8.supported(cin, cout, kh, kw, conv.stride):
       continue
-    if int8 == 'auto' and not G.int8_pays(kh, cin, cout, conv.stride, compute_dtype):
+    if int8 == 'auto' and not pays(kh, cin, cout, conv.stride, compute_dtype):
       continue
     try:
       packed[name] = I8.pack_layer(raw[name]['codes'], raw[name]['alpha'], raw[name]['beta'], meta)
@@ -167,6 +186,8 @@ def load_int8(model_helper, path: str, device='cuda', compute_dtype=torch.float3
   for op in graph.activation_ops:
     if op.type in ('Relu', 'Relu6'):
       op.bits = int(activation_bits)
+  if static:
+    _check_act_ranges(path, graph, ranges)
   graph.finalize(requires_grad=False)
   graph.store.load_numpy(variables, strict=True)
   graph.training = False
@@ -179,8 +200,38 @@ def load_int8(model_helper, path: str, device='cuda', compute_dtype=torch.float3
     dw_layers[name].int8 = {'wcol': torch.from_numpy(p['wcol'].view(np.int32)).to(graph.device),
                             'scale_beta': torch.from_numpy(p['scale_beta']).to(graph.device)}
 
+  if static:
+    # each range into its slot, through the kernels a batch with that minimum / maximum would go through: the slot then decodes
+    # exactly as it would after such a batch
+    from pocketflow_amd import hip
+    hip.minmax_slots_init(graph.act_slots)
+    for op in graph.activation_ops:
+      if op.name in ranges:
+        hip.minmax_tensor(torch.tensor(ranges[op.name], dtype=torch.float32, device=graph.device), graph.act_slots[op.index], None)
+    graph.act_static = graph.act_alpha_beta()
+
+    def forward_static(images) -> torch.Tensor:
+      with torch.no_grad(), graph.as_default():
+        return model_helper.forward_eval(G.to_device_images(images, graph))   # the slots stay as loaded: nothing calibrates
+    return graph, forward_static
+
   def forward(images) -> torch.Tensor:
     with torch.no_grad(), graph.as_default():
       graph.begin_step()                         # the activation quantisers calibrate on every batch
       return model_helper.forward_eval(G.to_device_images(images, graph))
   return graph, forward
+
+
+def _check_act_ranges(path: str, graph, ranges) -> None:
+  """The artefact's ranges against the graph's Relu / Relu6 ops: one finite pair with min <= max for each, and nothing else."""
+  ops = {op.name for op in graph.activation_ops if op.type in ('Relu', 'Relu6')}
+  for name in sorted(ops - set(ranges)):
+    raise ValueError('%s: no activation range for %s' % (path, name))
+  for name in sorted(set(ranges) - ops):
+    raise ValueError('%s: an activation range for %s, which is no activation op of this graph' % (path, name))
+  for name in sorted(ops):
+    mn, mx = ranges[name]
+    if not (np.isfinite(mn) and np.isfinite(mx)):
+      raise ValueError('%s: the activation range of %s is not finite (%r, %r)' % (path, name, mn, mx))
+    if mn > mx:
+      raise ValueError('%s: the activation range of %s has min %r > max %r' % (path, name, mn, mx))

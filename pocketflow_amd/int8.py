@@ -217,3 +217,58 @@ def depthwise_reference(c: np.ndarray, alpha_a: float, beta_a: float, bits_a: in
   y = t1 + t2 + (t3a + t3b)
   mag = np.abs(t1) + np.abs(t2) + np.abs(t3a) + np.abs(t3b)
   return (y, mag) if terms else y
+
+
+# ---- fixed (calibrated) activation ranges: the static, clamping quantiser (pf_act_static.hip) -------------------------------------
+
+def range_alpha_beta(mn, mx):
+  """(alpha, beta) float32 as a slot holding (min, max) decodes: alpha = (max - min) + 1e-10f, beta = min (pf_common.h)."""
+  mn, mx = np.float32(mn), np.float32(mx)
+  return np.float32(np.float32(mx - mn) + np.float32(1e-10)), mn
+
+
+def static_codes(u, alpha, beta, bits: int) -> np.ndarray:
+  """uint8 codes of float32 values u under a FIXED range: the float32 chain of the device's quantiser, every operation rounded to
+  float32 (the library is built without contraction, so this is bit for bit what the kernels compute),
+    t = ((u - beta) / alpha) * k;  t = min(max(t, 0), k);  code = rint(t)   (half to even).
+  It is the per-batch quantiser's chain plus the one clamp: a value outside the calibrated range takes the end code."""
+  if not 1 <= int(bits) <= 8:
+    raise ValueError('static_codes: 1..8 bits (got %s)' % bits)
+  u = np.asarray(u, np.float32)
+  alpha, beta, k = np.float32(alpha), np.float32(beta), np.float32(2 ** int(bits) - 1)
+  with np.errstate(over='ignore', invalid='ignore'):
+    t = ((u - beta).astype(np.float32) / alpha).astype(np.float32)
+    t = (t * k).astype(np.float32)
+  t = np.minimum(np.maximum(t, np.float32(0)), k)
+  return np.rint(t).astype(np.uint8)
+
+
+def static_value(code, alpha, beta, bits: int) -> np.ndarray:
+  """The float32 value of a code: alpha * (code / k) + beta, multiply and then add, one float32 rounding each (the apply pass)."""
+  alpha, beta, k = np.float32(alpha), np.float32(beta), np.float32(2 ** int(bits) - 1)
+  q = (np.asarray(code).astype(np.float32) / k).astype(np.float32)
+  return ((alpha * q).astype(np.float32) + beta).astype(np.float32)
+
+
+def requant_reference(c: np.ndarray, alpha_a: float, beta_a: float, bits_a: int, d: np.ndarray, alpha_w, beta_w, bits_w: int, stride: int,
+                      scale: np.ndarray, shift: np.ndarray, act: Optional[str], out_min: float, out_max: float, out_bits: int,
+                      pad_h: Optional[int] = None, pad_w: Optional[int] = None):
+  """A layer on codes followed by its consumer's folded BatchNorm, activation and static quantiser, in int64 / float64:
+  y = conv_reference(...) for d of shape [N][R][S][C] (pads given) or depthwise_reference(...) for d of shape [C][3][3],
+  u = act(scale * y + shift), t = clip((u - out_min) / (out_max - out_min + 1e-10) * k, 0, k), code = rint(t).
+  Returns (codes int64, values float64) with value = alpha * code / k + out_min."""
+  d = np.asarray(d)
+  if d.ndim == 3:
+    y = depthwise_reference(c, alpha_a, beta_a, bits_a, d, float(np.asarray(alpha_w).reshape(-1)[0]),
+                            float(np.asarray(beta_w).reshape(-1)[0]), bits_w, stride)
+  else:
+    y = conv_reference(c, alpha_a, beta_a, bits_a, d, alpha_w, beta_w, bits_w, stride, pad_h, pad_w)
+  u = np.asarray(scale, np.float64) * y + np.asarray(shift, np.float64)
+  if act == 'Relu':
+    u = np.maximum(u, 0.0)
+  elif act == 'Relu6':
+    u = np.clip(u, 0.0, 6.0)
+  k = float(2 ** int(out_bits) - 1)
+  alpha = (float(out_max) - float(out_min)) + 1e-10
+  codes = np.rint(np.clip((u - float(out_min)) / alpha * k, 0.0, k)).astype(np.int64)
+  return codes, alpha * (codes / k) + float(out_min)

@@ -18,6 +18,9 @@ multiply integer codes on the i8 matrix cores ('off': every kernel decoded, the 
 `--uql_activation_bits` (default 32: no codes, nothing runs on int8) sets the activation quantisers; the result line then carries
 `nb_int8_layers`.  `--int8_depthwise off|on|auto` (default off) does the same for the depthwise 3x3 layers of a MobileNet
 (pf_dw_i8_fwd; 'auto' = the layers graph.int8_dw_pays accepts); packed depthwise layers count in `nb_int8_layers`.
+`--act_ranges batch|static` (default batch): 'static' quantises every activation against the fixed range the file carries (written by
+export_quant_int8_model --calib_batches N) instead of recalibrating per batch; `nb_requant_layers` then counts the packed layers that
+applied the BatchNorm + activation + quantiser behind them in their own epilogue.
 
     python -m pocketflow_amd.tools.benchmark.calc_inference_time --net resnet_at_ilsvrc12 --resnet_size 50 --batch_size 256 \\
         --compute_dtype bfloat16 --model_file ./models_uqtf_eval/model_int8.npz --int8 on --uql_activation_bits 8
@@ -48,6 +51,7 @@ flags.DEFINE_string('net', 'resnet_at_ilsvrc12', 'ModelHelper module under pocke
 flags.DEFINE_string('reinflate', 'auto', "'auto': re-inflate the layers graph.gather_pays rejects | 'none' | 'all' (full-shape baseline)")
 flags.DEFINE_string('int8', 'auto', "a model_int8.npz: 'auto' = the layers graph.int8_pays accepts on the int8 kernel | 'on' = every eligible layer | 'off' = none")
 flags.DEFINE_string('int8_depthwise', 'off', "a model_int8.npz: depthwise 3x3 layers on the int8 kernel: 'off' = none | 'on' = every eligible layer | 'auto' = the layers graph.int8_dw_pays accepts")
+flags.DEFINE_string('act_ranges', 'batch', "a model_int8.npz: 'batch' = every activation quantiser recalibrates per batch | 'static' = the ranges the file carries (export with --calib_batches)")
 flags.DEFINE_boolean('json', False, 'print one JSON result line')
 
 log = logging.getLogger('pocketflow_amd')
@@ -101,14 +105,14 @@ def main(argv=None) -> int:
   int8 = is_int8_artefact(FLAGS.model_file)
   if int8:
     graph, _ = load_int8(mh, FLAGS.model_file, device, AL.compute_dtype(), FLAGS.uql_activation_bits, int8=FLAGS.int8,
-                         depthwise=FLAGS.int8_depthwise)
+                         depthwise=FLAGS.int8_depthwise, act_ranges=FLAGS.act_ranges)
   else:
     graph, _ = load_shrunk(mh, FLAGS.model_file, device, AL.compute_dtype(), reinflate=FLAGS.reinflate)
   batch = int(mh.dataset_train.batch_size)
   x = to_device_images(np.zeros((batch,) + tuple(mh.dataset_train.image_shape), dtype=np.float32), graph)
 
   def forward_eval(images):
-    if int8:
+    if int8 and graph.act_static is None:
       graph.begin_step()                         # the activation quantisers calibrate on every batch
     return mh.forward_eval(images)
   sec = measure(forward_eval, graph, x, FLAGS.nb_repts_warmup, FLAGS.nb_repts)
@@ -119,7 +123,8 @@ def main(argv=None) -> int:
           'kernel_params_kept_share': graph.kernel_params_kept / max(graph.kernel_params, 1)}
   if int8:
     rslt.update({'int8': FLAGS.int8, 'int8_depthwise': FLAGS.int8_depthwise, 'nb_int8_layers': graph.nb_int8, 'nb_int8_layers_ran': len(graph.int8_ran),
-                 'activation_bits': FLAGS.uql_activation_bits})
+                 'activation_bits': FLAGS.uql_activation_bits, 'act_ranges': FLAGS.act_ranges,
+                 'nb_requant_layers': len(graph.requant_ran)})
   print('time consumption of %s: %.3f ms per batch of %d, %.4f ms per image (%d gathered layers, %d re-inflated)'
         % (FLAGS.model_file, rslt['ms_per_batch'], batch, rslt['ms_per_image'], graph.nb_gathered, len(graph.reinflated)))
   if int8:

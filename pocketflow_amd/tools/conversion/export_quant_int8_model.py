@@ -19,7 +19,9 @@ before it is written -- there is no second implementation of the quantiser here.
 Artefact: one `.npz` -- per quantised kernel `<name>/codes` (bit-packed, `bits` per weight, HWIO order like the reference's
 checkpoints), `<name>/alpha`, `<name>/beta` (float32, one per bucket), `<name>/meta` = [bits, bucket mode, bucket size, *shape];
 every other variable as float32 -- plus `export_summary.json` (bytes before / after per tensor, incl. the 2 x 32 bits per
-bucket the reference accounts for, uq utils.py:299-306).
+bucket the reference accounts for, uq utils.py:299-306).  With `--calib_batches N` (N > 0) the file also carries one float32
+`<activation op name>/act_range` = [min, max] per Relu / Relu6 op: the range of that activation over N evaluation batches
+(`calibrate_act_ranges`), which `inference.load_int8(act_ranges='static')` quantises against instead of recalibrating per batch.
 
     python -m pocketflow_amd.tools.conversion.export_quant_int8_model --model_name resnet --dataset_name ilsvrc_12 \\
         --uql_weight_bits 8 [--uql_use_buckets --uql_bucket_type channel]      # reads uql_save_quant_model_path (needs the GPU)
@@ -36,6 +38,7 @@ import numpy as np
 log = logging.getLogger('pocketflow_amd')
 
 MODE_TENSOR, MODE_CHANNEL, MODE_SPLIT = 0, 1, 2
+ACT_RANGE_SUFFIX = '/act_range'
 
 
 def _bucket_index(shape, mode: int, bucket_size: int) -> np.ndarray:
@@ -146,9 +149,67 @@ def load_exported(path: str) -> Dict[str, np.ndarray]:
       out[name] = decode_tensor(z[key], z[name + '/alpha'], z[name + '/beta'], z[name + '/meta'])
       done.update({key, name + '/alpha', name + '/beta', name + '/meta'})
   for key in z.files:
-    if key not in done:
+    if key not in done and not key.endswith(ACT_RANGE_SUFFIX):      # ranges are no variables: load_act_ranges
       out[key] = z[key]
   return out
+
+
+def load_act_ranges(path: str) -> Dict[str, Tuple[float, float]]:
+  """{activation op name: (min, max)} of the `<op name>/act_range` entries of an artefact; empty for a file without ranges.  An
+  entry that is not two numbers is a ValueError that names it."""
+  out = {}
+  with np.load(path) as z:
+    for key in z.files:
+      if key.endswith(ACT_RANGE_SUFFIX):
+        v = np.asarray(z[key])
+        if v.size != 2 or v.dtype.kind not in 'fiu':
+          raise ValueError('%s: %s holds %s, expected [min, max]' % (path, key, tuple(v.shape)))
+        v = v.astype(np.float32).reshape(-1)
+        out[key[:-len(ACT_RANGE_SUFFIX)]] = (float(v[0]), float(v[1]))
+  return out
+
+
+def decode_slots(slots: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+  """(min, max), float32 each, of int32 min / max slots [n][2] as the device keeps them: the order-preserving encoding of the
+  minimum and the complement of that of the maximum (pf_common.h enc_f32 / dec_f32, slot_alpha_beta)."""
+  e = np.ascontiguousarray(slots).view(np.uint32).reshape(-1, 2)
+  dec = lambda v: np.where(v & np.uint32(0x80000000), v & np.uint32(0x7FFFFFFF), ~v).astype(np.uint32).view(np.float32)
+  return dec(e[:, 0].copy()), dec(~e[:, 1])
+
+
+def calibrate_act_ranges(model_helper, path: str, nb_batches: int, activation_bits: int = 8, device='cuda', dtype=None) -> Dict:
+  """Run `nb_batches` evaluation batches of the model helper's dataset through the artefact at `path` on the float route
+  (load_int8(int8='off'): what the reference's eval graph evaluates, every quantiser recalibrating per batch), keep the minimum of
+  the minima and the maximum of the maxima every activation quantiser saw, and rewrite the file with one float32
+  `<activation op name>/act_range` = [min, max] per Relu / Relu6 op.  Returns {op name: (min, max)}."""
+  import torch
+  from pocketflow_amd.inference import load_int8
+  if int(nb_batches) < 1:
+    raise ValueError('calibrate_act_ranges: nb_batches must be positive (got %s)' % nb_batches)
+  graph, forward = load_int8(model_helper, path, device, dtype if dtype is not None else torch.float32, activation_bits, int8='off')
+  it = model_helper.build_dataset_eval()
+  lo = hi = None
+  for _ in range(int(nb_batches)):
+    images, _ = it.get_next()
+    forward(images)
+    mn, mx = decode_slots(graph.act_slots.cpu().numpy())
+    lo = mn if lo is None else np.minimum(lo, mn)
+    hi = mx if hi is None else np.maximum(hi, mx)
+  ranges = {}
+  for op in graph.activation_ops:
+    if op.type in ('Relu', 'Relu6'):
+      ranges[op.name] = (float(lo[op.index]), float(hi[op.index]))
+  write_act_ranges(path, ranges)
+  return ranges
+
+
+def write_act_ranges(path: str, ranges: Dict[str, Tuple[float, float]]) -> None:
+  """Rewrite the artefact at `path` with exactly these ranges (earlier `*/act_range` entries are dropped; every other entry as is)."""
+  with np.load(path) as z:
+    out = {k: z[k] for k in z.files if not k.endswith(ACT_RANGE_SUFFIX)}
+  for name, (mn, mx) in ranges.items():
+    out[name + ACT_RANGE_SUFFIX] = np.array([mn, mx], np.float32)
+  np.savez(path, **out)
 
 
 def load_codes(path: str):
@@ -169,6 +230,7 @@ def main(argv=None):
   flags.DEFINE_string('export_file', 'model_int8.npz', 'file name of the exported model (beside uql_save_quant_model_path)')
   flags.DEFINE_string('model_name', 'resnet', 'lenet | resnet | mobilenet')
   flags.DEFINE_string('dataset_name', 'cifar_10', 'cifar_10 | ilsvrc_12')
+  flags.DEFINE_integer('calib_batches', 0, '# of evaluation batches to calibrate fixed activation ranges on (0: none, the file as before)')
   import importlib
   import pocketflow_amd.learners.uniform_quantization.learner as UQ
   FLAGS.parse(argv if argv is not None else sys.argv[1:])
@@ -177,7 +239,14 @@ def main(argv=None):
   from pocketflow_amd.utils import checkpoint
   learner.restore_vars(checkpoint.latest_checkpoint(os.path.dirname(FLAGS.uql_save_quant_model_path)))
   path = os.path.join(os.path.dirname(FLAGS.uql_save_quant_model_path), FLAGS.export_file)
-  print(json.dumps({k: v for k, v in export_from_learner(learner, path).items() if k != 'layers'}))
+  summ = {k: v for k, v in export_from_learner(learner, path).items() if k != 'layers'}
+  if FLAGS.calib_batches > 0:
+    from pocketflow_amd.learners import abstract_learner as AL
+    mh = learner.model_helper if hasattr(learner, 'model_helper') else mod.ModelHelper()
+    del learner
+    summ['act_ranges'] = len(calibrate_act_ranges(mh, path, FLAGS.calib_batches, FLAGS.uql_activation_bits, AL.require_gpu(),
+                                                  AL.compute_dtype()))
+  print(json.dumps(summ))
 
 
 if __name__ == '__main__':

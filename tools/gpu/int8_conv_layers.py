@@ -11,6 +11,18 @@ with each of them on both routes.  Bounds: max(FLOPs / peak, bytes / 8 TB/s) wit
 route and twice that for int8; bytes = pre-BN input read + intermediate written and read + output written + kernel.
 
   python tools/gpu/int8_conv_layers.py > profiles/int8_conv_layers.txt
+
+STATIC=1 prints the static column instead -- the layer on a graph with FIXED activation ranges, where the BatchNorm + activation +
+quantiser BEHIND the layer has a known range:
+
+  float  the bf16 kernel on the fake-quantised bf16 input + pf_bn_act_quant_static over its output (bf16 -> the consumer's uint8 codes)
+  int8   pf_conv_i8_fwd_q: codes in, the consumer's codes out, one launch
+
+in ROUNDS alternating rounds; `pays` marks the rows where the int8 route is faster by more than the larger spread (max - min over the
+rounds): what graph.int8_pays_static has to return.  (A layer whose output joins a residual has no such consumer; it is timed as if
+it had, for the kernel's sake.)
+
+  STATIC=1 python tools/gpu/int8_conv_layers.py >> profiles/int8_conv_layers.txt
 """
 import os
 import sys
@@ -27,6 +39,66 @@ from gather_conv_layers import MOBILENET, RESNET50
 
 B = int(os.environ.get('B', 256))
 MFMA_PEAK, HBM_PEAK = 2.5e15, 8.0e12
+
+
+def main_static():
+  rounds = int(os.environ.get('ROUNDS', 3))
+  print('# STATIC ranges: B = %d, bf16 activations, 8-bit codes; us per layer (best of %d alternating rounds, each the best of 3 replays of '
+        '20 captured launches); spread = max - min over the rounds' % (B, rounds))
+  print('%-10s %-20s %-22s %2s | %9s %9s %9s | %9s | %7s | %8s %8s | %4s' % (
+      'net', 'layer', 'H,C,N,k,stride', 'n', 'bf16 us', 'static us', 'float us', 'i8_q us', 'f / i8', 'f spread', 'i spread', 'pays'))
+  for net, layers in (('resnet50', RESNET50), ('mobilenet', MOBILENET)):
+    tot_f = tot_i = 0.0
+    for name, H, C, N, k, stride, pad, _lazy, cnt in layers:
+      if not hip.conv_i8_supported(C, N, k, k, stride) or (k > 1 and C % 64):
+        print('%-10s %-20s %-22s %2d | not eligible' % (net, name, '%d,%d,%d,%d,%d' % (H, C, N, k, stride), cnt))
+        continue
+      Ho = (H + 2 * pad - k) // stride + 1
+      M = B * Ho * Ho
+      g = torch.Generator(device='cuda').manual_seed(H + C + N + k)
+      xq = torch.rand((B, C, H, H), device='cuda', generator=g).mul_(4.0).bfloat16().contiguous(memory_format=torch.channels_last)
+      codes = torch.randint(0, 256, (B, C, H, H), dtype=torch.uint8, device='cuda').contiguous(memory_format=torch.channels_last)
+      ab = torch.tensor([4.0, 0.0], device='cuda')
+      oab = torch.tensor([3.0, 0.0], device='cuda')
+      ss = torch.stack([torch.rand(N, device='cuda') * 0.1 + 0.05, torch.randn(N, device='cuda')]).contiguous()
+      rng = np.random.RandomState(C + N)
+      d = rng.randint(0, 256, size=(k, k, C, N)).astype(np.uint8)
+      alpha, beta = rng.uniform(0.05, 0.6, N).astype(np.float32), -rng.uniform(0.02, 0.3, N).astype(np.float32)
+      meta = np.array([8, ex.MODE_CHANNEL, 0, k, k, C, N], np.int64)
+      p = int8.pack_layer(ex.pack_codes(d.reshape(-1), 8), alpha, beta, meta)
+      wdec = ex.decode_tensor(ex.pack_codes(d.reshape(-1), 8), alpha, beta, meta)
+      wfull = torch.from_numpy(np.ascontiguousarray(wdec.transpose(3, 0, 1, 2))).cuda().bfloat16()
+      pw, psb, pts, ptp = (torch.from_numpy(np.ascontiguousarray(p[key])).cuda() for key in ('w', 'scale_beta', 'tsum', 'tapsum'))
+      y = torch.empty((B, N, Ho, Ho), dtype=torch.bfloat16, device='cuda').contiguous(memory_format=torch.channels_last)
+      out = torch.empty((B, N, Ho, Ho), dtype=torch.uint8, device='cuda').contiguous(memory_format=torch.channels_last)
+      if k == 1:
+        geom = None if stride == 1 else (Ho, Ho, H, H, stride)
+        w2 = wfull.reshape(N, C)
+        conv_f = lambda: hip.conv1x1_fwd(xq, w2, y, M, N, C, geom=geom)
+      else:
+        conv_f = lambda: hip.conv2d_fwd(xq, wfull, y, B, H, H, C, N, k, k, stride, pad, pad, Ho, Ho)
+      static_f = lambda: hip.bn_act_quant_static(y, out, M, N, ss, 'Relu', oab, 8)
+      conv_q = lambda: hip.conv_i8_fwd_q(codes, pw, ab, 8, psb, pts, ptp, ss, 'Relu', oab, 8, out, B, H, H, C, N, k, k, stride, pad, pad,
+                                         Ho, Ho)
+
+      def route_f():
+        conv_f()
+        static_f()
+      t = {key: [] for key in ('bf16', 'static', 'float', 'int8')}
+      for _ in range(rounds):
+        for key, fn in (('bf16', conv_f), ('static', static_f), ('float', route_f), ('int8', conv_q)):
+          t[key].append(gpu_time_us(fn))
+      spread_f, spread_i = max(t['float']) - min(t['float']), max(t['int8']) - min(t['int8'])
+      t = {key: min(v) for key, v in t.items()}
+      pays = t['float'] - t['int8'] > max(spread_f, spread_i)
+      print('%-10s %-20s %-22s %2d | %9.1f %9.1f %9.1f | %9.1f | %7.2f | %8.1f %8.1f | %4s' % (
+          net, name, '%d,%d,%d,%d,%d' % (H, C, N, k, stride), cnt, t['bf16'], t['static'], t['float'], t['int8'], t['float'] / t['int8'],
+          spread_f, spread_i, 'yes' if pays else 'no'))
+      tot_f += cnt * t['float']
+      tot_i += cnt * t['int8']
+      del xq, y, codes, out
+    print('%-10s eligible convolutions of one forward pass with the quantiser behind them, static ranges  float %.2f ms   int8 %.2f ms   '
+          'float / int8 %.2f' % (net, tot_f / 1e3, tot_i / 1e3, tot_f / max(tot_i, 1e-9)))
 
 
 def main():
@@ -101,4 +173,4 @@ def main():
 
 
 if __name__ == '__main__':
-  main()
+  main_static() if os.environ.get('STATIC', '0') == '1' else main()

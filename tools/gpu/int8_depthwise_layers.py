@@ -11,6 +11,17 @@ graph.int8_dw_pays has to return.  Bounds: bytes / 8 TB/s, bytes = pre-BN input 
 written (float: 2 + 2 + 2 and 2 per output; int8: 2 + 1 + 1 and 2 per output).
 
   python tools/gpu/int8_depthwise_layers.py > profiles/int8_depthwise_layers.txt
+
+STATIC=1 prints the static column instead -- the layer on a graph with FIXED activation ranges, where the BatchNorm + ReLU6 + quantiser
+BEHIND the layer has a known range:
+
+  float  pf_depthwise_fwd on the fake-quantised bf16 input (with the statistics rows the graph asks it for) + pf_bn_act_quant_static
+         over its output (bf16 -> the consumer's uint8 codes)
+  int8   pf_dw_i8_fwd_q: codes in, the consumer's codes out, one launch
+
+`pays` as above: what graph.int8_dw_pays_static has to return.  Bounds: float 2 + 2, 2 + 1 bytes per input / output element; int8 1 + 1.
+
+  STATIC=1 python tools/gpu/int8_depthwise_layers.py >> profiles/int8_depthwise_layers.txt
 """
 import os
 import sys
@@ -30,6 +41,61 @@ HBM_PEAK = 8.0e12
 # (name, input H = W, C, stride, count) of utils/external/mobilenet_v1.py's conv defs at 224 x 224
 LAYERS = [('dw1', 112, 32, 1, 1), ('dw2 /2', 112, 64, 2, 1), ('dw3', 56, 128, 1, 1), ('dw4 /2', 56, 128, 2, 1), ('dw5', 28, 256, 1, 1),
           ('dw6 /2', 28, 256, 2, 1), ('dw7-11', 14, 512, 1, 5), ('dw12 /2', 14, 512, 2, 1), ('dw13', 7, 1024, 1, 1)]
+
+
+def main_static():
+  print('# STATIC ranges: B = %d, bf16 activations, 8-bit codes; us per layer (best of %d alternating rounds, each the best of 3 replays of '
+        '20 captured launches); spread = max - min over the rounds; bound = bytes / 8 TB/s' % (B, ROUNDS))
+  print('%-10s %-10s %-14s %2s | %9s %9s %9s | %9s | %7s | %7s %7s | %8s %8s | %4s' % (
+      'net', 'layer', 'H,C,stride', 'n', 'dw us', 'static us', 'float us', 'dw_q us', 'f / i8', 'f bound', 'i bound', 'f spread', 'i spread',
+      'pays'))
+  tot_f = tot_i = 0.0
+  for name, H, C, stride, cnt in LAYERS:
+    Ho = -(-H // stride)
+    pad = int8.same_pads(H, 3, stride)[0]
+    rows, M = B * H * H, B * Ho * Ho
+    g = torch.Generator(device='cuda').manual_seed(H + C + stride)
+    xq = torch.rand((B, C, H, H), device='cuda', generator=g).mul_(6.0).bfloat16().contiguous(memory_format=torch.channels_last)
+    codes = torch.randint(0, 256, (B, C, H, H), dtype=torch.uint8, device='cuda').contiguous(memory_format=torch.channels_last)
+    ab = torch.tensor([6.0, 0.0], device='cuda')
+    oab = torch.tensor([4.5, 0.0], device='cuda')                  # narrower than ReLU6's image: the clamp acts
+    ss = torch.stack([torch.rand(C, device='cuda') * 0.2 + 0.1, torch.randn(C, device='cuda')]).contiguous()
+    rng = np.random.RandomState(C + stride)
+    d = rng.randint(0, 256, size=(3, 3, C, 1)).astype(np.uint8)
+    alpha, beta = rng.uniform(0.05, 0.6, 1).astype(np.float32), -rng.uniform(0.02, 0.3, 1).astype(np.float32)
+    meta = np.array([8, ex.MODE_TENSOR, 0, 3, 3, C, 1], np.int64)
+    p = int8.pack_depthwise(ex.pack_codes(d.reshape(-1), 8), alpha, beta, meta)
+    wdec = ex.decode_tensor(ex.pack_codes(d.reshape(-1), 8), alpha, beta, meta)
+    wcrs = torch.from_numpy(np.ascontiguousarray(wdec[..., 0].transpose(2, 0, 1))).cuda().bfloat16()
+    wcol = torch.from_numpy(p['wcol'].view(np.int32)).cuda()
+    wsb = torch.from_numpy(p['scale_beta']).cuda()
+    y = torch.empty((B, C, Ho, Ho), dtype=torch.bfloat16, device='cuda').contiguous(memory_format=torch.channels_last)
+    out = torch.empty((B, C, Ho, Ho), dtype=torch.uint8, device='cuda').contiguous(memory_format=torch.channels_last)
+    partial = torch.empty((hip.depthwise_groups(B, Ho, Ho, C), 4, C), dtype=torch.float32, device='cuda')
+    dw_f = lambda: hip.depthwise_fwd(xq, wcrs, y, B, H, H, C, 3, stride, pad, pad, Ho, Ho, partial=partial)
+    static_f = lambda: hip.bn_act_quant_static(y, out, M, C, ss, 'Relu6', oab, 8)
+    dw_q = lambda: hip.dw_i8_fwd_q(codes, wcol, wsb, ab, 8, ss, 'Relu6', oab, 8, out, B, H, H, C, stride, pad, pad, Ho, Ho)
+
+    def route_f():
+      dw_f()
+      static_f()
+    t = {key: [] for key in ('dw', 'static', 'float', 'int8')}
+    for _ in range(ROUNDS):
+      for key, fn in (('dw', dw_f), ('static', static_f), ('float', route_f), ('int8', dw_q)):
+        t[key].append(gpu_time_us(fn))
+    spread_f, spread_i = max(t['float']) - min(t['float']), max(t['int8']) - min(t['int8'])
+    t = {key: min(v) for key, v in t.items()}
+    bound_f = (rows * C * 2 + M * C * 5) / HBM_PEAK * 1e6
+    bound_i = (rows * C + M * C) / HBM_PEAK * 1e6
+    pays = t['float'] - t['int8'] > max(spread_f, spread_i)
+    print('%-10s %-10s %-14s %2d | %9.1f %9.1f %9.1f | %9.1f | %7.2f | %7.2f %7.2f | %8.1f %8.1f | %4s' % (
+        'mobilenet', name, '%d,%d,%d' % (H, C, stride), cnt, t['dw'], t['static'], t['float'], t['int8'], t['float'] / t['int8'],
+        bound_f / t['float'], bound_i / t['int8'], spread_f, spread_i, 'yes' if pays else 'no'))
+    tot_f += cnt * t['float']
+    tot_i += cnt * t['int8']
+    del xq, y, codes, out
+  print('mobilenet  depthwise layers of one forward pass with the quantiser behind them, static ranges  float %.2f ms   int8 %.2f ms   '
+        'float / int8 %.2f' % (tot_f / 1e3, tot_i / 1e3, tot_f / max(tot_i, 1e-9)))
 
 
 def main():
@@ -96,4 +162,4 @@ def main():
 
 
 if __name__ == '__main__':
-  main()
+  main_static() if os.environ.get('STATIC', '0') == '1' else main()

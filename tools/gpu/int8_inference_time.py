@@ -6,8 +6,15 @@ spread (max - min) over the rounds.  NET=mobilenet does the same for MobileNet-v
 --int8 on --int8_depthwise on (the depthwise layers on pf_dw_i8_fwd as well) and --int8 auto --int8_depthwise auto (what
 graph.int8_pays and graph.int8_dw_pays accept).
 
+STATIC=1 times FIXED activation ranges instead: the artefact is calibrated over two evaluation batches (calibrate_act_ranges) and the
+routes are the parent's two (--act_ranges batch with --int8 off, and with the best per-batch setting: --int8 auto, for MobileNet plus
+--int8_depthwise auto) and the static ones (--act_ranges static with --int8 off, --int8 on, for MobileNet --int8 on --int8_depthwise on, and
+--int8 auto --int8_depthwise auto: what graph.int8_pays_static and graph.int8_dw_pays_static accept).
+
   python tools/gpu/int8_inference_time.py > profiles/int8_inference_time.txt
   NET=mobilenet python tools/gpu/int8_inference_time.py > profiles/int8_mobilenet_inference_time.txt
+  (NET=mobilenet STATIC=1 python tools/gpu/int8_inference_time.py; STATIC=1 python tools/gpu/int8_inference_time.py) \
+      > profiles/int8_static_inference_time.txt
 """
 import io
 import json
@@ -25,6 +32,7 @@ IMAGE = int(os.environ.get('IMAGE', 224))
 ROUNDS = int(os.environ.get('ROUNDS', 3))
 REPTS = int(os.environ.get('REPTS', 20))
 NET = os.environ.get('NET', 'resnet50')
+STATIC = os.environ.get('STATIC', '0') == '1'
 
 
 def main():
@@ -51,6 +59,17 @@ def main():
       FLAGS.resnet_size = 50
       net_args, title = ['--net', 'resnet_at_ilsvrc12', '--resnet_size', '50'], 'ResNet-50'
       routes = [(mode, ['--int8', mode]) for mode in ('off', 'auto', 'on')]
+    if STATIC:
+      # (ResNet-50 has no depthwise layer: --int8_depthwise on would be the 'static on' row again)
+      best = ['--int8', 'auto', '--int8_depthwise', 'auto' if NET == 'mobilenet' else 'off']
+      routes = [('off', ['--act_ranges', 'batch', '--int8', 'off', '--int8_depthwise', 'off']),
+                ('batch best', ['--act_ranges', 'batch'] + best),
+                ('static off', ['--act_ranges', 'static', '--int8', 'off', '--int8_depthwise', 'off']),
+                ('static on', ['--act_ranges', 'static', '--int8', 'on', '--int8_depthwise', 'off']),
+                ] + ([('static on+dw', ['--act_ranges', 'static', '--int8', 'on', '--int8_depthwise', 'on'])] if NET == 'mobilenet' else []) + [
+                ('static auto', ['--act_ranges', 'static', '--int8', 'auto', '--int8_depthwise', 'auto'])]
+    else:
+      routes = [(mode, args + ['--act_ranges', 'batch']) for mode, args in routes]
     FLAGS.compute_dtype, FLAGS.synthetic_pool = 'bfloat16', 2
     FLAGS.uql_weight_bits = FLAGS.uql_activation_bits = 8
     FLAGS.uql_use_buckets, FLAGS.uql_bucket_type = True, 'channel'
@@ -62,6 +81,9 @@ def main():
     E.export_from_learner(learner, path)
     del learner
     torch.cuda.empty_cache()
+    if STATIC:
+      E.calibrate_act_ranges(mh, path, 2, 8, 'cuda', torch.bfloat16)
+      torch.cuda.empty_cache()
     common = net_args + ['--nb_classes', '1001', '--image_size', str(IMAGE), '--batch_size', str(B),
               '--compute_dtype', 'bfloat16', '--nb_repts_warmup', '5', '--nb_repts', str(REPTS), '--json', '--model_file', path,
               '--uql_activation_bits', '8']
@@ -75,12 +97,12 @@ def main():
           T.main(common + args)
         line = json.loads([ln for ln in buf.getvalue().splitlines() if ln.startswith('{')][-1])
         ms[mode].append(line['ms_per_batch'])
-        print('round %d  --int8 %-7s  %9.3f ms per batch  nb_int8_layers %3d (%d ran)'
-              % (rnd, mode, line['ms_per_batch'], line['nb_int8_layers'], line['nb_int8_layers_ran']))
+        print('round %d  --int8 %-12s  %9.3f ms per batch  nb_int8_layers %3d (%d ran, %d requantising)'
+              % (rnd, mode, line['ms_per_batch'], line['nb_int8_layers'], line['nb_int8_layers_ran'], line['nb_requant_layers']))
         torch.cuda.empty_cache()
     for mode, _ in routes:
       v = sorted(ms[mode])
-      print('--int8 %-7s  median %9.3f ms  spread %7.3f ms  (off / this %.3f)'
+      print('--int8 %-12s  median %9.3f ms  spread %7.3f ms  (off / this %.3f)'
             % (mode, v[len(v) // 2], v[-1] - v[0], sorted(ms['off'])[len(v) // 2] / v[len(v) // 2]))
 
 
