@@ -23,6 +23,19 @@ __device__ __forceinline__ float uqs_value(float level, float alpha, float beta,
   return alpha * (level / k) + beta;           // multiply, then add: two roundings, as uq_point
 }
 
+// the requantising step of the kernels on codes, four channels at a time: lv = the levels of act(scale * v + shift); scale / shift
+// point at the four channels' entries of the folded BatchNorm table (16-byte aligned)
+template <int ACT>
+__device__ __forceinline__ void uqs_requant4(const float* scale, const float* shift, const float* v, float* lv, float alpha, float beta,
+                                             float k) {
+  const float4 sc = *reinterpret_cast<const float4*>(scale);
+  const float4 sh = *reinterpret_cast<const float4*>(shift);
+  lv[0] = uqs_level(apply_act<ACT>(fmaf(sc.x, v[0], sh.x)), alpha, beta, k);
+  lv[1] = uqs_level(apply_act<ACT>(fmaf(sc.y, v[1], sh.y)), alpha, beta, k);
+  lv[2] = uqs_level(apply_act<ACT>(fmaf(sc.z, v[2], sh.z)), alpha, beta, k);
+  lv[3] = uqs_level(apply_act<ACT>(fmaf(sc.w, v[3], sh.w)), alpha, beta, k);
+}
+
 // N consecutive channels of one pixel, given as levels, stored as the output kind TO: uint8_t = codes (N bytes, one vector store of
 // N bytes), float / bf16_t = values.  p is aligned to the vector it takes (N bytes of codes, 16 bytes of float32, 2 N bytes of bf16).
 template <typename TO, int N> struct UqsStore;
@@ -66,6 +79,18 @@ template <typename F> static inline bool pf_with_out_kind(int out_kind, F&& f) {
   else if (out_kind == PF_OUT_BF16) f((bf16_t*)nullptr);
   else return false;
   return true;
+}
+// host: what every static entry checks of its output side.  `epilogue`: a kernel on codes, whose lanes store whole vectors (out and
+// scale_shift 16-byte aligned), which has at most 8 bits for every output kind and no instantiation for an unknown activation.  The
+// stand-alone pass takes up to 32 bits for a value output and any alignment (its scalar loop); an unknown activation there is none.
+static inline bool pf_static_out_ok(bool epilogue, int out_kind, int out_bits, int out_act, const void* out, const float* scale_shift,
+                                    const float* out_alpha_beta) {
+  if (out == nullptr || scale_shift == nullptr || out_alpha_beta == nullptr) return false;
+  if (out_kind != PF_OUT_CODES && out_kind != PF_OUT_F32 && out_kind != PF_OUT_BF16) return false;
+  if (out_bits < 1 || out_bits > (epilogue || out_kind == PF_OUT_CODES ? 8 : 32)) return false;
+  if (!epilogue) return true;
+  if (out_act != PF_ACT_NONE && out_act != PF_ACT_RELU && out_act != PF_ACT_RELU6) return false;
+  return pf_aligned16(out) && pf_aligned16(scale_shift);
 }
 static inline bool pf_out_aligned(int out_kind, const void* p, int n) {   // n consecutive channels per vector store
   const uintptr_t bytes = out_kind == PF_OUT_CODES ? (uintptr_t)n : out_kind == PF_OUT_F32 ? 16u : (uintptr_t)(2 * n > 16 ? 16 : 2 * n);

@@ -66,10 +66,8 @@ static int launch_bn_static(const T* x, void* out, int out_kind, int64_t rows, i
 
 extern "C" int pf_bn_act_quant_static(const void* x, void* out, int dtype, int out_kind, int64_t rows, int C, const float* scale_shift,
                                       int act, const float* out_alpha_beta, int bits, void* stream) {
-  if (rows <= 0 || C <= 0 || x == nullptr || out == nullptr || scale_shift == nullptr || out_alpha_beta == nullptr)
+  if (rows <= 0 || C <= 0 || x == nullptr || !pf_static_out_ok(false, out_kind, bits, act, out, scale_shift, out_alpha_beta))
     return (int)hipErrorInvalidValue;
-  if (out_kind != PF_OUT_CODES && out_kind != PF_OUT_F32 && out_kind != PF_OUT_BF16) return (int)hipErrorInvalidValue;
-  if (bits < 1 || bits > (out_kind == PF_OUT_CODES ? 8 : 32)) return (int)hipErrorInvalidValue;
   const float k = uq_k_of_bits(bits);
   if (dtype == PF_F32)
     return launch_bn_static<float>((const float*)x, out, out_kind, rows, C, scale_shift, act, out_alpha_beta, k, (hipStream_t)stream);

@@ -192,3 +192,31 @@ __device__ __forceinline__ void conv_i8_body(const I8Args& a, Emit&& emit) {
     }
   }
 }
+
+// ---- host side: checks, operands and launch geometry shared by the entries (residual and output are each entry's own) ------------
+extern "C" int pf_conv_i8_supported(int C, int N, int R, int S, int stride);
+
+static inline int i8_setup(I8Args& a, dim3& grid, const uint8_t* x, const int8_t* w, const float* act_alpha_beta, int act_bits,
+                           const float* w_scale_beta, const int32_t* w_tsum, const int32_t* w_tapsum, int imgs, int H, int W, int C,
+                           int N, int R, int S, int stride, int pad_h, int pad_w, int Ho, int Wo) {
+  if (!pf_conv_i8_supported(C, N, R, S, stride) || imgs <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0 || pad_h < 0 || pad_w < 0)
+    return (int)hipErrorInvalidValue;
+  if (act_bits < 1 || act_bits > 8 || x == nullptr || w == nullptr || act_alpha_beta == nullptr || w_scale_beta == nullptr ||
+      w_tsum == nullptr || w_tapsum == nullptr)
+    return (int)hipErrorInvalidValue;
+  // every output window lies inside the symmetrically padded image
+  if ((int64_t)(Ho - 1) * stride + R - 2 * pad_h > H || (int64_t)(Wo - 1) * stride + S - 2 * pad_w > W) return (int)hipErrorInvalidValue;
+  if (!pf_aligned16(x) || !pf_aligned16(w)) return (int)hipErrorInvalidValue;
+  a.x = x; a.w = w; a.ab = act_alpha_beta; a.wtab = w_scale_beta; a.tsum = w_tsum; a.dtap = w_tapsum; a.res = nullptr; a.y = nullptr;
+  a.imgs = imgs; a.H = H; a.W = W; a.C = C; a.N = N; a.R = R; a.S = S; a.stride = stride; a.pad_h = pad_h; a.pad_w = pad_w;
+  a.Ho = Ho; a.Wo = Wo;
+  a.K = R * S * C;
+  a.Kp = (a.K + I8_BK - 1) / I8_BK * I8_BK;
+  a.M = (int64_t)imgs * Ho * Wo;
+  a.ka = uq_k_of_bits(act_bits);
+  const int64_t gx = (a.M + I8_BM - 1) / I8_BM;
+  const int gy = (N + I8_BN - 1) / I8_BN;
+  if (gx > 0x7FFFFFFFll || gy > 65535) return (int)hipErrorInvalidValue;
+  grid = dim3((unsigned)gx, (unsigned)gy);
+  return 0;
+}

@@ -113,25 +113,13 @@ extern "C" int pf_conv_i8_supported(int C, int N, int R, int S, int stride) {
 extern "C" int pf_conv_i8_fwd(const uint8_t* x, const int8_t* w, const float* act_alpha_beta, int act_bits, const float* w_scale_beta,
                               const int32_t* w_tsum, const int32_t* w_tapsum, const void* res, void* y, int out_dtype, int imgs, int H,
                               int W, int C, int N, int R, int S, int stride, int pad_h, int pad_w, int Ho, int Wo, void* stream) {
-  if (!pf_conv_i8_supported(C, N, R, S, stride) || imgs <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0 || pad_h < 0 || pad_w < 0)
-    return (int)hipErrorInvalidValue;
-  if (act_bits < 1 || act_bits > 8 || x == nullptr || w == nullptr || act_alpha_beta == nullptr || w_scale_beta == nullptr ||
-      w_tsum == nullptr || w_tapsum == nullptr || y == nullptr)
-    return (int)hipErrorInvalidValue;
-  if ((int64_t)(Ho - 1) * stride + R - 2 * pad_h > H || (int64_t)(Wo - 1) * stride + S - 2 * pad_w > W) return (int)hipErrorInvalidValue;
-  if (!pf_aligned16(x) || !pf_aligned16(w) || !pf_aligned16(y) || !pf_aligned16(res)) return (int)hipErrorInvalidValue;
+  if (y == nullptr || !pf_aligned16(y) || !pf_aligned16(res)) return (int)hipErrorInvalidValue;
   I8Args a;
-  a.x = x; a.w = w; a.ab = act_alpha_beta; a.wtab = w_scale_beta; a.tsum = w_tsum; a.dtap = w_tapsum; a.res = res; a.y = y;
-  a.imgs = imgs; a.H = H; a.W = W; a.C = C; a.N = N; a.R = R; a.S = S; a.stride = stride; a.pad_h = pad_h; a.pad_w = pad_w;
-  a.Ho = Ho; a.Wo = Wo;
-  a.K = R * S * C;
-  a.Kp = (a.K + I8_BK - 1) / I8_BK * I8_BK;
-  a.M = (int64_t)imgs * Ho * Wo;
-  a.ka = uq_k_of_bits(act_bits);
-  const int64_t gx = (a.M + I8_BM - 1) / I8_BM;
-  if (gx > 0x7FFFFFFFll) return (int)hipErrorInvalidValue;
-  const dim3 grid((unsigned)gx, (unsigned)((N + I8_BN - 1) / I8_BN));
-  if (grid.y > 65535u) return (int)hipErrorInvalidValue;
+  dim3 grid;
+  const int err = i8_setup(a, grid, x, w, act_alpha_beta, act_bits, w_scale_beta, w_tsum, w_tapsum, imgs, H, W, C, N, R, S, stride, pad_h,
+                           pad_w, Ho, Wo);
+  if (err) return err;
+  a.res = res; a.y = y;
   hipStream_t st = (hipStream_t)stream;
   if (out_dtype == PF_F32) k_conv_i8<float><<<grid, PF_THREADS, 0, st>>>(a);
   else if (out_dtype == PF_BF16) k_conv_i8<bf16_t><<<grid, PF_THREADS, 0, st>>>(a);

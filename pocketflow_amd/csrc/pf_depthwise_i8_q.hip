@@ -25,14 +25,8 @@ __global__ __launch_bounds__(DWI_T) void k_dw_i8_q(const DwiArgs a, const DwiQAr
   dw_i8_body<ST>(a, [&](int64_t off, const float* v, int cg) {
     float lv[16];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float4 sc = *reinterpret_cast<const float4*>(q.ss + cg * 16 + 4 * i);
-      const float4 sh = *reinterpret_cast<const float4*>(q.ss + a.C + cg * 16 + 4 * i);
-      lv[4 * i] = uqs_level(apply_act<ACT>(fmaf(sc.x, v[4 * i], sh.x)), alpha, beta, q.ko);
-      lv[4 * i + 1] = uqs_level(apply_act<ACT>(fmaf(sc.y, v[4 * i + 1], sh.y)), alpha, beta, q.ko);
-      lv[4 * i + 2] = uqs_level(apply_act<ACT>(fmaf(sc.z, v[4 * i + 2], sh.z)), alpha, beta, q.ko);
-      lv[4 * i + 3] = uqs_level(apply_act<ACT>(fmaf(sc.w, v[4 * i + 3], sh.w)), alpha, beta, q.ko);
-    }
+    for (int i = 0; i < 4; ++i)
+      uqs_requant4<ACT>(q.ss + cg * 16 + 4 * i, q.ss + a.C + cg * 16 + 4 * i, v + 4 * i, lv + 4 * i, alpha, beta, q.ko);
     UqsStore<TO, 16>::run(o + off, lv, alpha, beta, q.ko);
   });
 }
@@ -44,11 +38,7 @@ extern "C" int pf_dw_i8_fwd_q(const uint8_t* x, const uint32_t* w_cols, const fl
                               void* out, int out_kind, int B, int H, int W, int C, int stride, int pad_h, int pad_w, int Ho, int Wo,
                               void* stream) {
   if (!pf_dw_i8_supported(C, 3, stride)) return (int)hipErrorInvalidValue;
-  if (out == nullptr || out_scale_shift == nullptr || out_alpha_beta == nullptr) return (int)hipErrorInvalidValue;
-  if (!pf_aligned16(out) || !pf_aligned16(out_scale_shift)) return (int)hipErrorInvalidValue;
-  if (out_kind != PF_OUT_CODES && out_kind != PF_OUT_F32 && out_kind != PF_OUT_BF16) return (int)hipErrorInvalidValue;
-  if (out_bits < 1 || out_bits > 8) return (int)hipErrorInvalidValue;
-  if (out_act != PF_ACT_NONE && out_act != PF_ACT_RELU && out_act != PF_ACT_RELU6) return (int)hipErrorInvalidValue;
+  if (!pf_static_out_ok(true, out_kind, out_bits, out_act, out, out_scale_shift, out_alpha_beta)) return (int)hipErrorInvalidValue;
   DwiArgs a;
   dim3 grid;
   const int err = dwi_setup(a, grid, x, w_cols, w_scale_beta, act_alpha_beta, act_bits, B, H, W, C, stride, pad_h, pad_w, Ho, Wo);

@@ -1737,8 +1737,9 @@ class Conv2D:
       raise RuntimeError('%s: a convolution packed for int8 runs in inference only: call it under torch.no_grad() on a graph '
                          'finalised with requires_grad=False' % self.kernel.name)
     if isinstance(x, CodesAct):
-      if self.int8 is not None and self._int8_geometry(x.x) is not None:
-        return self._call_int8(x, residual, requant)
+      geom = self._int8_geometry(x.x.shape, x.x.is_cuda) if self.int8 is not None else None
+      if geom is not None:
+        return self._call_int8(x, residual, requant, geom)
       x = x.materialize()                        # every other consumer: the fake-quantised tensor of the apply pass, as without int8
     if fused_conv1x1_ok(x, self):                # 1x1 on pf_conv.hip: the producer BN's normalise / act / fake-quant in the prologue
       lazy = x if isinstance(x, LazyAct) else None
@@ -1758,7 +1759,7 @@ class Conv2D:
                           self.stride, out_bn=out_bn)
     x = materialize(x)
     b = self.bias.tensor.to(x.dtype) if self.bias is not None else None
-    ph, pw, out_hw = self._geometry(x)
+    ph, pw, out_hw = self._geometry(x.shape)
     if (self.padding == 'SAME' and residual is None and x.shape[1] == 3 and self.k == 3 and self.stride == 2
         and own_stem3_ok(x, self, (ph[0], pw[0]), out_hw)):    # the MobileNet stem: asymmetric 'SAME' pads without a padded image copy
       if torch.is_grad_enabled() and w.requires_grad:
@@ -1790,17 +1791,17 @@ class Conv2D:
       y = F.conv2d(x, w, b, stride=self.stride, padding=pad)
     return y if residual is None else y + residual
 
-  def _geometry(self, x):
-    """What `self.padding` means for the input `x`: ((top, bottom), (left, right), (Ho, Wo)).  An int pads every side by that much;
+  def _geometry(self, shape):
+    """What `self.padding` means for an input of NCHW `shape`: ((top, bottom), (left, right), (Ho, Wo)).  An int pads every side by that much;
     TF 'SAME' puts the odd pixel at the END; 'VALID', 'SAME' with a 1x1 kernel and any other string pad nothing."""
     ph = pw = (0, 0)
     if isinstance(self.padding, int):
       ph = pw = (self.padding, self.padding)
     elif self.padding == 'SAME' and self.k > 1:
-      ph = _same_pads(x.shape[2], self.k, self.stride)
-      pw = _same_pads(x.shape[3], self.k, self.stride)
-    return ph, pw, (_out_size(x.shape[2], self.k, self.stride, ph[0] + ph[1]),
-                    _out_size(x.shape[3], self.k, self.stride, pw[0] + pw[1]))
+      ph = _same_pads(shape[2], self.k, self.stride)
+      pw = _same_pads(shape[3], self.k, self.stride)
+    return ph, pw, (_out_size(shape[2], self.k, self.stride, ph[0] + ph[1]),
+                    _out_size(shape[3], self.k, self.stride, pw[0] + pw[1]))
 
   def _call_gathered(self, x, residual, out_bn) -> torch.Tensor:
     """The shrunk layer: reduction over the kept input channels only (hip.conv_gather_fwd), with the epilogues the dense inference
@@ -1813,7 +1814,7 @@ class Conv2D:
                          'on a graph finalised with requires_grad=False' % var.name)
     if x.dim() != 4 or x.shape[1] != var.cin_full:
       raise ValueError('%s: input of shape %s, the layer has %d input channels' % (var.name, tuple(x.shape), var.cin_full))
-    ph, pw, (Ho, Wo) = self._geometry(x)
+    ph, pw, (Ho, Wo) = self._geometry(x.shape)
     x, pad = _symmetric_pads(x, ph, pw)
     x = _nhwc(x)
     B, C, H, Wd = x.shape
@@ -1834,44 +1835,34 @@ class Conv2D:
     """This layer will multiply the CODES of an input of this NCHW shape: it is packed, and no route ahead of the int8 kernel in
     __call__ (taps, a gather) takes the call."""
     return (self.int8 is not None and self.graph.taps is None and self.kernel.gather_host is None
-            and self._int8_geometry(_ShapeOnly(tuple(shape), is_cuda)) is not None)
+            and self._int8_geometry(shape, is_cuda) is not None)
 
-  def _int8_geometry(self, x):
-    """(pad_h, pad_w, Ho, Wo) where pf_conv_i8_fwd takes this layer on the input x, else None: symmetric pads only (it has no padded
-    copy to fall back on), no bias, a 4-D device tensor."""
-    if self.bias is not None or x.dim() != 4 or not x.is_cuda or x.shape[1] != self.kernel.ref_shape[2]:
+  def _int8_geometry(self, shape, is_cuda: bool):
+    """(pad_h, pad_w, Ho, Wo) where pf_conv_i8_fwd takes this layer on an input of NCHW `shape`, else None: symmetric pads only (it has
+    no padded copy to fall back on), no bias, a 4-D device tensor."""
+    if self.bias is not None or len(shape) != 4 or not is_cuda or shape[1] != self.kernel.ref_shape[2]:
       return None
-    ph, pw, (Ho, Wo) = self._geometry(x)
+    ph, pw, (Ho, Wo) = self._geometry(shape)
     if ph[0] != ph[1] or pw[0] != pw[1]:
       return None
     return ph[0], pw[0], Ho, Wo
 
-  def _call_int8(self, x: 'CodesAct', residual, requant=None) -> torch.Tensor:
+  def _call_int8(self, x: 'CodesAct', residual, requant, geom) -> torch.Tensor:
     """The packed layer on the i8 matrix cores: the producer's codes times the signed weights, scales and offsets in the epilogue
     (pocketflow_amd/int8.py states the formula), the residual added before the one rounding to the compute dtype.  `requant`: the
     quantising BatchNormAct that alone consumes the output, on a graph with fixed ranges: applied in the epilogue (pf_conv_i8_fwd_q),
-    the output being that layer's output -- codes where ITS consumer multiplies codes, the fake-quantised tensor otherwise."""
-    p = self.int8
-    pad_h, pad_w, Ho, Wo = self._int8_geometry(x.x)
-    codes, ab = x.codes()
-    B, C, H, Wd = codes.shape
+    the output being that layer's output -- codes where ITS consumer multiplies codes, the fake-quantised tensor otherwise.  `geom`:
+    what _int8_geometry returned for x."""
+    p, bits = self.int8, x.bits
+    pad_h, pad_w, Ho, Wo = geom
+    B, C, H, Wd = x.x.shape
     N = self.kernel.ref_shape[3]
-    if requant is not None:
-      ss, oab, as_codes = requant.requant_plan((B, N, Ho, Wo), codes.is_cuda)
-      out = torch.empty((B, N, Ho, Wo), dtype=torch.uint8 if as_codes else x.dtype, device=codes.device, memory_format=torch.channels_last)
-      with region('conv_i8_fwd_q', float(codes.numel() + out.numel() * out.element_size())):
-        hip.conv_i8_fwd_q(codes, p['w'], ab, x.bits, p['scale_beta'], p['tsum'], p['tapsum'], ss, requant.act, oab, requant.op.bits, out,
-                          B, H, Wd, C, N, self.k, self.k, self.stride, pad_h, pad_w, Ho, Wo)
-      self.graph.int8_ran.add(self.kernel.name)
-      self.graph.requant_ran.add(self.kernel.name)
-      return requant.requant_result(out, ss, oab, x.dtype)
-    y = torch.empty((B, N, Ho, Wo), dtype=x.dtype, device=codes.device, memory_format=torch.channels_last)
-    res = None if residual is None else _nhwc(residual).to(y.dtype)
-    with region('conv_i8_fwd', float(codes.numel() + y.numel() * y.element_size() * (2 if res is not None else 1))):
-      hip.conv_i8_fwd(codes, p['w'], ab, x.bits, p['scale_beta'], p['tsum'], p['tapsum'], y, B, H, Wd, C, N, self.k, self.k, self.stride,
-                      pad_h, pad_w, Ho, Wo, residual=res)
-    self.graph.int8_ran.add(self.kernel.name)
-    return y
+    dims = (B, H, Wd, C, N, self.k, self.k, self.stride, pad_h, pad_w, Ho, Wo)
+    return _run_on_codes(
+        self, x, (B, N, Ho, Wo), 'conv_i8_fwd', requant, residual,
+        lambda codes, ab, y, res: hip.conv_i8_fwd(codes, p['w'], ab, bits, p['scale_beta'], p['tsum'], p['tapsum'], y, *dims, residual=res),
+        lambda codes, ab, ss, oab, out: hip.conv_i8_fwd_q(codes, p['w'], ab, bits, p['scale_beta'], p['tsum'], p['tapsum'], ss, requant.act, oab,
+                                                          requant.op.bits, out, *dims))
 
   def plain(self, x: torch.Tensor) -> torch.Tensor:
     """The convolution alone on a materialised tensor (tracing / channel pruning)."""
@@ -1883,14 +1874,26 @@ class Conv2D:
       self.graph.taps, self.graph.fuse_conv1x1 = taps, fuse
 
 
-class _ShapeOnly(object):
-  """What the geometry checks read of a tensor, for a tensor that does not exist yet."""
-
-  def __init__(self, shape, is_cuda):
-    self.shape, self.is_cuda = shape, is_cuda
-
-  def dim(self):
-    return len(self.shape)
+def _run_on_codes(layer, x: 'CodesAct', shape, name: str, requant, residual, launch, launch_q):
+  """A packed layer on the codes of `x`, its output of NCHW `shape`: launch(codes, alpha_beta, y, residual) stores the output in the
+  compute dtype; with `requant` (the BatchNormAct applied in the epilogue) launch_q(codes, alpha_beta, scale_shift, out_alpha_beta, out)
+  stores that layer's output.  `name`: the region of the plain launch, name + '_q' that of the requantising one."""
+  g, var = layer.graph, layer.kernel
+  codes, ab = x.codes()
+  if requant is not None:
+    ss, oab, as_codes = requant.requant_plan(shape, codes.is_cuda)
+    out = torch.empty(shape, dtype=torch.uint8 if as_codes else x.dtype, device=codes.device, memory_format=torch.channels_last)
+    with region(name + '_q', float(codes.numel() + out.numel() * out.element_size())):
+      launch_q(codes, ab, ss, oab, out)
+    g.int8_ran.add(var.name)
+    g.requant_ran.add(var.name)
+    return requant.requant_result(out, ss, oab, x.dtype)
+  y = torch.empty(shape, dtype=x.dtype, device=codes.device, memory_format=torch.channels_last)
+  res = None if residual is None else _nhwc(residual).to(y.dtype)
+  with region(name, float(codes.numel() + y.numel() * y.element_size() * (2 if res is not None else 1))):
+    launch(codes, ab, y, res)
+  g.int8_ran.add(var.name)
+  return y
 
 
 class TapStop(Exception):
@@ -1988,7 +1991,7 @@ class DepthwiseConv2D:
       self.graph.taps = taps
 
   def takes_codes(self, shape, is_cuda: bool) -> bool:
-    """This layer will multiply the CODES of an input of this NCHW shape (the test of __call__ below)."""
+    """This layer will multiply the CODES of an input of this NCHW shape: it is packed and no tap takes the call."""
     return self.int8 is not None and self.graph.taps is None and len(shape) == 4 and bool(is_cuda) and shape[1] == self.channels
 
   def __call__(self, x, want_stats: bool = False, out_bn=None) -> torch.Tensor:
@@ -1999,7 +2002,7 @@ class DepthwiseConv2D:
       if torch.is_grad_enabled() and (self.kernel.tensor.requires_grad or (x.x if isinstance(x, LazyAct) else x).requires_grad):
         raise RuntimeError('%s: a depthwise convolution packed for int8 runs in inference only: call it under torch.no_grad() on a '
                            'graph finalised with requires_grad=False' % self.kernel.name)
-      if isinstance(x, CodesAct) and x.x.dim() == 4 and x.x.is_cuda and x.x.shape[1] == self.channels:
+      if isinstance(x, CodesAct) and self.takes_codes(x.x.shape, x.x.is_cuda):
         return self._call_int8(x, out_bn if (out_bn is not None and out_bn.requantises()) else None)
     x = materialize(x)                           # a CodesAct too: the fake-quantised tensor of the apply pass, as without int8
     if self.graph.taps is not None:
@@ -2023,25 +2026,15 @@ class DepthwiseConv2D:
     """The packed layer on pf_dw_i8_fwd: the producer's codes times the kernel's codes in integers, scales and offsets in the epilogue
     (pocketflow_amd/int8.py states the formula), one rounding to the compute dtype.  The BatchNorm behind it makes its own statistics
     pass (the output carries none).  `requant`: as in Conv2D._call_int8 (pf_dw_i8_fwd_q)."""
-    p = self.int8
-    codes, ab = x.codes()
-    B, C, H, Wd = codes.shape
-    ph, pw = _same_pads(H, self.k, self.stride), _same_pads(Wd, self.k, self.stride)
+    p, bits = self.int8, x.bits
+    B, C, H, Wd = x.x.shape
     Ho, Wo = -(-H // self.stride), -(-Wd // self.stride)
-    if requant is not None:
-      ss, oab, as_codes = requant.requant_plan((B, C, Ho, Wo), codes.is_cuda)
-      out = torch.empty((B, C, Ho, Wo), dtype=torch.uint8 if as_codes else x.dtype, device=codes.device, memory_format=torch.channels_last)
-      with region('dw_i8_fwd_q', float(codes.numel() + out.numel() * out.element_size())):
-        hip.dw_i8_fwd_q(codes, p['wcol'], p['scale_beta'], ab, x.bits, ss, requant.act, oab, requant.op.bits, out, B, H, Wd, C, self.stride,
-                        ph[0], pw[0], Ho, Wo)
-      self.graph.int8_ran.add(self.kernel.name)
-      self.graph.requant_ran.add(self.kernel.name)
-      return requant.requant_result(out, ss, oab, x.dtype)
-    y = torch.empty((B, C, Ho, Wo), dtype=x.dtype, device=codes.device, memory_format=torch.channels_last)
-    with region('dw_i8_fwd', float(codes.numel() + y.numel() * y.element_size())):
-      hip.dw_i8_fwd(codes, p['wcol'], p['scale_beta'], ab, x.bits, y, B, H, Wd, C, self.stride, ph[0], pw[0], Ho, Wo)
-    self.graph.int8_ran.add(self.kernel.name)
-    return y
+    dims = (B, H, Wd, C, self.stride, _same_pads(H, self.k, self.stride)[0], _same_pads(Wd, self.k, self.stride)[0], Ho, Wo)
+    return _run_on_codes(
+        self, x, (B, C, Ho, Wo), 'dw_i8_fwd', requant, None,
+        lambda codes, ab, y, res: hip.dw_i8_fwd(codes, p['wcol'], p['scale_beta'], ab, bits, y, *dims),
+        lambda codes, ab, ss, oab, out: hip.dw_i8_fwd_q(codes, p['wcol'], p['scale_beta'], ab, bits, ss, requant.act, oab, requant.op.bits, out,
+                                                        *dims))
 
 
 class Dense:
@@ -2234,14 +2227,16 @@ class BatchNormAct:
     rows = x.numel() // C
     if bits is None and lazy:
       return LazyAct(x, self._eval_scale_shift(x), self.act, None, None, rows, C)
+    # this layer hands out codes: every consumer may multiply them, and the one that does not materialises
+    as_codes = bits is not None and bits <= 8 and self.graph.int8 and self.codes_ok and x.is_cuda and x.dim() == 4
     if bits is not None and self._static():
       ss, ab = self._eval_scale_shift(x), self.graph.act_static[self.op.index]
-      if bits <= 8 and self.graph.int8 and self.codes_ok and x.is_cuda and x.dim() == 4:
+      if as_codes:
         return StaticCodesAct(x, ss, self.act, ab, bits, rows, C)
       q = torch.empty_like(x)
       hip.bn_act_quant_static(x, q, rows, C, ss, self.act, ab, bits)
       return q
-    if bits is not None and bits <= 8 and self.graph.int8 and self.codes_ok and x.is_cuda and x.dim() == 4:
+    if as_codes:
       return CodesAct(x, self._calibrated_scale_shift(x, slot), self.act, slot, bits, rows, C)
     q = torch.empty_like(x)
     if bits is None:

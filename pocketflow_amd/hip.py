@@ -770,24 +770,31 @@ def conv_i8_supported(C: int, N: int, R: int, S: int, stride: int) -> bool:
   return bool(_lib.pf_conv_i8_supported(c_int(C), c_int(N), c_int(R), c_int(S), c_int(stride)))
 
 
+def _conv_i8_operands(what: str, X, Wp, alpha_beta, w_scale_beta, w_tsum, w_tapsum, B, H, Wd, C, N, R, S, stride, pad_h, pad_w, Ho, Wo,
+                      types_ok: bool = True, types_note: str = '', sizes_ok: bool = True) -> None:
+  """The checks conv_i8_fwd and conv_i8_fwd_q share.  `types_ok` / `sizes_ok`: the verdict on the caller's own operands (residual,
+  output), refused with the same two messages; `types_note`: what the caller adds to the list of types."""
+  _dev(X)
+  Kp = -(-(R * S * C) // 64) * 64
+  if X.dtype != torch.uint8 or Wp.dtype != torch.int8 or alpha_beta.dtype != torch.float32 or w_scale_beta.dtype != torch.float32 or (
+      w_tsum.dtype != torch.int32 or w_tapsum.dtype != torch.int32) or not types_ok:
+    raise TypeError('%s: X uint8, Wp int8, tables float32 / int32%s' % (what, types_note))
+  if not conv_i8_supported(C, N, R, S, stride):
+    raise ValueError('%s: C=%d N=%d R=%d S=%d stride=%d is not eligible (pf_conv_i8_supported)' % (what, C, N, R, S, stride))
+  if X.numel() != B * H * Wd * C or Wp.numel() != N * Kp or alpha_beta.numel() < 2 or (
+      w_scale_beta.numel() != 2 * N or w_tsum.numel() != N or w_tapsum.numel() != N * R * S) or not sizes_ok:
+    raise ValueError('%s: operand sizes do not match B=%d H=%d W=%d C=%d N=%d R=%d S=%d Ho=%d Wo=%d' % (what, B, H, Wd, C, N, R, S, Ho, Wo))
+  if (Ho - 1) * stride + R - 2 * pad_h > H or (Wo - 1) * stride + S - 2 * pad_w > Wd:
+    raise ValueError('%s: the output extends beyond the symmetrically padded input' % what)
+
+
 def conv_i8_fwd(X, Wp, alpha_beta, act_bits: int, w_scale_beta, w_tsum, w_tapsum, Y, B: int, H: int, Wd: int, C: int, N: int, R: int,
                 S: int, stride: int, pad_h: int, pad_w: int, Ho: int, Wo: int, residual=None) -> None:
   """Y[B][Ho][Wo][N] (float32 / bf16) = the convolution of the DECODED operands, from X uint8 codes [B][H][Wd][C] and the packed
   layer of int8.pack_layer (Wp int8 [N][Kp], w_scale_beta [N][2], w_tsum [N], w_tapsum [N][R*S]) (+ residual of Y's type)."""
-  _dev(X)
-  Kp = -(-(R * S * C) // 64) * 64
-  if X.dtype != torch.uint8 or Wp.dtype != torch.int8 or alpha_beta.dtype != torch.float32 or w_scale_beta.dtype != torch.float32 or (
-      w_tsum.dtype != torch.int32 or w_tapsum.dtype != torch.int32) or (residual is not None and residual.dtype != Y.dtype):
-    raise TypeError('conv_i8_fwd: X uint8, Wp int8, tables float32 / int32, residual of the output type')
-  if not conv_i8_supported(C, N, R, S, stride):
-    raise ValueError('conv_i8_fwd: C=%d N=%d R=%d S=%d stride=%d is not eligible (pf_conv_i8_supported)' % (C, N, R, S, stride))
-  if X.numel() != B * H * Wd * C or Wp.numel() != N * Kp or Y.numel() != B * Ho * Wo * N or alpha_beta.numel() < 2 or (
-      w_scale_beta.numel() != 2 * N or w_tsum.numel() != N or w_tapsum.numel() != N * R * S) or (
-      residual is not None and residual.numel() != Y.numel()):
-    raise ValueError('conv_i8_fwd: operand sizes do not match B=%d H=%d W=%d C=%d N=%d R=%d S=%d Ho=%d Wo=%d'
-                     % (B, H, Wd, C, N, R, S, Ho, Wo))
-  if (Ho - 1) * stride + R - 2 * pad_h > H or (Wo - 1) * stride + S - 2 * pad_w > Wd:
-    raise ValueError('conv_i8_fwd: the output extends beyond the symmetrically padded input')
+  _conv_i8_operands('conv_i8_fwd', X, Wp, alpha_beta, w_scale_beta, w_tsum, w_tapsum, B, H, Wd, C, N, R, S, stride, pad_h, pad_w, Ho, Wo,
+                    types_ok=residual is None or residual.dtype == Y.dtype, types_note=', residual of the output type',
+                    sizes_ok=Y.numel() == B * Ho * Wo * N and (residual is None or residual.numel() == Y.numel()))
   _check(_lib.pf_conv_i8_fwd(_ptr(X), _ptr(Wp), _ptr(alpha_beta), c_int(int(act_bits)), _ptr(w_scale_beta), _ptr(w_tsum), _ptr(w_tapsum),
                              _ptr(residual), _ptr(Y), c_int(dtype_code(Y)), c_int(B), c_int(H), c_int(Wd), c_int(C), c_int(N), c_int(R),
                              c_int(S), c_int(stride), c_int(pad_h), c_int(pad_w), c_int(Ho), c_int(Wo), _stream()), 'pf_conv_i8_fwd')
@@ -798,18 +805,22 @@ def dw_i8_supported(C: int, k: int, stride: int) -> bool:
   return bool(_lib.pf_dw_i8_supported(c_int(C), c_int(k), c_int(stride)))
 
 
+def _dw_i8_operands(what: str, X, w_cols, w_scale_beta, alpha_beta, B, H, Wd, C, stride, Ho, Wo, sizes_ok: bool) -> None:
+  """The checks dw_i8_fwd and dw_i8_fwd_q share.  `sizes_ok`: the verdict on the caller's own output side, refused with the sizes message."""
+  _dev(X)
+  if X.dtype != torch.uint8 or w_cols.dtype != torch.int32 or alpha_beta.dtype != torch.float32 or w_scale_beta.dtype != torch.float32:
+    raise TypeError('%s: X uint8, w_cols int32, w_scale_beta and alpha_beta float32' % what)
+  if not dw_i8_supported(C, 3, stride):
+    raise ValueError('%s: C=%d stride=%d is not eligible (pf_dw_i8_supported)' % (what, C, stride))
+  if X.numel() != B * H * Wd * C or w_cols.numel() != 3 * C or alpha_beta.numel() < 2 or w_scale_beta.numel() != 2 or not sizes_ok:
+    raise ValueError('%s: operand sizes do not match B=%d H=%d W=%d C=%d Ho=%d Wo=%d' % (what, B, H, Wd, C, Ho, Wo))
+
+
 def dw_i8_fwd(X, w_cols, w_scale_beta, alpha_beta, act_bits: int, Y, B: int, H: int, Wd: int, C: int, stride: int, pad_h: int, pad_w: int,
               Ho: int, Wo: int) -> None:
   """Y[B][Ho][Wo][C] (float32 / bf16) = the depthwise 3x3 convolution of the DECODED operands, from X uint8 codes [B][H][Wd][C] and the
   tables of int8.pack_depthwise (w_cols uint32 [C][3] viewed as int32, w_scale_beta float32 [2]); pad_h / pad_w: the front pads."""
-  _dev(X)
-  if X.dtype != torch.uint8 or w_cols.dtype != torch.int32 or alpha_beta.dtype != torch.float32 or w_scale_beta.dtype != torch.float32:
-    raise TypeError('dw_i8_fwd: X uint8, w_cols int32, w_scale_beta and alpha_beta float32')
-  if not dw_i8_supported(C, 3, stride):
-    raise ValueError('dw_i8_fwd: C=%d stride=%d is not eligible (pf_dw_i8_supported)' % (C, stride))
-  if X.numel() != B * H * Wd * C or w_cols.numel() != 3 * C or Y.numel() != B * Ho * Wo * C or alpha_beta.numel() < 2 or (
-      w_scale_beta.numel() != 2):
-    raise ValueError('dw_i8_fwd: operand sizes do not match B=%d H=%d W=%d C=%d Ho=%d Wo=%d' % (B, H, Wd, C, Ho, Wo))
+  _dw_i8_operands('dw_i8_fwd', X, w_cols, w_scale_beta, alpha_beta, B, H, Wd, C, stride, Ho, Wo, Y.numel() == B * Ho * Wo * C)
   _check(_lib.pf_dw_i8_fwd(_ptr(X), _ptr(w_cols), _ptr(w_scale_beta), _ptr(alpha_beta), c_int(int(act_bits)), _ptr(Y),
                            c_int(dtype_code(Y)), c_int(B), c_int(H), c_int(Wd), c_int(C), c_int(stride), c_int(pad_h), c_int(pad_w),
                            c_int(Ho), c_int(Wo), _stream()), 'pf_dw_i8_fwd')
@@ -856,20 +867,9 @@ def conv_i8_fwd_q(X, Wp, alpha_beta, act_bits: int, w_scale_beta, w_tsum, w_taps
                   residual=None) -> None:
   """conv_i8_fwd whose epilogue applies the consumer's folded BatchNorm, activation and static quantiser: Out[B][Ho][Wo][N] as uint8
   codes or as the fake-quantised value, by its dtype.  A residual is refused by the library."""
-  _dev(X)
-  Kp = -(-(R * S * C) // 64) * 64
-  if X.dtype != torch.uint8 or Wp.dtype != torch.int8 or alpha_beta.dtype != torch.float32 or w_scale_beta.dtype != torch.float32 or (
-      w_tsum.dtype != torch.int32 or w_tapsum.dtype != torch.int32):
-    raise TypeError('conv_i8_fwd_q: X uint8, Wp int8, tables float32 / int32')
-  if not conv_i8_supported(C, N, R, S, stride):
-    raise ValueError('conv_i8_fwd_q: C=%d N=%d R=%d S=%d stride=%d is not eligible (pf_conv_i8_supported)' % (C, N, R, S, stride))
   kind = _static_operands('conv_i8_fwd_q', Out, out_scale_shift, out_alpha_beta, B * Ho * Wo * N, N, out_bits)
-  if X.numel() != B * H * Wd * C or Wp.numel() != N * Kp or alpha_beta.numel() < 2 or (
-      w_scale_beta.numel() != 2 * N or w_tsum.numel() != N or w_tapsum.numel() != N * R * S) or int(out_bits) > 8:
-    raise ValueError('conv_i8_fwd_q: operand sizes do not match B=%d H=%d W=%d C=%d N=%d R=%d S=%d Ho=%d Wo=%d'
-                     % (B, H, Wd, C, N, R, S, Ho, Wo))
-  if (Ho - 1) * stride + R - 2 * pad_h > H or (Wo - 1) * stride + S - 2 * pad_w > Wd:
-    raise ValueError('conv_i8_fwd_q: the output extends beyond the symmetrically padded input')
+  _conv_i8_operands('conv_i8_fwd_q', X, Wp, alpha_beta, w_scale_beta, w_tsum, w_tapsum, B, H, Wd, C, N, R, S, stride, pad_h, pad_w, Ho, Wo,
+                    sizes_ok=int(out_bits) <= 8)
   _check(_lib.pf_conv_i8_fwd_q(_ptr(X), _ptr(Wp), _ptr(alpha_beta), c_int(int(act_bits)), _ptr(w_scale_beta), _ptr(w_tsum), _ptr(w_tapsum),
                                _ptr(residual), _ptr(out_scale_shift), c_int(ACT_CODES[out_act]), _ptr(out_alpha_beta), c_int(int(out_bits)),
                                _ptr(Out), c_int(kind), c_int(B), c_int(H), c_int(Wd), c_int(C), c_int(N), c_int(R), c_int(S), c_int(stride),
@@ -880,14 +880,8 @@ def dw_i8_fwd_q(X, w_cols, w_scale_beta, alpha_beta, act_bits: int, out_scale_sh
                 H: int, Wd: int, C: int, stride: int, pad_h: int, pad_w: int, Ho: int, Wo: int) -> None:
   """dw_i8_fwd whose epilogue applies the consumer's folded BatchNorm, activation and static quantiser: Out[B][Ho][Wo][C] as uint8
   codes or as the fake-quantised value, by its dtype."""
-  _dev(X)
-  if X.dtype != torch.uint8 or w_cols.dtype != torch.int32 or alpha_beta.dtype != torch.float32 or w_scale_beta.dtype != torch.float32:
-    raise TypeError('dw_i8_fwd_q: X uint8, w_cols int32, w_scale_beta and alpha_beta float32')
-  if not dw_i8_supported(C, 3, stride):
-    raise ValueError('dw_i8_fwd_q: C=%d stride=%d is not eligible (pf_dw_i8_supported)' % (C, stride))
   kind = _static_operands('dw_i8_fwd_q', Out, out_scale_shift, out_alpha_beta, B * Ho * Wo * C, C, out_bits)
-  if X.numel() != B * H * Wd * C or w_cols.numel() != 3 * C or alpha_beta.numel() < 2 or w_scale_beta.numel() != 2 or int(out_bits) > 8:
-    raise ValueError('dw_i8_fwd_q: operand sizes do not match B=%d H=%d W=%d C=%d Ho=%d Wo=%d' % (B, H, Wd, C, Ho, Wo))
+  _dw_i8_operands('dw_i8_fwd_q', X, w_cols, w_scale_beta, alpha_beta, B, H, Wd, C, stride, Ho, Wo, int(out_bits) <= 8)
   _check(_lib.pf_dw_i8_fwd_q(_ptr(X), _ptr(w_cols), _ptr(w_scale_beta), _ptr(alpha_beta), c_int(int(act_bits)), _ptr(out_scale_shift),
                              c_int(ACT_CODES[out_act]), _ptr(out_alpha_beta), c_int(int(out_bits)), _ptr(Out), c_int(kind), c_int(B),
                              c_int(H), c_int(Wd), c_int(C), c_int(stride), c_int(pad_h), c_int(pad_w), c_int(Ho), c_int(Wo), _stream()),

@@ -194,11 +194,13 @@ def load_int8(model_helper, path: str, device='cuda', compute_dtype=torch.float3
   graph.frozen = True                            # the weights are fixed from here on
   graph.int8 = bool(packed) or bool(packed_dw)
   graph.nb_int8 = len(packed) + len(packed_dw)
+
+  def upload(table):
+    return torch.from_numpy(np.ascontiguousarray(table)).to(graph.device)
   for name, p in packed.items():
-    layers[name].int8 = {k: torch.from_numpy(np.ascontiguousarray(p[k])).to(graph.device) for k in ('w', 'scale_beta', 'tsum', 'tapsum')}
+    layers[name].int8 = {k: upload(p[k]) for k in ('w', 'scale_beta', 'tsum', 'tapsum')}
   for name, p in packed_dw.items():
-    dw_layers[name].int8 = {'wcol': torch.from_numpy(p['wcol'].view(np.int32)).to(graph.device),
-                            'scale_beta': torch.from_numpy(p['scale_beta']).to(graph.device)}
+    dw_layers[name].int8 = {'wcol': upload(p['wcol'].view(np.int32)), 'scale_beta': upload(p['scale_beta'])}
 
   if static:
     # each range into its slot, through the kernels a batch with that minimum / maximum would go through: the slot then decodes
@@ -210,14 +212,10 @@ def load_int8(model_helper, path: str, device='cuda', compute_dtype=torch.float3
         hip.minmax_tensor(torch.tensor(ranges[op.name], dtype=torch.float32, device=graph.device), graph.act_slots[op.index], None)
     graph.act_static = graph.act_alpha_beta()
 
-    def forward_static(images) -> torch.Tensor:
-      with torch.no_grad(), graph.as_default():
-        return model_helper.forward_eval(G.to_device_images(images, graph))   # the slots stay as loaded: nothing calibrates
-    return graph, forward_static
-
   def forward(images) -> torch.Tensor:
     with torch.no_grad(), graph.as_default():
-      graph.begin_step()                         # the activation quantisers calibrate on every batch
+      if not static:
+        graph.begin_step()                       # the activation quantisers calibrate on every batch; static: the slots stay as loaded
       return model_helper.forward_eval(G.to_device_images(images, graph))
   return graph, forward
 

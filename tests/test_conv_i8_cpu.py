@@ -179,3 +179,34 @@ def test_int8_kernels_compile_without_spills(tmp_path):
     assert sp == 0 and vg <= 256, (name, vg, sp)
     seen.append(name)
   assert sum('k_conv_i8' in n for n in seen) == 2 and sum('k_bn_codes' in n for n in seen) == 12
+
+
+def test_takes_codes_truth_table():
+  """`takes_codes(shape, is_cuda)` -- the one test of "this layer will multiply codes" that __call__ and a requantising producer
+  share -- on shapes alone: no tensor, no GPU, no finalised graph.  Stride 2 on 8 x 8 makes the 'SAME' pads (0, 1), which the
+  kernel on codes (symmetric pads only) does not take; on 7 x 7 they are (1, 1)."""
+  import torch
+  from pocketflow_amd import graph as G
+  g = G.Graph('model', 'cpu', torch.float32)
+  slot = {'packed': True}                                             # any non-None value: takes_codes only asks whether it is there
+  with g.as_default():
+    c1 = G.Conv2D(g, 'c1', 16, 8, 3, stride=1)
+    c2 = G.Conv2D(g, 'c2', 16, 8, 3, stride=2)
+    cb = G.Conv2D(g, 'cb', 16, 8, 3, stride=1, use_bias=True)
+    cg = G.Conv2D(g, 'cg', 16, 8, 3, stride=1)
+    dw = G.DepthwiseConv2D(g, 'dw', 48, 3, 1)
+  for layer in (c1, c2, cb, cg, dw):
+    assert not layer.takes_codes((2, layer.kernel.ref_shape[2], 8, 8), True)          # no slot
+    layer.int8 = slot
+  cg.kernel.gather_host = np.arange(8, dtype=np.int32)
+  assert c1.takes_codes((2, 16, 8, 8), True)
+  assert not c2.takes_codes((2, 16, 8, 8), True) and c2.takes_codes((2, 16, 7, 7), True)
+  assert not cb.takes_codes((2, 16, 8, 8), True)
+  assert not c1.takes_codes((2, 24, 8, 8), True)
+  assert not c1.takes_codes((2, 16), True)
+  assert not c1.takes_codes((2, 16, 8, 8), False)
+  assert not cg.takes_codes((2, 16, 8, 8), True)
+  assert dw.takes_codes((2, 48, 8, 8), True)
+  assert not dw.takes_codes((2, 32, 8, 8), True) and not dw.takes_codes((2, 48), True) and not dw.takes_codes((2, 48, 8, 8), False)
+  g.taps = {}
+  assert not c1.takes_codes((2, 16, 8, 8), True) and not dw.takes_codes((2, 48, 8, 8), True)

@@ -2,6 +2,8 @@
 
 The exact case pins the lane maps of v_mfma_i32_16x16x64_i8: with integer-valued scales every term of the layer formula is an
 integer below 2^24, so the float32 output has to equal the reference bit for bit."""
+from ctypes import c_int, c_void_p
+
 import numpy as np
 import pytest
 import torch
@@ -109,6 +111,60 @@ def test_entry_point_rejects_what_it_does_not_cover(hip):
     hip.conv_i8_fwd(c, *args, B, H, W, 16, 8, 1, 1, 2, 0, 0, H, W)
   with pytest.raises(TypeError):
     hip.conv_i8_fwd(c.float(), *args, B, H, W, 16, 8, 1, 1, 1, 0, 0, H, W)
+
+
+def _small_operands():
+  """2 images of 6 x 6, 16 -> 8 channels, 1 x 1, codes all 0 and unit scales (every output is 0); the output holds a canary."""
+  p = _layer(np.random.default_rng(0), 16, 8, 1, 8, np.ones(8), np.zeros(8))
+  x = torch.zeros((B, 6, 6, 16), dtype=torch.uint8, device='cuda')
+  ab = torch.tensor([1.0, 0.0], device='cuda')
+  y = torch.full((B, 6, 6, 8), 12345.0, device='cuda')
+  return x, dev(p['w']), ab, dev(p['scale_beta']), dev(p['tsum']), dev(p['tapsum']), y
+
+
+def test_c_entry_refuses_what_it_does_not_cover(hip):
+  """pf_conv_i8_fwd itself (its checks are the setup shared with pf_conv_i8_fwd_q plus its own operands): every defect returns
+  non-zero before a launch and leaves the canary-filled output untouched; the same call with nothing wrong is taken."""
+  lib = hip._lib
+  ptr = lambda t: c_void_p(0 if t is None else t.data_ptr())
+  good = _small_operands()
+  y = good[-1]
+
+  def call(x, w, ab, wtab, tsum, tap, y_, C=16, stride=1, act_bits=8, dtype=hip.PF_F32, Ho=6):
+    return lib.pf_conv_i8_fwd(ptr(x), ptr(w), ptr(ab), c_int(act_bits), ptr(wtab), ptr(tsum), ptr(tap), c_void_p(0), ptr(y_), c_int(dtype),
+                              c_int(B), c_int(6), c_int(6), c_int(C), c_int(8), c_int(1), c_int(1), c_int(stride), c_int(0), c_int(0),
+                              c_int(Ho), c_int(Ho), c_void_p(0))
+  for i in range(len(good)):
+    assert call(*[None if j == i else t for j, t in enumerate(good)]) != 0, i
+  assert call(*good, C=24) != 0 and call(*good, stride=3) != 0
+  assert call(*good, act_bits=0) != 0 and call(*good, act_bits=9) != 0
+  assert call(*good, dtype=7) != 0
+  assert call(*good, stride=2) != 0                                   # Ho = H at stride 2: the output window leaves the input
+  torch.cuda.synchronize()
+  assert bool((y == 12345.0).all())
+  assert call(*good) == 0
+  torch.cuda.synchronize()
+  assert bool((y == 0.0).all())
+
+
+def test_requantising_wrapper_refuses_what_it_does_not_cover(hip):
+  """hip.conv_i8_fwd_q shares its operand checks with hip.conv_i8_fwd: the same defects, refused under its own name."""
+  x, w, ab, wtab, tsum, tap, _ = _small_operands()
+  ss, oab = torch.ones(2 * 8, device='cuda'), torch.tensor([1.0, 0.0], device='cuda')
+  out = torch.zeros((B, 6, 6, 8), dtype=torch.uint8, device='cuda')
+
+  def call(x_=x, out_=out, stride=1, bits=8):
+    hip.conv_i8_fwd_q(x_, w, ab, 8, wtab, tsum, tap, ss, 'Relu', oab, bits, out_, B, 6, 6, 16, 8, 1, 1, stride, 0, 0, 6, 6)
+  with pytest.raises(ValueError, match='^conv_i8_fwd_q: .*not eligible'):
+    call(stride=3)
+  with pytest.raises(ValueError, match='^conv_i8_fwd_q: .*beyond'):
+    call(stride=2)
+  with pytest.raises(TypeError, match='^conv_i8_fwd_q: '):
+    call(x_=x.float())
+  with pytest.raises(ValueError, match='^conv_i8_fwd_q: '):
+    call(bits=9)
+  with pytest.raises(ValueError, match='^conv_i8_fwd_q: '):
+    call(out_=out.float(), bits=9)                                    # a value output: still at most 8 bits in an epilogue
 
 
 # ------------------------------------------------------------------------------------------------

@@ -176,14 +176,14 @@ def test_general_parameters_and_determinism(hip, ref_large, H, W, C, stride):
 
 
 def test_entry_point_rejects_what_it_does_not_cover(hip):
-  """C = 24, stride 3 and a null pointer return non-zero from the C entry and leave a canary-filled output untouched; k = 5 is refused
-  by the predicate (the forward entry is 3 x 3 only and takes no k)."""
+  """C = 24, stride 3, 0 or 9 activation bits, an unknown output dtype and a null pointer return non-zero from the C entry and leave a
+  canary-filled output untouched; k = 5 is refused by the predicate (the forward entry is 3 x 3 only and takes no k)."""
   H = W = 6
   lib = hip._lib
 
-  def call(x, wcol, wsb, ab, y, C, stride):
+  def call(x, wcol, wsb, ab, y, C, stride, act_bits=8, dtype=0):
     ptr = lambda t: c_void_p(0 if t is None else t.data_ptr())
-    return lib.pf_dw_i8_fwd(ptr(x), ptr(wcol), ptr(wsb), ptr(ab), c_int(8), ptr(y), c_int(hip.PF_F32), c_int(B), c_int(H), c_int(W),
+    return lib.pf_dw_i8_fwd(ptr(x), ptr(wcol), ptr(wsb), ptr(ab), c_int(act_bits), ptr(y), c_int(dtype), c_int(B), c_int(H), c_int(W),
                             c_int(C), c_int(stride), c_int(1), c_int(1), c_int(H), c_int(W), c_void_p(0))
   x = torch.zeros((B, H, W, 48), dtype=torch.uint8, device='cuda')
   wcol = torch.zeros((48, 3), dtype=torch.int32, device='cuda')
@@ -191,10 +191,12 @@ def test_entry_point_rejects_what_it_does_not_cover(hip):
   ab = torch.tensor([1.0, 0.0], device='cuda')
   y = torch.full((B, H, W, 48), 12345.0, device='cuda')
   assert call(x, wcol, wsb, ab, y, 24, 1) != 0
-  assert call(x, wcol, wsb, ab, y, 16, 3) != 0
+  assert call(x, wcol, wsb, ab, y, 16, 3) != 0 and call(x, wcol, wsb, ab, y, 48, 3) != 0
+  assert call(x, wcol, wsb, ab, y, 48, 1, act_bits=0) != 0 and call(x, wcol, wsb, ab, y, 48, 1, act_bits=9) != 0
+  assert call(x, wcol, wsb, ab, y, 48, 1, dtype=7) != 0
   assert not hip.dw_i8_supported(16, 5, 1) and not hip.dw_i8_supported(24, 3, 1) and not hip.dw_i8_supported(16, 3, 3)
   for args in ((None, wcol, wsb, ab, y), (x, None, wsb, ab, y), (x, wcol, None, ab, y), (x, wcol, wsb, None, y), (x, wcol, wsb, ab, None)):
-    assert call(*args, 16, 1) != 0
+    assert call(*args, 16, 1) != 0 and call(*args, 48, 1) != 0
   torch.cuda.synchronize()
   assert bool((y == 12345.0).all())
   with pytest.raises(ValueError, match='not eligible'):
@@ -204,3 +206,24 @@ def test_entry_point_rejects_what_it_does_not_cover(hip):
   assert call(x, wcol, wsb, ab, y, 48, 1) == 0                       # the same call with nothing wrong is taken
   torch.cuda.synchronize()
   assert bool((y == 0.0).all())
+
+
+def test_requantising_wrapper_refuses_what_it_does_not_cover(hip):
+  """hip.dw_i8_fwd_q shares its operand checks with hip.dw_i8_fwd: the same defects, refused under its own name."""
+  H = W = 6
+  x = torch.zeros((B, H, W, 48), dtype=torch.uint8, device='cuda')
+  wcol = torch.zeros((48, 3), dtype=torch.int32, device='cuda')
+  wsb, ss = torch.ones(2, device='cuda'), torch.ones(2 * 48, device='cuda')
+  ab = oab = torch.tensor([1.0, 0.0], device='cuda')
+  out = torch.zeros((B, H, W, 48), dtype=torch.uint8, device='cuda')
+
+  def call(x_=x, out_=out, stride=1, bits=8):
+    hip.dw_i8_fwd_q(x_, wcol, wsb, ab, 8, ss, 'Relu6', oab, bits, out_, B, H, W, 48, stride, 1, 1, H, W)
+  with pytest.raises(ValueError, match='^dw_i8_fwd_q: .*not eligible'):
+    call(stride=3)
+  with pytest.raises(TypeError, match='^dw_i8_fwd_q: '):
+    call(x_=x.float())
+  with pytest.raises(ValueError, match='^dw_i8_fwd_q: '):
+    call(bits=9)
+  with pytest.raises(ValueError, match='^dw_i8_fwd_q: '):
+    call(out_=out.float(), bits=9)                                    # a value output: still at most 8 bits in an epilogue

@@ -30,15 +30,33 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import numpy as np
 import torch
-from _timing import gpu_time_us
-from pocketflow_amd import hip, int8
-from pocketflow_amd.tools.conversion import export_quant_int8_model as ex
+from _int8_layers import conv_layer, nhwc, time_rounds
+from pocketflow_amd import hip
 from gather_conv_layers import MOBILENET, RESNET50
 
 B = int(os.environ.get('B', 256))
 MFMA_PEAK, HBM_PEAK = 2.5e15, 8.0e12
+NETS = (('resnet50', RESNET50), ('mobilenet', MOBILENET))
+
+
+def eligible(net, layers):
+  """(label of the row, H, C, N, k, stride, pad, count) of the layers the i8 kernel takes; the others are printed as such."""
+  for name, H, C, N, k, stride, pad, _lazy, cnt in layers:
+    label = '%-10s %-20s %-22s %2d' % (net, name, '%d,%d,%d,%d,%d' % (H, C, N, k, stride), cnt)
+    if not hip.conv_i8_supported(C, N, k, k, stride) or (k > 1 and C % 64):
+      print(label + ' | not eligible')
+      continue
+    yield label, H, C, N, k, stride, pad, cnt
+
+
+def float_conv(xq, wfull, y, H, C, N, k, stride, pad, Ho):
+  """The launch of the bf16 kernel Conv2D dispatches the shape to."""
+  if k == 1:
+    geom = None if stride == 1 else (Ho, Ho, H, H, stride)
+    w2 = wfull.reshape(N, C)
+    return lambda: hip.conv1x1_fwd(xq, w2, y, B * Ho * Ho, N, C, geom=geom)
+  return lambda: hip.conv2d_fwd(xq, wfull, y, B, H, H, C, N, k, k, stride, pad, pad, Ho, Ho)
 
 
 def main_static():
@@ -47,12 +65,9 @@ def main_static():
         '20 captured launches); spread = max - min over the rounds' % (B, rounds))
   print('%-10s %-20s %-22s %2s | %9s %9s %9s | %9s | %7s | %8s %8s | %4s' % (
       'net', 'layer', 'H,C,N,k,stride', 'n', 'bf16 us', 'static us', 'float us', 'i8_q us', 'f / i8', 'f spread', 'i spread', 'pays'))
-  for net, layers in (('resnet50', RESNET50), ('mobilenet', MOBILENET)):
+  for net, layers in NETS:
     tot_f = tot_i = 0.0
-    for name, H, C, N, k, stride, pad, _lazy, cnt in layers:
-      if not hip.conv_i8_supported(C, N, k, k, stride) or (k > 1 and C % 64):
-        print('%-10s %-20s %-22s %2d | not eligible' % (net, name, '%d,%d,%d,%d,%d' % (H, C, N, k, stride), cnt))
-        continue
+    for label, H, C, N, k, stride, pad, cnt in eligible(net, layers):
       Ho = (H + 2 * pad - k) // stride + 1
       M = B * Ho * Ho
       g = torch.Generator(device='cuda').manual_seed(H + C + N + k)
@@ -61,22 +76,9 @@ def main_static():
       ab = torch.tensor([4.0, 0.0], device='cuda')
       oab = torch.tensor([3.0, 0.0], device='cuda')
       ss = torch.stack([torch.rand(N, device='cuda') * 0.1 + 0.05, torch.randn(N, device='cuda')]).contiguous()
-      rng = np.random.RandomState(C + N)
-      d = rng.randint(0, 256, size=(k, k, C, N)).astype(np.uint8)
-      alpha, beta = rng.uniform(0.05, 0.6, N).astype(np.float32), -rng.uniform(0.02, 0.3, N).astype(np.float32)
-      meta = np.array([8, ex.MODE_CHANNEL, 0, k, k, C, N], np.int64)
-      p = int8.pack_layer(ex.pack_codes(d.reshape(-1), 8), alpha, beta, meta)
-      wdec = ex.decode_tensor(ex.pack_codes(d.reshape(-1), 8), alpha, beta, meta)
-      wfull = torch.from_numpy(np.ascontiguousarray(wdec.transpose(3, 0, 1, 2))).cuda().bfloat16()
-      pw, psb, pts, ptp = (torch.from_numpy(np.ascontiguousarray(p[key])).cuda() for key in ('w', 'scale_beta', 'tsum', 'tapsum'))
-      y = torch.empty((B, N, Ho, Ho), dtype=torch.bfloat16, device='cuda').contiguous(memory_format=torch.channels_last)
-      out = torch.empty((B, N, Ho, Ho), dtype=torch.uint8, device='cuda').contiguous(memory_format=torch.channels_last)
-      if k == 1:
-        geom = None if stride == 1 else (Ho, Ho, H, H, stride)
-        w2 = wfull.reshape(N, C)
-        conv_f = lambda: hip.conv1x1_fwd(xq, w2, y, M, N, C, geom=geom)
-      else:
-        conv_f = lambda: hip.conv2d_fwd(xq, wfull, y, B, H, H, C, N, k, k, stride, pad, pad, Ho, Ho)
+      wfull, (pw, psb, pts, ptp) = conv_layer(k, C, N)
+      y, out = nhwc((B, N, Ho, Ho), torch.bfloat16), nhwc((B, N, Ho, Ho), torch.uint8)
+      conv_f = float_conv(xq, wfull, y, H, C, N, k, stride, pad, Ho)
       static_f = lambda: hip.bn_act_quant_static(y, out, M, N, ss, 'Relu', oab, 8)
       conv_q = lambda: hip.conv_i8_fwd_q(codes, pw, ab, 8, psb, pts, ptp, ss, 'Relu', oab, 8, out, B, H, H, C, N, k, k, stride, pad, pad,
                                          Ho, Ho)
@@ -84,16 +86,11 @@ def main_static():
       def route_f():
         conv_f()
         static_f()
-      t = {key: [] for key in ('bf16', 'static', 'float', 'int8')}
-      for _ in range(rounds):
-        for key, fn in (('bf16', conv_f), ('static', static_f), ('float', route_f), ('int8', conv_q)):
-          t[key].append(gpu_time_us(fn))
-      spread_f, spread_i = max(t['float']) - min(t['float']), max(t['int8']) - min(t['int8'])
-      t = {key: min(v) for key, v in t.items()}
-      pays = t['float'] - t['int8'] > max(spread_f, spread_i)
-      print('%-10s %-20s %-22s %2d | %9.1f %9.1f %9.1f | %9.1f | %7.2f | %8.1f %8.1f | %4s' % (
-          net, name, '%d,%d,%d,%d,%d' % (H, C, N, k, stride), cnt, t['bf16'], t['static'], t['float'], t['int8'], t['float'] / t['int8'],
-          spread_f, spread_i, 'yes' if pays else 'no'))
+      t, spread = time_rounds((('bf16', conv_f), ('static', static_f), ('float', route_f), ('int8', conv_q)), rounds)
+      pays = t['float'] - t['int8'] > max(spread['float'], spread['int8'])
+      print('%s | %9.1f %9.1f %9.1f | %9.1f | %7.2f | %8.1f %8.1f | %4s' % (
+          label, t['bf16'], t['static'], t['float'], t['int8'], t['float'] / t['int8'], spread['float'], spread['int8'],
+          'yes' if pays else 'no'))
       tot_f += cnt * t['float']
       tot_i += cnt * t['int8']
       del xq, y, codes, out
@@ -106,12 +103,9 @@ def main():
         'launches); bound = max(FLOPs / peak, bytes / 8 TB/s)' % B)
   print('%-10s %-20s %-22s %2s | %9s %9s %9s | %9s %9s %9s | %7s | %7s %7s' % (
       'net', 'layer', 'H,C,N,k,stride', 'n', 'apply us', 'bf16 us', 'float us', 'codes us', 'i8 us', 'int8 us', 'f / i8', 'f bound', 'i bound'))
-  for net, layers in (('resnet50', RESNET50), ('mobilenet', MOBILENET)):
+  for net, layers in NETS:
     tot_f = tot_i = 0.0
-    for name, H, C, N, k, stride, pad, _lazy, cnt in layers:
-      if not hip.conv_i8_supported(C, N, k, k, stride) or (k > 1 and C % 64):
-        print('%-10s %-20s %-22s %2d | not eligible' % (net, name, '%d,%d,%d,%d,%d' % (H, C, N, k, stride), cnt))
-        continue
+    for label, H, C, N, k, stride, pad, cnt in eligible(net, layers):
       Ho = (H + 2 * pad - k) // stride + 1
       M = B * Ho * Ho
       rows = B * H * H
@@ -119,27 +113,15 @@ def main():
       x = torch.randn((B, C, H, H), device='cuda', generator=g).bfloat16().contiguous(memory_format=torch.channels_last)
       ss = torch.stack([torch.rand(C, device='cuda') + 0.5, torch.randn(C, device='cuda')]).contiguous()
       xq = torch.empty_like(x)
-      codes = torch.empty(x.shape, dtype=torch.uint8, device='cuda').contiguous(memory_format=torch.channels_last)
+      codes = nhwc(x.shape, torch.uint8)
       ab = torch.empty(2, device='cuda')
       slot = torch.empty((1, 2), dtype=torch.int32, device='cuda')
       hip.minmax_slots_init(slot)
       hip.bn_act_quant_apply(x, xq, rows, C, ss, 'Relu', None, 8, False)
       hip.minmax_tensor(xq, slot[0])
-      rng = np.random.RandomState(C + N)
-      d = rng.randint(0, 256, size=(k, k, C, N)).astype(np.uint8)
-      alpha, beta = rng.uniform(0.05, 0.6, N).astype(np.float32), -rng.uniform(0.02, 0.3, N).astype(np.float32)
-      meta = np.array([8, ex.MODE_CHANNEL, 0, k, k, C, N], np.int64)
-      p = int8.pack_layer(ex.pack_codes(d.reshape(-1), 8), alpha, beta, meta)
-      wdec = ex.decode_tensor(ex.pack_codes(d.reshape(-1), 8), alpha, beta, meta)
-      wfull = torch.from_numpy(np.ascontiguousarray(wdec.transpose(3, 0, 1, 2))).cuda().bfloat16()
-      pw, psb, pts, ptp = (torch.from_numpy(np.ascontiguousarray(p[key])).cuda() for key in ('w', 'scale_beta', 'tsum', 'tapsum'))
-      y = torch.empty((B, N, Ho, Ho), dtype=torch.bfloat16, device='cuda').contiguous(memory_format=torch.channels_last)
-      if k == 1:
-        geom = None if stride == 1 else (Ho, Ho, H, H, stride)
-        w2 = wfull.reshape(N, C)
-        conv_f = lambda: hip.conv1x1_fwd(xq, w2, y, M, N, C, geom=geom)
-      else:
-        conv_f = lambda: hip.conv2d_fwd(xq, wfull, y, B, H, H, C, N, k, k, stride, pad, pad, Ho, Ho)
+      wfull, (pw, psb, pts, ptp) = conv_layer(k, C, N)
+      y = nhwc((B, N, Ho, Ho), torch.bfloat16)
+      conv_f = float_conv(xq, wfull, y, H, C, N, k, stride, pad, Ho)
       apply_f = lambda: hip.bn_act_quant_apply(x, xq, rows, C, ss, 'Relu', slot[0], 8, True)
       codes_f = lambda: hip.bn_act_quant_codes(x, codes, rows, C, ss, 'Relu', slot[0], 8, ab)
       conv_i = lambda: hip.conv_i8_fwd(codes, pw, ab, 8, psb, pts, ptp, y, B, H, H, C, N, k, k, stride, pad, pad, Ho, Ho)
@@ -151,20 +133,16 @@ def main():
       def route_i():
         codes_f()
         conv_i()
-      t = {key: [] for key in ('apply', 'bf16', 'float', 'codes', 'i8', 'int8')}
-      for _ in range(2):                          # alternate the two routes
-        for key, fn in (('apply', apply_f), ('bf16', conv_f), ('float', route_f), ('codes', codes_f), ('i8', conv_i), ('int8', route_i)):
-          t[key].append(gpu_time_us(fn))
-      t = {key: min(v) for key, v in t.items()}
+      t, _ = time_rounds((('apply', apply_f), ('bf16', conv_f), ('float', route_f), ('codes', codes_f), ('i8', conv_i), ('int8', route_i)), 2)
       flops = 2.0 * M * N * k * k * C
       read = rows * C // (stride * stride if k == 1 else 1)
       bytes_f = rows * C * 4 + read * 2 + M * N * 2 + N * k * k * C * 2
       bytes_i = rows * C * 3 + read + M * N * 2 + N * k * k * C
       bound_f = max(flops / MFMA_PEAK, bytes_f / HBM_PEAK) * 1e6
       bound_i = max(flops / (2 * MFMA_PEAK), bytes_i / HBM_PEAK) * 1e6
-      print('%-10s %-20s %-22s %2d | %9.1f %9.1f %9.1f | %9.1f %9.1f %9.1f | %7.2f | %7.2f %7.2f' % (
-          net, name, '%d,%d,%d,%d,%d' % (H, C, N, k, stride), cnt, t['apply'], t['bf16'], t['float'], t['codes'], t['i8'], t['int8'],
-          t['float'] / t['int8'], bound_f / t['float'], bound_i / t['int8']))
+      print('%s | %9.1f %9.1f %9.1f | %9.1f %9.1f %9.1f | %7.2f | %7.2f %7.2f' % (
+          label, t['apply'], t['bf16'], t['float'], t['codes'], t['i8'], t['int8'], t['float'] / t['int8'], bound_f / t['float'],
+          bound_i / t['int8']))
       tot_f += cnt * t['float']
       tot_i += cnt * t['int8']
       del x, xq, y, codes

@@ -29,11 +29,9 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import numpy as np
 import torch
-from _timing import gpu_time_us
+from _int8_layers import depthwise_layer, nhwc, time_rounds
 from pocketflow_amd import hip, int8
-from pocketflow_amd.tools.conversion import export_quant_int8_model as ex
 
 B = int(os.environ.get('B', 256))
 ROUNDS = int(os.environ.get('ROUNDS', 3))
@@ -60,17 +58,8 @@ def main_static():
     ab = torch.tensor([6.0, 0.0], device='cuda')
     oab = torch.tensor([4.5, 0.0], device='cuda')                  # narrower than ReLU6's image: the clamp acts
     ss = torch.stack([torch.rand(C, device='cuda') * 0.2 + 0.1, torch.randn(C, device='cuda')]).contiguous()
-    rng = np.random.RandomState(C + stride)
-    d = rng.randint(0, 256, size=(3, 3, C, 1)).astype(np.uint8)
-    alpha, beta = rng.uniform(0.05, 0.6, 1).astype(np.float32), -rng.uniform(0.02, 0.3, 1).astype(np.float32)
-    meta = np.array([8, ex.MODE_TENSOR, 0, 3, 3, C, 1], np.int64)
-    p = int8.pack_depthwise(ex.pack_codes(d.reshape(-1), 8), alpha, beta, meta)
-    wdec = ex.decode_tensor(ex.pack_codes(d.reshape(-1), 8), alpha, beta, meta)
-    wcrs = torch.from_numpy(np.ascontiguousarray(wdec[..., 0].transpose(2, 0, 1))).cuda().bfloat16()
-    wcol = torch.from_numpy(p['wcol'].view(np.int32)).cuda()
-    wsb = torch.from_numpy(p['scale_beta']).cuda()
-    y = torch.empty((B, C, Ho, Ho), dtype=torch.bfloat16, device='cuda').contiguous(memory_format=torch.channels_last)
-    out = torch.empty((B, C, Ho, Ho), dtype=torch.uint8, device='cuda').contiguous(memory_format=torch.channels_last)
+    wcrs, wcol, wsb = depthwise_layer(C, stride)
+    y, out = nhwc((B, C, Ho, Ho), torch.bfloat16), nhwc((B, C, Ho, Ho), torch.uint8)
     partial = torch.empty((hip.depthwise_groups(B, Ho, Ho, C), 4, C), dtype=torch.float32, device='cuda')
     dw_f = lambda: hip.depthwise_fwd(xq, wcrs, y, B, H, H, C, 3, stride, pad, pad, Ho, Ho, partial=partial)
     static_f = lambda: hip.bn_act_quant_static(y, out, M, C, ss, 'Relu6', oab, 8)
@@ -79,12 +68,8 @@ def main_static():
     def route_f():
       dw_f()
       static_f()
-    t = {key: [] for key in ('dw', 'static', 'float', 'int8')}
-    for _ in range(ROUNDS):
-      for key, fn in (('dw', dw_f), ('static', static_f), ('float', route_f), ('int8', dw_q)):
-        t[key].append(gpu_time_us(fn))
-    spread_f, spread_i = max(t['float']) - min(t['float']), max(t['int8']) - min(t['int8'])
-    t = {key: min(v) for key, v in t.items()}
+    t, spread = time_rounds((('dw', dw_f), ('static', static_f), ('float', route_f), ('int8', dw_q)), ROUNDS)
+    spread_f, spread_i = spread['float'], spread['int8']
     bound_f = (rows * C * 2 + M * C * 5) / HBM_PEAK * 1e6
     bound_i = (rows * C + M * C) / HBM_PEAK * 1e6
     pays = t['float'] - t['int8'] > max(spread_f, spread_i)
@@ -113,22 +98,14 @@ def main():
     x = torch.randn((B, C, H, H), device='cuda', generator=g).bfloat16().contiguous(memory_format=torch.channels_last)
     ss = torch.stack([torch.rand(C, device='cuda') + 0.5, torch.randn(C, device='cuda')]).contiguous()
     xq = torch.empty_like(x)
-    codes = torch.empty(x.shape, dtype=torch.uint8, device='cuda').contiguous(memory_format=torch.channels_last)
+    codes = nhwc(x.shape, torch.uint8)
     ab = torch.empty(2, device='cuda')
     slot = torch.empty((1, 2), dtype=torch.int32, device='cuda')
     hip.minmax_slots_init(slot)
     hip.bn_act_quant_apply(x, xq, rows, C, ss, 'Relu6', None, 8, False)
     hip.minmax_tensor(xq, slot[0])
-    rng = np.random.RandomState(C + stride)
-    d = rng.randint(0, 256, size=(3, 3, C, 1)).astype(np.uint8)
-    alpha, beta = rng.uniform(0.05, 0.6, 1).astype(np.float32), -rng.uniform(0.02, 0.3, 1).astype(np.float32)
-    meta = np.array([8, ex.MODE_TENSOR, 0, 3, 3, C, 1], np.int64)
-    p = int8.pack_depthwise(ex.pack_codes(d.reshape(-1), 8), alpha, beta, meta)
-    wdec = ex.decode_tensor(ex.pack_codes(d.reshape(-1), 8), alpha, beta, meta)
-    wcrs = torch.from_numpy(np.ascontiguousarray(wdec[..., 0].transpose(2, 0, 1))).cuda().bfloat16()
-    wcol = torch.from_numpy(p['wcol'].view(np.int32)).cuda()
-    wsb = torch.from_numpy(p['scale_beta']).cuda()
-    y = torch.empty((B, C, Ho, Ho), dtype=torch.bfloat16, device='cuda').contiguous(memory_format=torch.channels_last)
+    wcrs, wcol, wsb = depthwise_layer(C, stride)
+    y = nhwc((B, C, Ho, Ho), torch.bfloat16)
     partial = torch.empty((hip.depthwise_groups(B, Ho, Ho, C), 4, C), dtype=torch.float32, device='cuda')
     apply_f = lambda: hip.bn_act_quant_apply(x, xq, rows, C, ss, 'Relu6', slot[0], 8, True)
     dw_f = lambda: hip.depthwise_fwd(xq, wcrs, y, B, H, H, C, 3, stride, pad, pad, Ho, Ho, partial=partial)
@@ -142,12 +119,8 @@ def main():
     def route_i():
       codes_f()
       dw_i()
-    t = {key: [] for key in ('apply', 'dw', 'float', 'codes', 'i8', 'int8')}
-    for _ in range(ROUNDS):                       # alternate the two routes
-      for key, fn in (('apply', apply_f), ('dw', dw_f), ('float', route_f), ('codes', codes_f), ('i8', dw_i), ('int8', route_i)):
-        t[key].append(gpu_time_us(fn))
-    spread_f, spread_i = max(t['float']) - min(t['float']), max(t['int8']) - min(t['int8'])
-    t = {key: min(v) for key, v in t.items()}
+    t, spread = time_rounds((('apply', apply_f), ('dw', dw_f), ('float', route_f), ('codes', codes_f), ('i8', dw_i), ('int8', route_i)), ROUNDS)
+    spread_f, spread_i = spread['float'], spread['int8']
     bound_f = (rows * C * 6 + M * C * 2) / HBM_PEAK * 1e6
     bound_i = (rows * C * 4 + M * C * 2) / HBM_PEAK * 1e6
     pays = t['float'] - t['int8'] > max(spread_f, spread_i)
