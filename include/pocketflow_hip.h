@@ -239,6 +239,36 @@ int pf_bn_eval_scale_shift(const float* gamma, const float* beta, const float* m
                            const float* moving_var, float eps, int C, float* scale_shift,
                            void* stream);
 
+/* ---- the residual join of a ResNet-v1 block: BN (no activation of its own) + shortcut + ReLU (pf_bn_join.hip) ----------
+ * utils/external/resnet_model.py:250-252  inputs = batch_norm(inputs); inputs += shortcut; inputs = tf.nn.relu(inputs).
+ * x, r, u, dq, g: [rows][C] of `dtype` (PF_F32 / PF_BF16), C % 8 == 0, every pointer 16-byte aligned; scale_shift / mean_invstd the
+ * [2][C] float32 tables of pf_bn_finalize / pf_bn_eval_scale_shift; act = PF_ACT_NONE or PF_ACT_RELU.
+ * pf_bn_add_act_fwd: u = act(fmaf(scale[c], x, shift[c]) + r), one rounding on the store: float32 storage runs these float32
+ *   operations as written (bit for bit pf_bn_act_quant_apply without activation, a float32 add and a ReLU); bf16 storage evaluates
+ *   them in float64 and stores the exact value rounded once (two float32 roundings in front of the bf16 one would move several
+ *   times as many elements by a bf16 ulp as the single fmaf of pf_bn_act_quant_apply does).  slot != NULL: the min / max of
+ *   u AS STORED (after the rounding to `dtype`) are folded into the slot, in the encoding of pf_minmax_tensor (pf_minmax_decode /
+ *   pf_uq_apply read it unchanged).
+ * pf_bn_add_act_bwd_gate: g = dq * [fmaf(scale, x, shift) + r > 0] (act none: g = dq), the gate recomputed from x and r, and
+ *   partial[G][2][C] = {sum g, sum g * xhat} per row split, G = pf_bn_add_act_groups(rows, C), in the layout pf_bn_bwd_finalize
+ *   reads (fixed summation order: deterministic).  pf_bn_bwd_finalize and pf_bn_bwd_apply(act = none) on g then give the BN's dx /
+ *   dgamma / dbeta; g is the shortcut's gradient.
+ * pf_bn_add_act_bwd_gate_add: the same with dq + addend in the place of dq -- the gradients of the TWO consumers of a block's output
+ *   (the next block's first convolution and its shortcut), summed in float32 and rounded to `dtype` as autograd's accumulation would
+ *   store the sum.  addend may be NULL.
+ * pf_bn_add_act_groups: the number of row splits of both launches (0 for a shape they refuse).  A workgroup covers
+ *   256 / min(C / 8, 8) rows per trip and every split makes one trip until the cap min(256, 2048 / ceil(C / 64)) is reached; more rows
+ *   run in a grid-stride loop.
+ * Both launches return hipErrorInvalidValue WITHOUT launching for a null or misaligned pointer, C % 8 != 0, rows <= 0, an unknown
+ * dtype or an activation other than none / ReLU. */
+int pf_bn_add_act_groups(int64_t rows, int C);
+int pf_bn_add_act_fwd(const void* x, const void* r, void* u, int dtype, int64_t rows, int C, const float* scale_shift, int act,
+                      uint32_t* slot, void* stream);
+int pf_bn_add_act_bwd_gate(const void* dq, const void* x, const void* r, void* g, int dtype, int64_t rows, int C,
+                           const float* scale_shift, const float* mean_invstd, int act, float* partial, void* stream);
+int pf_bn_add_act_bwd_gate_add(const void* dq, const void* addend, const void* x, const void* r, void* g, int dtype, int64_t rows,
+                               int C, const float* scale_shift, const float* mean_invstd, int act, float* partial, void* stream);
+
 /* ---- K12 fused with K13/K4: 1x1 convolutions with BN/ReLU/fake-quant prologue and residual-add /
  * BN-statistics epilogue (bf16 NHWC, fp32 accumulate) -------------------------------------------
  * replaces, per bottleneck block, the chain  tf.layers.batch_normalization -> tf.nn.relu ->

@@ -51,6 +51,7 @@ FUSE_BN_BWD_STATS = os.environ.get('PF_FUSE_BN_BWD_STATS', '1') != '0'
 # backward passes rebuilt from the pooled gradient), the step's two losses + metrics in one launch (losses.py).  0: the separate chain.
 HEAD_FUSE = os.environ.get('PF_HEAD_FUSE', '1') != '0'
 HEAD_FUSE_ANY_DEVICE = False     # tests: run the head plumbing on CPU tensors (the HIP entry points are emulated there)
+BN_JOIN_ANY_DEVICE = False       # tests: likewise for the BN + shortcut + ReLU join of the v1 blocks (BatchNormAddAct)
 
 
 def _align(n: int) -> int:
@@ -397,6 +398,7 @@ class Graph:
     self._identity_ss: Dict[int, torch.Tensor] = {}
     self.conv_layers: List = []                # every Conv2D of the graph, in creation order (the loader finds a kernel's layer here)
     self.depthwise_layers: List = []           # every DepthwiseConv2D, likewise
+    self.join_layers: List = []                # every BatchNormAddAct (the int8 / static loaders refuse a graph that has one)
 
   # -- naming like tf.layers (conv2d, conv2d_1, ...) ---------------------------------------------
   def unique_name(self, base: str) -> str:
@@ -741,6 +743,104 @@ class _ActQuant(torch.autograd.Function):
     dx = torch.empty_like(u)
     hip.act_grad(g, u, dx, ctx.act)
     return dx, None, None, None
+
+
+class _BnAddActQuant(torch.autograd.Function):
+  """BN (batch statistics, or the moving ones with gradients) + shortcut -> act -> activation fake-quant: the tail of a ResNet-v1
+  block in ONE pass over the tensor (pf_bn_add_act_fwd, which also leaves the range of the stored sum in the slot) plus the
+  quantiser in place.  Backward is straight-through (as _ActQuant): pf_bn_add_act_bwd_gate recomputes the gate from x and the
+  shortcut, writes g = dq * gate -- the shortcut's gradient as it stands -- and leaves the BN-backward sums of g, so that
+  pf_bn_bwd_finalize / pf_bn_bwd_apply(act = none) on g finish the BN.
+  Returns TWO aliases of the output (as _BnLazy does of its input): a block output has two consumers, the next block's first
+  convolution and its shortcut (or projection).  Each reads its own alias, so their gradients arrive here separately and the gate
+  pass forms the sum autograd would form with a separate add kernel (pf_bn_add_act_bwd_gate_add)."""
+
+  @staticmethod
+  def forward(ctx, x, shortcut, gamma, beta, layer, graph, training, slot, bits, stats=None):
+    ctx.set_materialize_grads(False)               # an unused alias must arrive as None, not as a zeros tensor
+    x, r = _nhwc(x), _nhwc(shortcut)
+    C = gamma.numel()
+    rows = x.numel() // C
+    quantize = bits is not None
+    nbytes = float(x.numel() * x.element_size())
+    # the BN has no activation of its own and its output alone is never quantised: no slot for the finalize pass
+    scale_shift, mean_invstd = _bn_scale_shift(x, gamma, beta, layer.bn, graph, training, None, stats)
+    u = torch.empty_like(x)
+    if quantize:
+      hip.minmax_slots_init(slot)
+    with region('bn_add_act_fwd', 3 * nbytes):       # reads x and the shortcut, writes u
+      hip.bn_add_act_fwd(x, r, u, rows, C, scale_shift, layer.act, slot if quantize else None)
+    if quantize:
+      with region('uq_apply', 2 * nbytes):
+        hip.uq_apply(u, u, slot, bits, None)         # in place; the activation is already applied
+    ctx.save_for_backward(x, r, scale_shift, mean_invstd)
+    ctx.meta = (layer.act, graph, rows, C, not training)
+    ctx.params = (gamma, beta)
+    return u, u.view_as(u)
+
+  @staticmethod
+  def backward(ctx, dq, dskip):
+    x, r, scale_shift, mean_invstd = ctx.saved_tensors
+    act, graph, rows, C, frozen = ctx.meta
+    if dq is None:
+      dq, dskip = dskip, None
+    if dq is None:
+      return (None,) * 10
+
+    def as_x(t):
+      t = _nhwc(t)
+      return t if t.dtype == x.dtype else t.to(x.dtype)
+    dq = as_x(dq)
+    dskip = as_x(dskip) if dskip is not None else None
+    nblk = hip.bn_add_act_groups(rows, C)
+    partial = graph.scratch(nblk * 2 * C)
+    g = torch.empty_like(x)
+    # reads dq (and the second consumer's gradient), x and the shortcut, writes g
+    with region('bn_add_act_bwd_gate', (5.0 if dskip is not None else 4.0) * x.numel() * x.element_size()):
+      hip.bn_add_act_bwd_gate(dq, x, r, g, rows, C, scale_shift, mean_invstd, act, partial, addend=dskip)
+    dx, dgamma, dbeta = _bn_backward(g, x, scale_shift, mean_invstd, None, graph, rows, C, params=ctx.params,
+                                     pre=(partial, nblk), frozen=frozen)
+    return dx, g, dgamma, dbeta, None, None, None, None, None, None
+
+
+class _Fork(torch.autograd.Function):
+  """Two aliases of a tensor that has two consumers and no BatchNormAddAct behind it (the input of the first v1 bottleneck
+  block: projection + conv1).  Backward sums the two gradients on pf_bn_add_act_fwd with scale 1 / shift 0 and no activation
+  (fmaf(1, a, 0) + b = a + b, one rounding): the accumulation autograd would run as a separate aten kernel."""
+
+  @staticmethod
+  def forward(ctx, x, graph):
+    ctx.graph = graph
+    ctx.set_materialize_grads(False)
+    return x.view_as(x), x.view_as(x)
+
+  @staticmethod
+  def backward(ctx, a, b):
+    if a is None or b is None:
+      return (a if a is not None else b), None
+    a = _nhwc(a)
+    b = _nhwc(b)
+    if b.dtype != a.dtype:
+      b = b.to(a.dtype)
+    C = a.shape[1]
+    out = torch.empty_like(a)
+    with region('bn_add_act_fwd', 3.0 * a.numel() * a.element_size()):
+      hip.bn_add_act_fwd(a, b, out, a.numel() // C, C, ctx.graph.identity_scale_shift(C), None, None)
+    return out, None
+
+
+def bn_join_tensor_ok(x) -> bool:
+  """A tensor the join kernels (pf_bn_join.hip) take: 4-D, float32 / bf16, C % 8 == 0, on the GPU."""
+  return (isinstance(x, torch.Tensor) and (x.is_cuda or BN_JOIN_ANY_DEVICE) and x.dim() == 4 and x.shape[1] % 8 == 0
+          and x.dtype in (torch.float32, torch.bfloat16))
+
+
+def fork(x, graph):
+  """x, tagged with a second alias `x._pf_skip` for its second consumer, where the gradients of the two can be summed on the join
+  kernels (training on the GPU); x as it is otherwise."""
+  if bn_join_tensor_ok(x) and graph.taps is None and torch.is_grad_enabled() and x.requires_grad:
+    x, x._pf_skip = _Fork.apply(x, graph)
+  return x
 
 
 # =================================================================================================
@@ -2272,6 +2372,64 @@ class BatchNormAct:
     if g.frozen:
       self._frozen_ss = ss
     return ss
+
+
+class BatchNormAddAct:
+  """The tail of a ResNet-v1 block, `act(batch_norm(x) + shortcut)` (utils/external/resnet_model.py:250-252), as one layer: the
+  variables and moving averages are those of a BatchNormAct without activation (`self.bn`), the activation op is registered like a
+  free-standing Activation's (one more quantised activation for the learners), and on the GPU the three steps and the quantiser's
+  range run as one pass (_BnAddActQuant).  Anything the kernels do not take -- no GPU tensor, a dtype other than float32 / bf16,
+  C % 8 != 0 -- runs the composition of the v1 basic block: BatchNormAct, torch add, Activation.
+  Not covered by the int8 / fixed-range loaders: such a graph is refused with a ValueError that names this layer."""
+
+  def __init__(self, graph: Graph, name: str, channels: int, act: str, momentum: float, eps: float, act_name: str,
+               l2: bool = False):
+    if act not in ('Relu',):
+      raise ValueError('%s: the join kernels apply Relu (or nothing), not %s' % (name, act))
+    self.graph, self.name, self.act, self.C = graph, name, act, channels
+    self.bn = BatchNormAct(graph, name, channels, None, momentum, eps, l2=l2)
+    self.relu = Activation(graph, act_name, act)   # registers the op; also the activation of the composition
+    self.op = self.relu.op
+    graph.join_layers.append(self)
+
+  def refusal(self) -> str:
+    return ('%s/%s: the BN + shortcut + %s joins of the ResNet-v1 blocks are not covered by the int8 / static-range loaders'
+            % (self.graph.scope, self.name, self.act))
+
+  def takes(self, x, shortcut) -> bool:
+    return (bn_join_tensor_ok(x) and isinstance(shortcut, torch.Tensor) and shortcut.dtype == x.dtype
+            and shortcut.shape == x.shape and shortcut.device == x.device)
+
+  def __call__(self, x, shortcut) -> torch.Tensor:
+    g = self.graph
+    if g.act_static is not None or g.int8:
+      raise ValueError(self.refusal())
+    x, shortcut = materialize(x), materialize(shortcut)
+    if not self.takes(x, shortcut):
+      return self.relu(self.bn(x) + shortcut)
+    bits = self.op.bits
+    slot = g.act_slots[self.op.index] if bits is not None else None
+    gamma, beta = self.bn.gamma.tensor, self.bn.beta.tensor
+    if g.training and torch.is_grad_enabled():
+      u, skip = _BnAddActQuant.apply(x, shortcut, gamma, beta, self, g, True, slot, bits, getattr(x, '_pf_stats', None))
+      u._pf_skip = skip                            # for the second consumer of the block output (see _BnAddActQuant)
+      return u
+    if torch.is_grad_enabled() and not g.frozen and (x.requires_grad or shortcut.requires_grad or gamma.requires_grad):
+      if bits is not None:
+        raise NotImplementedError('inference-mode BN with gradients and activation quantisation (no learner needs it)')
+      u, skip = _BnAddActQuant.apply(x, shortcut, gamma, beta, self, g, False, None, None)
+      u._pf_skip = skip
+      return u
+    # inference mode without gradients: the moving statistics folded to scale / shift, the same pass
+    x, r = _nhwc(x), _nhwc(shortcut)
+    rows = x.numel() // self.C
+    u = torch.empty_like(x)
+    if bits is not None:
+      hip.minmax_slots_init(slot)
+    hip.bn_add_act_fwd(x, r, u, rows, self.C, self.bn._eval_scale_shift(x), self.act, slot)
+    if bits is not None:
+      hip.uq_apply(u, u, slot, bits, None)
+    return u
 
 
 class _MaxPool(torch.autograd.Function):

@@ -59,6 +59,7 @@ SYMBOLS = [
     'pf_bn_act_quant_codes', 'pf_conv_i8_supported', 'pf_conv_i8_fwd',
     'pf_dw_i8_supported', 'pf_dw_i8_fwd',
     'pf_bn_act_quant_static', 'pf_conv_i8_fwd_q', 'pf_dw_i8_fwd_q',
+    'pf_bn_add_act_groups', 'pf_bn_add_act_fwd', 'pf_bn_add_act_bwd_gate', 'pf_bn_add_act_bwd_gate_add',
 ]
 
 
@@ -489,6 +490,30 @@ def bn_bwd_apply(dq, x, dx, rows, C, scale_shift, mean_invstd, dgamma, dbeta, ac
 def bn_eval_scale_shift(gamma, beta, moving_mean, moving_var, eps: float, scale_shift) -> None:
   _check(_lib.pf_bn_eval_scale_shift(_ptr(gamma), _ptr(beta), _ptr(moving_mean), _ptr(moving_var), c_float(eps),
                                      c_int(gamma.numel()), _ptr(scale_shift), _stream()), 'pf_bn_eval_scale_shift')
+
+
+def bn_add_act_groups(rows: int, C: int) -> int:
+  """Row splits of bn_add_act_fwd / bn_add_act_bwd_gate = rows of the gate pass's partial sums [G][2][C] (0: shape refused)."""
+  return int(_lib.pf_bn_add_act_groups(c_int64(rows), c_int(C)))
+
+
+def bn_add_act_fwd(x, r, u, rows, C, scale_shift, act, slot=None) -> None:
+  """u = act(scale * x + shift + r) (a v1 block's BN + shortcut + ReLU); with `slot` also the min / max of the stored u."""
+  _check(_lib.pf_bn_add_act_fwd(_ptr(x), _ptr(r), _ptr(u), c_int(dtype_code(x)), c_int64(rows), c_int(C), _ptr(scale_shift),
+                                c_int(ACT_CODES[act]), _ptr(slot), _stream()), 'pf_bn_add_act_fwd')
+
+
+def bn_add_act_bwd_gate(dq, x, r, g, rows, C, scale_shift, mean_invstd, act, partial, addend=None) -> None:
+  """g = (dq [+ addend]) * [scale * x + shift + r > 0] and partial[bn_add_act_groups(rows, C)][2][C] = {sum g, sum g * xhat} for
+  bn_bwd_finalize.  `addend`: the gradient of the block output's second consumer."""
+  if addend is None:
+    _check(_lib.pf_bn_add_act_bwd_gate(_ptr(dq), _ptr(x), _ptr(r), _ptr(g), c_int(dtype_code(x)), c_int64(rows), c_int(C),
+                                       _ptr(scale_shift), _ptr(mean_invstd), c_int(ACT_CODES[act]), _ptr(partial), _stream()),
+           'pf_bn_add_act_bwd_gate')
+    return
+  _check(_lib.pf_bn_add_act_bwd_gate_add(_ptr(dq), _ptr(addend), _ptr(x), _ptr(r), _ptr(g), c_int(dtype_code(x)), c_int64(rows),
+                                         c_int(C), _ptr(scale_shift), _ptr(mean_invstd), c_int(ACT_CODES[act]), _ptr(partial),
+                                         _stream()), 'pf_bn_add_act_bwd_gate_add')
 
 
 # ------------------------------------------------------------------------------------------------

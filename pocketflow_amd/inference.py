@@ -149,6 +149,8 @@ def load_int8(model_helper, path: str, device='cuda', compute_dtype=torch.float3
   graph.fuse_conv1x1 = bool(FLAGS.fuse_conv1x1)
   with graph.as_default():
     model_helper.forward_eval(input_spec(model_helper))
+  for join in graph.join_layers:                 # the BN + shortcut + ReLU tails of ResNet-v1 blocks: no codes, no clamping pass
+    raise ValueError(join.refusal())
   layers = {conv.kernel.name: conv for conv in graph.conv_layers}
   dw_layers = {dw.kernel.name: dw for dw in graph.depthwise_layers}
   packed, packed_dw = {}, {}

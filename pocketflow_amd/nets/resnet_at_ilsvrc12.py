@@ -14,6 +14,7 @@ from pocketflow_amd.utils.lrn_rate_utils import setup_lrn_rate_piecewise_constan
 from pocketflow_amd.utils.multi_gpu_wrapper import MultiGpuWrapper as mgw
 
 flags.DEFINE_integer('resnet_size', 18, '# of layers in the ResNet model')
+flags.DEFINE_integer('resnet_version', 2, 'ResNet version: 2 (pre-activation, the default) | 1 (conv-BN-ReLU blocks)')
 flags.DEFINE_float('nb_epochs_rat', 1.0, '# of training epochs\'s ratio')
 flags.DEFINE_float('lrn_rate_init', 1e-1, 'initial learning rate')
 flags.DEFINE_float('batch_size_norm', 256, 'normalization factor of batch size')
@@ -38,7 +39,7 @@ def forward_fn(inputs, is_train, data_format):
     bottleneck = FLAGS.resnet_size >= 50
     net = graph.nets['resnet'] = ResNet.Model(
         FLAGS.resnet_size, bottleneck, FLAGS.nb_classes, 64, 7, 2, 3, 2, get_block_sizes(FLAGS.resnet_size),
-        [1, 2, 2, 2], data_format=data_format, graph=graph)
+        [1, 2, 2, 2], resnet_version=FLAGS.resnet_version, data_format=data_format, graph=graph)
   if inputs.device.type == 'meta':
     return torch.empty((inputs.shape[0], FLAGS.nb_classes), device='meta')
   return net(inputs, is_train)
@@ -83,6 +84,8 @@ class ModelHelper(AbstractModelHelper):
 
   @property
   def model_name(self):
+    if FLAGS.resnet_version == 1:
+      return 'resnet_v1_%d' % FLAGS.resnet_size
     return 'resnet_%d' % FLAGS.resnet_size
 
   @property
