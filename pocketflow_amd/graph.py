@@ -30,7 +30,6 @@ from __future__ import annotations
 import contextlib
 import math
 import os
-import weakref
 import threading
 from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
@@ -52,6 +51,8 @@ FUSE_BN_BWD_STATS = os.environ.get('PF_FUSE_BN_BWD_STATS', '1') != '0'
 HEAD_FUSE = os.environ.get('PF_HEAD_FUSE', '1') != '0'
 HEAD_FUSE_ANY_DEVICE = False     # tests: run the head plumbing on CPU tensors (the HIP entry points are emulated there)
 BN_JOIN_ANY_DEVICE = False       # tests: likewise for the BN + shortcut + ReLU join of the v1 blocks (BatchNormAddAct)
+# how a BatchNorm layer runs (BatchNormAct._mode): batch statistics; moving statistics with gradients; moving statistics without
+BN_TRAIN, BN_EVAL_GRAD, BN_EVAL = 0, 1, 2
 
 
 def _align(n: int) -> int:
@@ -618,99 +619,92 @@ def _bn_blocks(rows: int, C: int) -> int:
   return int(min(256, max(1, rows // 64)))
 
 
+class BnSums(object):
+  """What a training-mode BatchNormAct shares with the convolutions that read its output, so that its ONE consumer's backward-data
+  kernel can reduce the BN-backward sums in its epilogue.  BatchNormAct.__call__ makes it, the node's forward fills it and keeps it in
+  its ctx, and the output carries it as `_pf_bn` (a materialised tensor and a LazyAct alike): the consumers count themselves in
+  `n_consumers` (a consumer that cannot leave the sums counts twice) and the single one leaves `bwd_stats`.
+  It holds the BN's INPUT, never the node's output or the LazyAct: that reference would close a cycle ctx -> record -> output ->
+  grad_fn -> ctx which only Python's cyclic collector frees -- one step's activations (~10 GB at B = 256) alive for a random number
+  of further steps, the caching allocator at the memory ceiling (measured: 26 GB reserved after 5 steps, 52 GB after 13; DESIGN.md
+  section 6)."""
+  __slots__ = ('x', 'scale_shift', 'mean_invstd', 'act', 'n_consumers', 'bwd_stats')
+
+  def __init__(self):
+    self.n_consumers = 0
+    self.bwd_stats = None                        # (partial, n_blocks, data_ptr of the dq they are the sums of)
+
+  def sums_for(self, dq):
+    """(partial, n_blocks) where the single consumer's backward-data kernel already reduced THIS dq, else None."""
+    bs = self.bwd_stats
+    return bs[:2] if bs is not None and bs[2] == dq.data_ptr() else None
+
+
+def _bn_enter(ctx, x, gamma, beta, layer, graph, training, slot, stats, rec=None, *more):
+  """The forward prologue the BN nodes share: x in NHWC memory, the layer's scale / shift (_bn_scale_shift), and everything
+  _bn_leave needs saved on ctx (`more`: further tensors to save behind the three).  Returns (x, rows, C, scale_shift)."""
+  x = _nhwc(x)
+  C = gamma.numel()
+  rows = x.numel() // C
+  scale_shift, mean_invstd = _bn_scale_shift(x, gamma, beta, layer, graph, training, slot, stats)
+  ctx.save_for_backward(x, scale_shift, mean_invstd, *more)
+  ctx.bn = (layer.act, graph, rows, C, (gamma, beta), not training, rec)
+  if rec is not None:
+    rec.x, rec.scale_shift, rec.mean_invstd, rec.act = x, scale_shift, mean_invstd, layer.act
+  return x, rows, C, scale_shift
+
+
+def _bn_leave(ctx, dq, pre=None, **kw):
+  """(dx, dgamma, dbeta) of a node entered with _bn_enter for the gradient `dq` of the activated output: _bn_backward on the saved
+  state, with the sums the single consumer left for this dq where it did (BnSums)."""
+  x, scale_shift, mean_invstd = ctx.saved_tensors[:3]
+  act, graph, rows, C, params, frozen, rec = ctx.bn
+  if rec is not None:
+    pre = rec.sums_for(dq)
+  return _bn_backward(dq, x, scale_shift, mean_invstd, act, graph, rows, C, params=params, pre=pre, frozen=frozen, **kw)
+
+
 class _BnActQuant(torch.autograd.Function):
-  """BN (batch stats) -> act -> activation fake-quant, fused (pf_bn_* kernels)."""
+  """BN -> act -> activation fake-quant, fused (pf_bn_* kernels).  `training`: batch statistics.  Otherwise inference mode WITH
+  gradients: the networks the pruning-ratio search re-trains are built with forward_eval (reference pr_optimizer.py:176-196 "DO NOT
+  USE forward_train() HERE"), i.e. BN normalises with its moving statistics while gamma / beta (and everything upstream) are still
+  trained.  y = act(scale * x + shift), scale = gamma * rsqrt(var + eps), shift = beta - mean * scale;
+  dgamma = sum dy * (x - mean) * rsqrt(var + eps), dbeta = sum dy, dx = scale * dy  (same kernels as the training-mode backward:
+  the statistics pass with the moving mean / invstd, the apply pass with zero sums)."""
 
   @staticmethod
-  def forward(ctx, x, gamma, beta, layer, graph, training, slot, bits, stats=None, box=None):
-    x = _nhwc(x)
-    C = gamma.numel()
-    rows = x.numel() // C
+  def forward(ctx, x, gamma, beta, layer, graph, training, slot, bits, stats=None, rec=None):
+    x, rows, C, scale_shift = _bn_enter(ctx, x, gamma, beta, layer, graph, training, slot, stats, rec)
     quantize = bits is not None
-    nbytes = float(x.numel() * x.element_size())
-    scale_shift, mean_invstd = _bn_scale_shift(x, gamma, beta, layer, graph, training, slot if quantize else None, stats)
     q = torch.empty_like(x)
-    with region('bn_act_quant_apply', 2 * nbytes):   # 1 read of x + 1 write of q
+    with region('bn_act_quant_apply', 2.0 * x.numel() * x.element_size()):   # 1 read of x + 1 write of q
       hip.bn_act_quant_apply(x, q, rows, C, scale_shift, layer.act, slot, bits if quantize else 8, quantize)
-    ctx.save_for_backward(x, scale_shift, mean_invstd)
-    ctx.meta = (layer.act, graph, rows, C)
-    ctx.params = (gamma, beta)
-    ctx.box = box
-    if box is not None:                          # lets a single consuming convolution fuse the BN-backward sums
-      box.update(x=x, scale_shift=scale_shift, mean_invstd=mean_invstd, act=layer.act, n_consumers=0, bwd_stats=None)
     return q
 
   @staticmethod
   def backward(ctx, dq):
-    x, scale_shift, mean_invstd = ctx.saved_tensors
-    act, graph, rows, C = ctx.meta
-    pre = None
-    bs = ctx.box.get('bwd_stats') if ctx.box is not None else None
-    if bs is not None and bs[2] == dq.data_ptr():
-      pre = bs[:2]                               # the consumer's backward-data kernel already reduced dy
-    dx, dgamma, dbeta = _bn_backward(dq, x, scale_shift, mean_invstd, act, graph, rows, C, params=ctx.params, pre=pre)
-    return dx, dgamma, dbeta, None, None, None, None, None, None, None
-
-
-class _BnEvalAct(torch.autograd.Function):
-  """Inference-mode BN -> act WITH gradients: the networks the pruning-ratio search re-trains are built with
-  forward_eval (reference pr_optimizer.py:176-196 "DO NOT USE forward_train() HERE"), i.e. BN normalises with
-  its moving statistics while gamma / beta (and everything upstream) are still trained.
-  y = act(scale * x + shift), scale = gamma * rsqrt(var + eps), shift = beta - mean * scale;
-  dgamma = sum dy * (x - mean) * rsqrt(var + eps), dbeta = sum dy, dx = scale * dy  (same kernels as the
-  training-mode backward: the statistics pass with the moving mean / invstd, the apply pass with zero sums)."""
-
-  @staticmethod
-  def forward(ctx, x, gamma, beta, layer, graph):
-    x = _nhwc(x)
-    C = gamma.numel()
-    rows = x.numel() // C
-    ss, mi = _bn_scale_shift(x, gamma, beta, layer, graph, False, None)
-    q = torch.empty_like(x)
-    hip.bn_act_quant_apply(x, q, rows, C, ss, layer.act, None, 8, False)
-    ctx.save_for_backward(x, ss, mi)
-    ctx.meta = (layer.act, graph, rows, C)
-    ctx.params = (gamma, beta)
-    return q
-
-  @staticmethod
-  def backward(ctx, dq):
-    x, ss, mi = ctx.saved_tensors
-    act, graph, rows, C = ctx.meta
-    dx, dgamma, dbeta = _bn_backward(dq, x, ss, mi, act, graph, rows, C, params=ctx.params, frozen=True)
-    return dx, dgamma, dbeta, None, None
+    return _bn_leave(ctx, dq) + (None,) * 7
 
 
 class _BnActPool(torch.autograd.Function):
   """The network head: BN -> act -> activation fake-quant -> mean over H, W, without the activated map in between
-  (pf_bn_act_quant_pool; x.float().mean(dim=(2, 3)).to(x.dtype) of the q _BnActQuant / _BnEvalAct would have written).
-  `training`: batch statistics (from the producing convolution's epilogue when it left them), else inference mode WITH
-  gradients (_BnEvalAct's case: moving statistics, backward with zero sums).  Returns [B][C]; backward takes its gradient
-  and runs the pooled forms of the two BN-backward passes, dgamma / dbeta straight into the flat gradient views."""
+  (pf_bn_act_quant_pool; x.float().mean(dim=(2, 3)).to(x.dtype) of the q _BnActQuant would have written), in both of its modes.
+  Returns [B][C]; backward takes its gradient and runs the pooled forms of the two BN-backward passes, dgamma / dbeta straight
+  into the flat gradient views."""
 
   @staticmethod
   def forward(ctx, x, gamma, beta, layer, graph, training, slot, bits, stats=None):
-    x = _nhwc(x)
-    C = gamma.numel()
-    rows = x.numel() // C
-    hw = rows // x.shape[0]
+    x, rows, C, scale_shift = _bn_enter(ctx, x, gamma, beta, layer, graph, training, slot, stats)
+    ctx.hw = hw = rows // x.shape[0]
     quantize = bits is not None
-    scale_shift, mean_invstd = _bn_scale_shift(x, gamma, beta, layer, graph, training, slot if quantize else None, stats)
     pooled = torch.empty((x.shape[0], C), dtype=x.dtype, device=x.device)
     with region('bn_act_quant_pool', float(x.numel() * x.element_size())):   # 1 read of x
       hip.bn_act_quant_pool(x, pooled, rows, C, hw, scale_shift, layer.act, slot, bits if quantize else 8, quantize)
-    ctx.save_for_backward(x, scale_shift, mean_invstd)
-    ctx.meta = (layer.act, graph, rows, C, hw, not training)
-    ctx.params = (gamma, beta)
     return pooled
 
   @staticmethod
   def backward(ctx, g):
-    x, scale_shift, mean_invstd = ctx.saved_tensors
-    act, graph, rows, C, hw, frozen = ctx.meta
-    dx, dgamma, dbeta = _bn_backward(g.contiguous(), x, scale_shift, mean_invstd, act, graph, rows, C, params=ctx.params,
-                                     frozen=frozen, pool_hw=hw)
-    return dx, dgamma, dbeta, None, None, None, None, None, None
+    return _bn_leave(ctx, g.contiguous(), pool_hw=ctx.hw) + (None,) * 6
 
 
 def head_fuse_ok(graph, x) -> bool:
@@ -758,13 +752,12 @@ class _BnAddActQuant(torch.autograd.Function):
   @staticmethod
   def forward(ctx, x, shortcut, gamma, beta, layer, graph, training, slot, bits, stats=None):
     ctx.set_materialize_grads(False)               # an unused alias must arrive as None, not as a zeros tensor
-    x, r = _nhwc(x), _nhwc(shortcut)
-    C = gamma.numel()
-    rows = x.numel() // C
+    r = _nhwc(shortcut)
+    # the BN (layer.bn) has no activation of its own and its output alone is never quantised: no slot for the finalize pass
+    x, rows, C, scale_shift = _bn_enter(ctx, x, gamma, beta, layer.bn, graph, training, None, stats, None, r)
+    ctx.act = layer.act
     quantize = bits is not None
     nbytes = float(x.numel() * x.element_size())
-    # the BN has no activation of its own and its output alone is never quantised: no slot for the finalize pass
-    scale_shift, mean_invstd = _bn_scale_shift(x, gamma, beta, layer.bn, graph, training, None, stats)
     u = torch.empty_like(x)
     if quantize:
       hip.minmax_slots_init(slot)
@@ -773,15 +766,12 @@ class _BnAddActQuant(torch.autograd.Function):
     if quantize:
       with region('uq_apply', 2 * nbytes):
         hip.uq_apply(u, u, slot, bits, None)         # in place; the activation is already applied
-    ctx.save_for_backward(x, r, scale_shift, mean_invstd)
-    ctx.meta = (layer.act, graph, rows, C, not training)
-    ctx.params = (gamma, beta)
     return u, u.view_as(u)
 
   @staticmethod
   def backward(ctx, dq, dskip):
-    x, r, scale_shift, mean_invstd = ctx.saved_tensors
-    act, graph, rows, C, frozen = ctx.meta
+    x, scale_shift, mean_invstd, r = ctx.saved_tensors
+    graph, rows, C = ctx.bn[1:4]
     if dq is None:
       dq, dskip = dskip, None
     if dq is None:
@@ -797,9 +787,8 @@ class _BnAddActQuant(torch.autograd.Function):
     g = torch.empty_like(x)
     # reads dq (and the second consumer's gradient), x and the shortcut, writes g
     with region('bn_add_act_bwd_gate', (5.0 if dskip is not None else 4.0) * x.numel() * x.element_size()):
-      hip.bn_add_act_bwd_gate(dq, x, r, g, rows, C, scale_shift, mean_invstd, act, partial, addend=dskip)
-    dx, dgamma, dbeta = _bn_backward(g, x, scale_shift, mean_invstd, None, graph, rows, C, params=ctx.params,
-                                     pre=(partial, nblk), frozen=frozen)
+      hip.bn_add_act_bwd_gate(dq, x, r, g, rows, C, scale_shift, mean_invstd, ctx.act, partial, addend=dskip)
+    dx, dgamma, dbeta = _bn_leave(ctx, g, pre=(partial, nblk))     # the BN behind the gate: no activation (layer.bn.act)
     return dx, g, dgamma, dbeta, None, None, None, None, None, None
 
 
@@ -856,13 +845,11 @@ class LazyAct(object):
   Gradients with respect to q flow into `x`'s autograd node (_BnLazy), which runs the BN backward once.
   """
 
-  def __init__(self, x, scale_shift, act, slot, bits, rows, C, mean_invstd=None):
+  def __init__(self, x, scale_shift, act, slot, bits, rows, C, bn=None):
     self.x, self.scale_shift, self.act, self.slot, self.bits = x, scale_shift, act, slot, bits
     self.rows, self.C = rows, C
-    self.mean_invstd = mean_invstd            # training mode only: lets a consumer fuse the BN-backward statistics
-    self.n_consumers = 0                      # fused convolutions that read this activation
-    self.bwd_stats = None                     # (partial, n_blocks, data_ptr of dq) left by the single consumer
-    self.n_grad_consumers = 0                 # ... of which take part in the backward pass
+    self._pf_bn = bn                          # training mode only (BnSums): lets a consumer fuse the BN-backward statistics
+    self.n_grad_consumers = 0                 # fused convolutions that read this activation and take part in the backward pass
     self.pending = None                       # dq of the first of TWO consumers, waiting to be joined by the second
     self.join_ok = False                      # set by the caller that KNOWS both consumers reach the loss (see _FusedConv1x1)
     self.pending_geom = None                  # geometry of a COMPACT parked gradient (a strided first consumer), else None
@@ -882,7 +869,8 @@ class LazyAct(object):
     return self.x.device
 
   def materialize(self) -> torch.Tensor:
-    self.n_consumers += 2                     # a materialised consumer: its gradient is summed by autograd
+    if self._pf_bn is not None:
+      self._pf_bn.n_consumers += 2            # a materialised consumer: its gradient is summed by autograd
     if self._q is None:
       self._q = _Materialize.apply(self.x, self)
     return self._q
@@ -1003,23 +991,9 @@ class _BnLazy(torch.autograd.Function):
   """BN statistics + finalize only; returns an alias of x that stands for q (see LazyAct)."""
 
   @staticmethod
-  def forward(ctx, x, gamma, beta, layer, graph, slot, bits, box, stats):
-    C = gamma.numel()
-    rows = x.numel() // C
-    scale_shift, mean_invstd = _bn_scale_shift(x, gamma, beta, layer, graph, True, slot if bits is not None else None, stats)
-    ctx.save_for_backward(x, scale_shift, mean_invstd)
-    ctx.meta = (layer.act, graph, rows, C)
-    ctx.params = (gamma, beta)
-    # [scale_shift, mean_invstd, weakref to the LazyAct (appended by the caller)].  WEAK: the LazyAct holds this node's
-    # output alias, so a strong reference would close a cycle ctx -> LazyAct -> alias -> grad_fn -> ctx that only Python's
-    # cyclic collector can free -- one step's 4C-channel activations (~10 GB at B = 256) would then live until the
-    # collector happens to run, the caching allocator would keep growing (measured: 26 GB reserved after 5 steps, 52 GB
-    # after 13) and, at the memory ceiling, fall into malloc-retry mode (torch.empty at 185 us: the host-bound bench
-    # processes of DESIGN.md section 6).  The consumers' autograd nodes hold the LazyAct strongly until backward is over.
-    ctx.box = box
+  def forward(ctx, x, gamma, beta, layer, graph, slot, rec, stats):
     ctx.set_materialize_grads(False)          # an unused shortcut alias must arrive as None, not as a zeros tensor
-    box.append(scale_shift)
-    box.append(mean_invstd)
+    x = _bn_enter(ctx, x, gamma, beta, layer, graph, True, slot, stats, rec)[0]
     # two aliases of x: the first stands for q (consumed by the fused convolutions), the second is x
     # itself for the block's identity shortcut -- routing the shortcut through this node lets the
     # backward add its gradient inside pf_bn_bwd_apply_add instead of a separate accumulation kernel
@@ -1027,17 +1001,9 @@ class _BnLazy(torch.autograd.Function):
 
   @staticmethod
   def backward(ctx, dq, dskip):
-    x, scale_shift, mean_invstd = ctx.saved_tensors
-    act, graph, rows, C = ctx.meta
     if dq is None:
-      return dskip, None, None, None, None, None, None, None, None
-    pre = None
-    lazy = ctx.box[2]() if len(ctx.box) > 2 else None      # None if every consumer is gone: only the fusion below is lost
-    if lazy is not None and lazy.bwd_stats is not None and lazy.bwd_stats[2] == dq.data_ptr():
-      pre = lazy.bwd_stats[:2]                # the single consumer's backward-data kernel already reduced dy
-    dx, dgamma, dbeta = _bn_backward(dq, x, scale_shift, mean_invstd, act, graph, rows, C, addend=dskip,
-                                     params=ctx.params, pre=pre)
-    return dx, dgamma, dbeta, None, None, None, None, None, None
+      return (dskip,) + (None,) * 7
+    return _bn_leave(ctx, dq, addend=dskip) + (None,) * 5
 
 
 def _grad_view(t: Optional[torch.Tensor], n: int):
@@ -1207,6 +1173,7 @@ class _FusedConv1x1(torch.autograd.Function):
     ss = lazy.scale_shift if lazy is not None else None
     quant = lazy is not None and lazy.bits is not None
     act = lazy.act if lazy is not None else None
+    bn = lazy._pf_bn if lazy is not None else None                             # the producer BN's record (BnSums), training mode
     dx = dw = None
     if ctx.needs_input_grad[1]:
       S = hip.conv1x1_wrw_splits(M, N, K)
@@ -1219,8 +1186,7 @@ class _FusedConv1x1(torch.autograd.Function):
       dw = _filter_grad(graph, ctx.w_leaf, ctx.w_var, (dy, x, w2d, ss, lazy), 'conv1x1_wrw', float((M * K + M * N) * 2), wrw)
     if ctx.needs_input_grad[0]:
       wt = _bwd_data_weight(graph, ctx.w_var, ctx.w_leaf).view(K, N)           # [K][N]
-      fuse_stats = (FUSE_BN_BWD_STATS and lazy is not None and lazy.n_consumers == 1 and geom is None
-                    and lazy.mean_invstd is not None and lazy.act in ('Relu', 'Relu6'))
+      fuse_stats = FUSE_BN_BWD_STATS and bn is not None and bn.n_consumers == 1 and geom is None and act in ('Relu', 'Relu6')
       # An activation with exactly TWO fused consumers (bn1 of a projection block: shortcut convolution + conv1): the
       # consumer whose backward runs first parks its dq on the LazyAct and reports no gradient; the second takes it as the
       # residual operand of its backward-data kernel -- the sum autograd would form with a separate add kernel (two reads
@@ -1228,21 +1194,20 @@ class _FusedConv1x1(torch.autograd.Function):
       # convolution, so the (possibly strided, zero-filled) shortcut gradient comes first and the dense one joins it.
       # Opt-in (`lazy.join_ok`, set by the bottleneck block): a parked gradient is only delivered by the second consumer's
       # backward, so both consumers must be known to reach the loss.
-      join = (JOIN_TWO_CONSUMERS and lazy is not None and lazy.join_ok and lazy.n_consumers == 2
+      join = (JOIN_TWO_CONSUMERS and bn is not None and lazy.join_ok and bn.n_consumers == 2
               and lazy.n_grad_consumers == 2)
       second = join and lazy.pending is not None
       res = lazy.pending if (second and geom is None) else None
       # The projection join (pf_conv1x1_bwd_data_join), where the loaded library offers it and its plan takes the dense consumer's
       # shape: a strided first consumer parks a COMPACT [B][K][Ho][Wo] gradient -- a plain dense GEMM, no zero fill, no row scatter --
       # which the second reads through the inverse row map; and the second takes the BN-backward sums of the joined gradient in
-      # the same launch, so that _BnLazy.backward finds them (lazy.bwd_stats) and skips its statistics pass.
+      # the same launch, so that _BnLazy.backward finds them (BnSums.bwd_stats) and skips its statistics pass.
       join_entry = getattr(hip, 'conv1x1_bwd_data_join', None) if PROJ_JOIN else None
       compact = (join and not second and geom is not None and join_entry is not None and lazy.dense_out is not None
                  and hip.conv1x1_join_plan(x.shape[0] * x.shape[2] * x.shape[3], lazy.dense_out, K) != 0)
       rgeom = lazy.pending_geom if res is not None else None
       join_stats = (res is not None and join_entry is not None and PROJ_JOIN_STATS and FUSE_BN_BWD_STATS
-                    and lazy.mean_invstd is not None and lazy.act in ('Relu', 'Relu6')
-                    and hip.conv1x1_join_plan(M, N, K, True) != 0)
+                    and act in ('Relu', 'Relu6') and hip.conv1x1_join_plan(M, N, K, True) != 0)
       if compact:
         dx = torch.empty((x.shape[0], K, geom[0], geom[1]), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
       elif geom is None:
@@ -1255,16 +1220,16 @@ class _FusedConv1x1(torch.autograd.Function):
         elif join_stats:
           G = hip.conv1x1_stats_groups(M, K, N)
           partial = torch.empty((G, 2, K), dtype=torch.float32, device=x.device)
-          join_entry(dy, wt, dx, res, M, N, K, rgeom=rgeom, bn_x=x, bn_scale_shift=lazy.scale_shift,
-                     bn_mean_invstd=lazy.mean_invstd, bn_act=lazy.act, partial=partial)
-          lazy.bwd_stats = (partial, G, dx.data_ptr())
+          join_entry(dy, wt, dx, res, M, N, K, rgeom=rgeom, bn_x=x, bn_scale_shift=bn.scale_shift,
+                     bn_mean_invstd=bn.mean_invstd, bn_act=act, partial=partial)
+          bn.bwd_stats = (partial, G, dx.data_ptr())
         elif rgeom is not None:
           join_entry(dy, wt, dx, res, M, N, K, rgeom=rgeom)
         elif fuse_stats:
           G = hip.conv1x1_stats_groups(M, K, N)
           partial = torch.empty((G, 2, K), dtype=torch.float32, device=x.device)
-          hip.conv1x1_bwd_data_bnstats(dy, wt, dx, x, lazy.scale_shift, lazy.mean_invstd, lazy.act, partial, M, N, K)
-          lazy.bwd_stats = (partial, G, dx.data_ptr())
+          hip.conv1x1_bwd_data_bnstats(dy, wt, dx, x, bn.scale_shift, bn.mean_invstd, act, partial, M, N, K)
+          bn.bwd_stats = (partial, G, dx.data_ptr())
         elif res is not None:
           hip.conv1x1_fwd(dy, wt, dx, M, K, N, R=res)
         else:
@@ -1335,19 +1300,19 @@ class _Conv2dIgemm(torch.autograd.Function):
   switches' other side and geometries outside the kernels' limits (channel counts, 31-bit offsets)."""
 
   @staticmethod
-  def forward(ctx, x, w, stride, pad, want_stats, graph, bn_box, w_var, box):
+  def forward(ctx, x, w, stride, pad, want_stats, graph, bn_sums, w_var, box):
     ctx.w_var = w_var
     w_krsc = w.detach().permute(0, 2, 3, 1)              # physical layout of the kernel: contiguous [N][R][S][C]
     y = _run_conv2d(x, w_krsc, stride, pad, want_stats)
     ctx.save_for_backward(x, w)
-    ctx.meta = (stride, pad, graph, bn_box)
+    ctx.meta = (stride, pad, graph, bn_sums)
     box.append(getattr(y, '_pf_stats', None))
     return y
 
   @staticmethod
   def backward(ctx, dy):
     x, w = ctx.saved_tensors
-    stride, pad, graph, bn_box = ctx.meta
+    stride, pad, graph, bn_sums = ctx.meta
     dy = _nhwc(dy)
     dx = dw = None
     N, C, R, S = w.shape
@@ -1385,22 +1350,22 @@ class _Conv2dIgemm(torch.autograd.Function):
         dx = torch.empty_like(x)
         # the BN-backward sums of x's producer BN from this launch's epilogue (stride 1: bn2 of a block; by classes: bn2 in front of a
         # stage's strided 3x3, round 6)
-        fuse = (FUSE_BN_BWD_STATS and bn_box is not None and bn_box.get('n_consumers') == 1
-                and bn_box.get('act') in ('Relu', 'Relu6') and bn_box['x'].shape == x.shape)
+        fuse = (FUSE_BN_BWD_STATS and bn_sums is not None and bn_sums.n_consumers == 1
+                and bn_sums.act in ('Relu', 'Relu6') and bn_sums.x.shape == x.shape)
         with region('conv2d_bwd_data', float((dy.numel() + x.numel() * (2 if fuse else 1)) * 2)):
           bn = {}
           if fuse:
             G = (hip.conv2d_stats_groups(B * H * W, C, geom=(B, H, W, N, C, R, S, 1, R - 1 - pad[0], S - 1 - pad[1], H, W))
                  if stride == 1 else hip.conv2d_bwd_data_strided_stats_groups(B, H, W, C, stride))
             partial = torch.empty((G, 2, C), dtype=torch.float32, device=x.device)
-            bn = dict(partial=partial, bn_x=bn_box['x'], bn_scale_shift=bn_box['scale_shift'], bn_mean_invstd=bn_box['mean_invstd'],
-                      bn_act=bn_box['act'])
+            bn = dict(partial=partial, bn_x=bn_sums.x, bn_scale_shift=bn_sums.scale_shift, bn_mean_invstd=bn_sums.mean_invstd,
+                      bn_act=bn_sums.act)
           if stride == 1:
             hip.conv2d_fwd(dy, wb, dx, B, H, W, N, C, R, S, 1, R - 1 - pad[0], S - 1 - pad[1], H, W, **bn)
           else:
             hip.conv2d_bwd_data_strided(dy, wb, dx, B, H, W, C, N, R, S, stride, pad[0], pad[1], Ho, Wo, **bn)
           if fuse:
-            bn_box['bwd_stats'] = (partial, G, dx.data_ptr())
+            bn_sums.bwd_stats = (partial, G, dx.data_ptr())
       elif OWN_CONV2D and OWN_CONV_GENERIC and x.is_cuda and dy.dtype == x.dtype and w.dtype == x.dtype:
         # geometries outside the MFMA kernels' limits (odd strided sizes, channel counts, 31-bit offsets): the general kernel
         dx = torch.empty_like(x)
@@ -1843,10 +1808,9 @@ class Conv2D:
       x = x.materialize()                        # every other consumer: the fake-quantised tensor of the apply pass, as without int8
     if fused_conv1x1_ok(x, self):                # 1x1 on pf_conv.hip: the producer BN's normalise / act / fake-quant in the prologue
       lazy = x if isinstance(x, LazyAct) else None
-      if lazy is not None:
-        lazy.n_consumers += 1
-      elif getattr(x, '_pf_bn', None) is not None:
-        x._pf_bn['n_consumers'] += 2             # a materialised BN output read by a 1x1: its BN-backward sums are not fused
+      bn_sums = getattr(x, '_pf_bn', None)
+      if bn_sums is not None:                     # (a MATERIALISED BN output read by a 1x1: its BN-backward sums are not fused)
+        bn_sums.n_consumers += 1 if lazy is not None else 2
       xin = lazy.x if lazy is not None else _nhwc(x)
       if torch.is_grad_enabled() and (xin.requires_grad or w.requires_grad):
         if lazy is not None and xin.requires_grad:
@@ -1871,18 +1835,18 @@ class Conv2D:
         return _StemConv.apply(x, w, self.graph, self.kernel)
       return _run_stem(x, w)
     if own_conv2d_ok(x, self, pad):              # RxS on the implicit-GEMM kernel
-      bn_box = getattr(x, '_pf_bn', None)
-      if bn_box is not None:
-        bn_box['n_consumers'] += 1
+      bn_sums = getattr(x, '_pf_bn', None)
+      if bn_sums is not None:
+        bn_sums.n_consumers += 1
       xin = _nhwc(x)
       if torch.is_grad_enabled() and (xin.requires_grad or w.requires_grad):
-        y = _apply_with_stats(_Conv2dIgemm, xin, w, self.stride, pad, want_stats, self.graph, bn_box, self.kernel)
+        y = _apply_with_stats(_Conv2dIgemm, xin, w, self.stride, pad, want_stats, self.graph, bn_sums, self.kernel)
       else:
         y = _run_conv2d(xin, w.detach().permute(0, 2, 3, 1), self.stride, pad, want_stats, out_bn=out_bn)
       return y if residual is None else y + residual
-    bn_box = getattr(x, '_pf_bn', None)
-    if bn_box is not None:
-      bn_box['n_consumers'] += 2                 # a consumer that cannot fuse the BN-backward sums
+    bn_sums = getattr(x, '_pf_bn', None)
+    if bn_sums is not None:
+      bn_sums.n_consumers += 2                    # a consumer that cannot fuse the BN-backward sums
     if im2col_conv_ok(x, self, pad):             # few-channel RxS as im2col + the 1x1 kernels
       y = _ConvIm2col.apply(_nhwc(x), w, self.stride, pad, out_hw, self.graph, self.kernel)
     elif convg_ok(x, w):                         # everything else on the general kernel
@@ -2113,9 +2077,9 @@ class DepthwiseConv2D:
     if (OWN_DEPTHWISE and (x.is_cuda or DEPTHWISE_ANY_DEVICE) and x.dim() == 4 and x.dtype in (torch.float32, torch.bfloat16) and w.dtype == x.dtype
         and hip.depthwise_supported(self.channels, self.k, self.stride)):
       Ho, Wo = -(-x.shape[2] // self.stride), -(-x.shape[3] // self.stride)
-      bn_box = getattr(x, '_pf_bn', None)
-      if bn_box is not None:
-        bn_box['n_consumers'] += 2                 # a consumer that does not fuse the BN-backward sums of its producer
+      bn_sums = getattr(x, '_pf_bn', None)
+      if bn_sums is not None:
+        bn_sums.n_consumers += 2                    # a consumer that does not fuse the BN-backward sums of its producer
       if torch.is_grad_enabled() and (x.requires_grad or w.requires_grad):
         return _apply_with_stats(_Depthwise, x, w, self.stride, ph[0], pw[0], Ho, Wo, want_stats, self.graph, self.kernel)
       return _run_depthwise(_nhwc(x), w, self.stride, ph[0], pw[0], Ho, Wo, want_stats)
@@ -2225,12 +2189,37 @@ class BatchNormAct:
     # producer that requantises for this layer writes codes exactly when that consumer multiplies codes
     self.consumer = None
 
+  def _mode(self, *tensors, op=None):
+    """(mode, bits, slot) of a call of this layer -- the ONE place that decides it.  BN_TRAIN: training, batch statistics.
+    BN_EVAL_GRAD: inference mode WITH gradients (moving statistics; gamma / beta and everything upstream still trained): gradients
+    are enabled, the graph is not frozen, and the layer's gamma or one of `tensors` (the call's inputs) requires them.  BN_EVAL:
+    inference without gradients.  A caller WITHOUT a tensor (_static, folds_into_producer: they decide before the input exists) gets
+    the conservative answer: gradients enabled on a graph that is not frozen counts as "may need gradients", whatever requires_grad
+    will say.  `bits` / `slot`: the quantiser of the activation `op` behind the BN (default: the layer's own) for a call with
+    tensors, None without one."""
+    g = self.graph
+    bits = slot = None
+    if tensors:                                   # (a caller without a tensor launches nothing: it gets no quantiser either)
+      op = op if op is not None else self.op
+      bits = op.bits if op is not None else None
+      slot = g.act_slots[op.index] if bits is not None else None
+    grad = torch.is_grad_enabled()
+    if g.training and grad:
+      return BN_TRAIN, bits, slot
+    if not grad or g.frozen:
+      return BN_EVAL, bits, slot
+    if tensors:
+      if not (self.gamma.tensor.requires_grad or any(t.requires_grad for t in tensors)):
+        return BN_EVAL, bits, slot
+      if bits is not None:
+        raise NotImplementedError('inference-mode BN with gradients and activation quantisation (no learner needs it)')
+    return BN_EVAL_GRAD, None, None
+
   def _static(self) -> bool:
     """Inference on a graph with fixed activation ranges, this layer quantising: the clamping kernels, no statistics pass."""
     g = self.graph
     return (g.act_static is not None and self.op is not None and self.op.bits is not None and g.taps is None
-            and not (g.training and torch.is_grad_enabled())
-            and not (torch.is_grad_enabled() and not g.frozen))
+            and self._mode()[0] == BN_EVAL)
 
   def requantises(self) -> bool:
     """A packed producer may apply this layer in its epilogue: fixed ranges, at most 8 bits, no gradients."""
@@ -2238,7 +2227,7 @@ class BatchNormAct:
 
   def requant_plan(self, shape, is_cuda: bool):
     """(scale_shift, alpha_beta row, write codes?) for a producer that applies this layer to an output of NCHW `shape`."""
-    ss = self._eval_scale_shift(self.gamma.tensor)
+    ss = self._inference_scale_shift(self.gamma.tensor, None)      # a fixed range: no slot
     as_codes = bool(self.graph.int8 and self.codes_ok and self.consumer is not None and self.consumer.takes_codes(shape, is_cuda))
     return ss, self.graph.act_static[self.op.index], as_codes
 
@@ -2257,38 +2246,32 @@ class BatchNormAct:
     g = self.graph
     if not FOLD_EVAL_BN or g.taps is not None or not g.fuse_conv1x1:
       return False
-    if g.training and torch.is_grad_enabled():
-      return False
-    if torch.is_grad_enabled() and not g.frozen:
-      return False                                # inference-mode BN WITH gradients (_BnEvalAct): its input must exist
+    if self._mode()[0] != BN_EVAL:
+      return False                                # training; inference-mode BN WITH gradients: its input must exist
     return self.op is None or self.op.bits is None
 
   def __call__(self, x: torch.Tensor, with_skip: bool = False):
     """`with_skip`: also return x for the block's identity shortcut (see _BnLazy)."""
     g = self.graph
-    bits = self.op.bits if self.op is not None else None
-    slot = g.act_slots[self.op.index] if (self.op is not None and bits is not None) else None
-    lazy = self.lazy_ok and g.fuse_conv1x1 and isinstance(x, torch.Tensor) and fusable_tensor(x)
     skip = x
     if getattr(x, '_pf_bn_done', None) is self:   # applied in the epilogue of the producing convolution (Conv2D `out_bn`)
       y = x
-    elif g.training and torch.is_grad_enabled():
-      stats = getattr(x, '_pf_stats', None)      # left by the fused convolution that produced x
-      if lazy:
-        box = []
-        alias, skip = _BnLazy.apply(_nhwc(x), self.gamma.tensor, self.beta.tensor, self, g, slot, bits, box, stats)
-        y = LazyAct(alias, box[0], self.act, slot, bits, x.numel() // self.C, self.C, mean_invstd=box[1])
-        box.append(weakref.ref(y))
-      else:
-        box = {}
-        y = _BnActQuant.apply(x, self.gamma.tensor, self.beta.tensor, self, g, True, slot, bits, stats, box)
-        y._pf_bn = box
-    elif torch.is_grad_enabled() and not g.frozen and (x.requires_grad or self.gamma.tensor.requires_grad):
-      if bits is not None:
-        raise NotImplementedError('inference-mode BN with gradients and activation quantisation (no learner needs it)')
-      y = _BnEvalAct.apply(materialize(x), self.gamma.tensor, self.beta.tensor, self, g)
     else:
-      y = self._inference(_nhwc(x), slot, bits, lazy)
+      mode, bits, slot = self._mode(x)
+      lazy = self.lazy_ok and g.fuse_conv1x1 and isinstance(x, torch.Tensor) and fusable_tensor(x)
+      if mode == BN_TRAIN:
+        stats = getattr(x, '_pf_stats', None)    # left by the fused convolution that produced x
+        rec = BnSums()                           # lets a single consuming convolution fuse the BN-backward sums
+        if lazy:
+          alias, skip = _BnLazy.apply(_nhwc(x), self.gamma.tensor, self.beta.tensor, self, g, slot, rec, stats)
+          y = LazyAct(alias, rec.scale_shift, self.act, slot, bits, x.numel() // self.C, self.C, bn=rec)
+        else:
+          y = _BnActQuant.apply(x, self.gamma.tensor, self.beta.tensor, self, g, True, slot, bits, stats, rec)
+          y._pf_bn = rec
+      elif mode == BN_EVAL_GRAD:
+        y = _BnActQuant.apply(materialize(x), self.gamma.tensor, self.beta.tensor, self, g, False, None, None)
+      else:
+        y = self._inference(_nhwc(x), slot, bits, lazy)
     if g.taps is not None and isinstance(y, torch.Tensor):
       y = _pass_tag(x, y)
     return (y, skip) if with_skip else y
@@ -2302,61 +2285,51 @@ class BatchNormAct:
       return None
     if self._static():
       return None                                 # pf_bn_act_quant_pool has no clamp: the separate chain through the static pass
-    bits = self.op.bits if self.op is not None else None
-    slot = g.act_slots[self.op.index] if (self.op is not None and bits is not None) else None
-    if g.training and torch.is_grad_enabled():
-      return _BnActPool.apply(x, self.gamma.tensor, self.beta.tensor, self, g, True, slot, bits, getattr(x, '_pf_stats', None))
-    if torch.is_grad_enabled() and not g.frozen and (x.requires_grad or self.gamma.tensor.requires_grad):
-      if bits is not None:
-        raise NotImplementedError('inference-mode BN with gradients and activation quantisation (no learner needs it)')
-      return _BnActPool.apply(x, self.gamma.tensor, self.beta.tensor, self, g, False, None, None)
+    mode, bits, slot = self._mode(x)
+    if mode != BN_EVAL:
+      return _BnActPool.apply(x, self.gamma.tensor, self.beta.tensor, self, g, mode == BN_TRAIN, slot, bits,
+                              getattr(x, '_pf_stats', None) if mode == BN_TRAIN else None)
     x = _nhwc(x)
-    C = self.C
-    rows = x.numel() // C
-    pooled = torch.empty((x.shape[0], C), dtype=x.dtype, device=x.device)
-    if bits is None:
-      hip.bn_act_quant_pool(x, pooled, rows, C, rows // x.shape[0], self._eval_scale_shift(x), self.act, None, 8, False)
-      return pooled
-    hip.bn_act_quant_pool(x, pooled, rows, C, rows // x.shape[0], self._calibrated_scale_shift(x, slot), self.act, slot, bits,
-                          True)
+    rows = x.numel() // self.C
+    pooled = torch.empty((x.shape[0], self.C), dtype=x.dtype, device=x.device)
+    hip.bn_act_quant_pool(x, pooled, rows, self.C, rows // x.shape[0], self._inference_scale_shift(x, slot), self.act, slot,
+                          bits if bits is not None else 8, bits is not None)
     return pooled
 
   def _inference(self, x, slot, bits, lazy):
-    """Inference mode without gradients, x in NHWC memory."""
+    """Inference mode without gradients, x in NHWC memory: lazy?  codes?  a fixed range or the batch's?  Then one launch."""
     C = self.C
     rows = x.numel() // C
+    static = bits is not None and self._static()
+    ss = self._inference_scale_shift(x, None if static else slot)
     if bits is None and lazy:
-      return LazyAct(x, self._eval_scale_shift(x), self.act, None, None, rows, C)
-    # this layer hands out codes: every consumer may multiply them, and the one that does not materialises
-    as_codes = bits is not None and bits <= 8 and self.graph.int8 and self.codes_ok and x.is_cuda and x.dim() == 4
-    if bits is not None and self._static():
-      ss, ab = self._eval_scale_shift(x), self.graph.act_static[self.op.index]
-      if as_codes:
-        return StaticCodesAct(x, ss, self.act, ab, bits, rows, C)
-      q = torch.empty_like(x)
-      hip.bn_act_quant_static(x, q, rows, C, ss, self.act, ab, bits)
-      return q
-    if as_codes:
-      return CodesAct(x, self._calibrated_scale_shift(x, slot), self.act, slot, bits, rows, C)
+      return LazyAct(x, ss, self.act, None, None, rows, C)
+    if bits is not None and bits <= 8 and self.graph.int8 and self.codes_ok and x.is_cuda and x.dim() == 4:
+      # this layer hands out codes: every consumer may multiply them, and the one that does not materialises
+      if static:
+        return StaticCodesAct(x, ss, self.act, self.graph.act_static[self.op.index], bits, rows, C)
+      return CodesAct(x, ss, self.act, slot, bits, rows, C)
     q = torch.empty_like(x)
-    if bits is None:
-      # inference BN + act only: y = act(scale*x + shift); the teacher's (frozen) scale/shift is cached
-      hip.bn_act_quant_apply(x, q, rows, C, self._eval_scale_shift(x), self.act, None, 8, False)
-      return q
-    hip.bn_act_quant_apply(x, q, rows, C, self._calibrated_scale_shift(x, slot), self.act, slot, bits, True)
+    if static:
+      hip.bn_act_quant_static(x, q, rows, C, ss, self.act, self.graph.act_static[self.op.index], bits)
+    else:
+      hip.bn_act_quant_apply(x, q, rows, C, ss, self.act, slot, bits if bits is not None else 8, bits is not None)
     return q
 
+  def _inference_scale_shift(self, x, slot):
+    """scale / shift for inference without gradients.  No `slot` (a layer without a quantiser, or one with a fixed range): the
+    moving statistics folded, the teacher's (frozen) pair cached.  With one: the calibrating statistics pass."""
+    return self._eval_scale_shift(x) if slot is None else self._calibrated_scale_shift(x, slot)
+
   def _calibrated_scale_shift(self, x, slot):
-    """scale / shift of the eval graph of a quantising learner: the moving statistics, plus one statistics pass over x that
-    leaves the freshly calibrated activation range in `slot`."""
+    """scale / shift of the eval graph of a quantising learner: the moving statistics, plus one statistics pass over x whose
+    finalize leaves the freshly calibrated activation range in `slot`."""
     g, C = self.graph, self.C
     rows = x.numel() // C
     with torch.no_grad():
-      nblk = _bn_blocks(rows, C)
-      partial = g.scratch(nblk * 4 * C)
+      partial, nblk, _ = _bn_statistics(x, rows, C, g)
       ss = torch.empty((2, C), dtype=torch.float32, device=x.device)
       mi = torch.empty((2, C), dtype=torch.float32, device=x.device)
-      hip.bn_stats(x, rows, C, partial, nblk)
       hip.bn_finalize(partial, nblk, rows, C, x, self.gamma.tensor, self.beta.tensor, self.moving_mean.tensor,
                       self.moving_var.tensor, self.momentum, self.eps, g.training, self.act, ss, mi, slot)
     return ss
@@ -2407,26 +2380,19 @@ class BatchNormAddAct:
     x, shortcut = materialize(x), materialize(shortcut)
     if not self.takes(x, shortcut):
       return self.relu(self.bn(x) + shortcut)
-    bits = self.op.bits
-    slot = g.act_slots[self.op.index] if bits is not None else None
-    gamma, beta = self.bn.gamma.tensor, self.bn.beta.tensor
-    if g.training and torch.is_grad_enabled():
-      u, skip = _BnAddActQuant.apply(x, shortcut, gamma, beta, self, g, True, slot, bits, getattr(x, '_pf_stats', None))
+    mode, bits, slot = self.bn._mode(x, shortcut, op=self.op)
+    if mode != BN_EVAL:
+      u, skip = _BnAddActQuant.apply(x, shortcut, self.bn.gamma.tensor, self.bn.beta.tensor, self, g, mode == BN_TRAIN, slot, bits,
+                                     getattr(x, '_pf_stats', None) if mode == BN_TRAIN else None)
       u._pf_skip = skip                            # for the second consumer of the block output (see _BnAddActQuant)
       return u
-    if torch.is_grad_enabled() and not g.frozen and (x.requires_grad or shortcut.requires_grad or gamma.requires_grad):
-      if bits is not None:
-        raise NotImplementedError('inference-mode BN with gradients and activation quantisation (no learner needs it)')
-      u, skip = _BnAddActQuant.apply(x, shortcut, gamma, beta, self, g, False, None, None)
-      u._pf_skip = skip
-      return u
-    # inference mode without gradients: the moving statistics folded to scale / shift, the same pass
+    # inference mode without gradients: the moving statistics folded to scale / shift (the BN itself has no quantiser), the same pass
     x, r = _nhwc(x), _nhwc(shortcut)
     rows = x.numel() // self.C
     u = torch.empty_like(x)
     if bits is not None:
       hip.minmax_slots_init(slot)
-    hip.bn_add_act_fwd(x, r, u, rows, self.C, self.bn._eval_scale_shift(x), self.act, slot)
+    hip.bn_add_act_fwd(x, r, u, rows, self.C, self.bn._inference_scale_shift(x, None), self.act, slot)
     if bits is not None:
       hip.uq_apply(u, u, slot, bits, None)
     return u

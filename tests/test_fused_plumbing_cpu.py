@@ -125,7 +125,7 @@ def test_a_step_leaves_no_reference_cycles(monkeypatch, fuse, filters, size):
   fake = FakeHip()
   monkeypatch.setattr(G, 'hip', fake)
   monkeypatch.setattr(G, 'fusable_tensor', lambda t: True)
-  g, net = _build(fuse, fake, 6, filters)                 # filters = 64: + the implicit-GEMM 3x3 path with its BN box
+  g, net = _build(fuse, fake, 6, filters)                 # filters = 64: + the implicit-GEMM 3x3 path with its BN record
   g.begin_step = lambda: None
   fake.minmax_slots_init(g.act_slots)
   x = torch.randn(4, 3, size, size).contiguous(memory_format=torch.channels_last)
@@ -240,23 +240,53 @@ STEP_LAUNCH_CENSUS = {
     ('mobilenet', 0.25): _MOBILENET_CENSUS,
     # depth multiplier 0.5: a 16-channel first layer on the MobileNet stem kernels
     ('mobilenet', 0.5): dict(_MOBILENET_CENSUS, conv_stem3_fwd=1, conv_stem3_wrw=1),
+    # the network built with forward_eval under gradients (what the pruning-ratio search re-trains): every BN materialised, moving
+    # statistics, the BN backward with zero sums -- no statistics pass, no finalize, no lazy route
+    ('resnet', None, 8, 'eval_grad'): dict(bn_apply=13, bn_bwd_apply=13, bn_bwd_stats=13, col2im=4, conv1x1_plain=28, conv1x1_wrw=14,
+                                           im2col=8),
+    ('resnet', None, 64, 'eval_grad'): dict(bn_apply=13, bn_bwd_apply=13, bn_bwd_stats=13, conv1x1_plain=20, conv1x1_wrw=10,
+                                            conv2d_fwd=7, conv2d_wrw=4),
+    # inference without gradients and without quantisers: bn1 / bn3 lazy, bn2 in conv1's epilogue (and bn3 in the implicit-GEMM conv2's)
+    ('resnet', None, 8, 'no_grad'): dict(bn_apply=1, conv1x1_fwd=10, conv1x1_plain=4, conv_out_affine=4, im2col=4),
+    ('resnet', None, 64, 'no_grad'): dict(bn_apply=1, conv1x1_fwd=6, conv1x1_plain=4, conv2d_fwd=4, conv_out_affine=8),
+    # ... and with 6-bit activations: every BN runs the calibrating statistics pass + finalize in front of its apply pass
+    ('resnet', 6, 8, 'no_grad'): dict(bn_apply=13, bn_finalize=13, bn_stats=13, conv1x1_plain=14, im2col=4),
+    ('resnet', 6, 64, 'no_grad'): dict(bn_apply=13, bn_finalize=13, bn_stats=13, conv1x1_plain=10, conv2d_fwd=4),
+    # ResNet-50 v1 (bottleneck blocks) at 2 x 3 x 32 x 32 with the join kernels on: one forward launch per block + the fork's sum, one
+    # gate launch per block, whose sums replace the statistics pass of the 16 BNs in front of the joins
+    ('resnet_v1', None): dict(bn_add_act_bwd_gate=1, bn_add_act_bwd_gate_add=15, bn_add_act_fwd=17, bn_apply=21, bn_bwd_apply=53,
+                              bn_bwd_stats=8, bn_finalize=53, bn_stats=1, conv1x1_bwd_data_bnstats=16, conv1x1_fwd=16,
+                              conv1x1_plain=40, conv1x1_wrw=36, conv2d_bwd_data_bnstats=13, conv2d_fwd=16, conv2d_wrw=16,
+                              conv_stem_fwd=1, conv_stem_wrw=1),
 }
 
 
 @pytest.mark.parametrize('config', list(STEP_LAUNCH_CENSUS), ids=lambda c: '-'.join(str(v) for v in c))
 def test_step_launch_census(monkeypatch, config):
-  """How often ONE training step (forward + backward) calls each HIP entry point, and through that which route every layer took:
+  """How often ONE training step (forward + backward; a fourth entry of the configuration: 'eval_grad', the same on the network built
+  with forward_eval, or 'no_grad', its forward pass alone) calls each HIP entry point, and through that which route every layer took:
   the 1x1 / im2col / implicit-GEMM / stem / depthwise convolution routes, the lazy and the materialised BN, every fused epilogue.
   The neighbouring tests compare fused against unfused results and assert a few counts each; this one pins all of them, so that a
   change to the plumbing that moves a layer to another route, or adds or drops a launch, shows up as a changed table."""
   from pocketflow_amd import graph as G
   from pocketflow_amd.utils.external.mobilenet_v1 import MobilenetV1
+  mode = config[3] if len(config) > 3 else 'train'
   fake = FakeHip()
+  if config[0] == 'resnet_v1':
+    from pocketflow_amd.utils.external import resnet_model as R
+    from test_resnet_v1_cpu import JoinFakeHip, V1_50
+    fake = JoinFakeHip()
+    monkeypatch.setattr(G, 'BN_JOIN_ANY_DEVICE', True)
   monkeypatch.setattr(G, 'hip', fake)
   monkeypatch.setattr(G, 'fusable_tensor', lambda t: True)
   if config[0] == 'resnet':
     g, net = _build(True, fake, config[1], config[2])
     shape, ncls = (4, 3, 12, 12), 7
+  elif config[0] == 'resnet_v1':
+    g = G.Graph('model', 'cpu', torch.float32)
+    net = R.Model(*V1_50, resnet_version=1, graph=g)
+    g.finalize(seed=3, requires_grad=True)
+    shape, ncls = (2, 3, 32, 32), 10
   else:
     monkeypatch.setattr(G, 'DEPTHWISE_ANY_DEVICE', True)
     g = G.Graph('model', 'cpu', torch.float32)
@@ -268,9 +298,13 @@ def test_step_launch_census(monkeypatch, config):
   wts = torch.randn(shape[0], ncls)
   g.begin_step = lambda: None
   fake.minmax_slots_init(g.act_slots)
-  with g.as_default():
-    logits = net(x, True)
-  (logits * wts).sum().backward()
+  if mode == 'no_grad':
+    with torch.no_grad(), g.as_default():
+      net(x, False)
+  else:
+    with g.as_default():
+      logits = net(x, mode == 'train')                # 'eval_grad': forward_eval, gradients enabled
+    (logits * wts).sum().backward()
   assert dict(fake.calls) == STEP_LAUNCH_CENSUS[config], sorted(fake.calls.items())
 
 

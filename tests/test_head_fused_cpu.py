@@ -140,7 +140,7 @@ def test_pooled_head_plumbing_is_exact_on_cpu(monkeypatch, act_bits):
 @pytest.mark.parametrize('mode,act_bits', [('eval', None), ('eval', 6), ('eval_grad', None)])
 def test_pooled_head_in_inference_mode_is_exact_on_cpu(monkeypatch, mode, act_bits):
   """Inference mode without gradients (cached / fresh scale and shift, with and without a quantiser) and with gradients
-  (_BnEvalAct's case: moving statistics, backward with zero sums)."""
+  (BN_EVAL_GRAD: moving statistics, backward with zero sums)."""
   a = _run_net(monkeypatch, HeadFakeHip(), False, act_bits, mode)
   b = _run_net(monkeypatch, HeadFakeHip(), True, act_bits, mode)
   _close(a, b)

@@ -475,7 +475,7 @@ def test_nuq_rl_bit_search_on_cpu(cpu_learners, caplog, opt_mode, use_buckets):
 
 
 def test_inference_mode_bn_with_gradients(cpu_learners):
-  """graph._BnEvalAct (frozen statistics, trainable gamma / beta) against plain torch autograd."""
+  """graph._BnActQuant in inference mode with gradients (frozen statistics, trainable gamma / beta) against plain torch autograd."""
   FLAGS, fake, tmp = cpu_learners
   import pocketflow_amd.graph as G
   g = G.Graph('model', 'cpu', torch.float32)

@@ -32,7 +32,7 @@ def _setup(tmp_path, **kw):
 
 
 def test_inference_mode_bn_gradients_on_gpu():
-  """graph._BnEvalAct: pf_bn_eval_scale_shift + pf_bn_act_quant_apply forward, pf_bn_bwd_stats / finalize +
+  """graph._BnActQuant with training=False: pf_bn_eval_scale_shift + pf_bn_act_quant_apply forward, pf_bn_bwd_stats / finalize +
   pf_bn_bwd_apply (zero sums) backward, against torch autograd; float32 and bfloat16 activations."""
   import pocketflow_amd.graph as G
   for dtype, tol in ((torch.float32, 1e-4), (torch.bfloat16, 3e-2)):
