@@ -639,6 +639,28 @@ class BnSums(object):
     bs = self.bwd_stats
     return bs[:2] if bs is not None and bs[2] == dq.data_ptr() else None
 
+  def add_consumer(self, fuses: bool):
+    """One more layer reads the BN's output: a consumer whose backward-data kernel can leave the BN-backward sums counts once, any
+    other twice, so that `n_consumers == 1` means "exactly one consumer, and it fuses".  Called from ONE site per layer class
+    (Conv2D.__call__, DepthwiseConv2D.__call__, LazyAct.materialize), keyed by the route the call takes:
+      Conv2D   fused 1x1 reading a LazyAct            1        DepthwiseConv2D   own kernel           2
+               fused 1x1 reading a materialised tensor 2       LazyAct.materialize                    2
+               implicit GEMM                          1
+               im2col, general kernel, library        2
+    These count NOTHING, and that is kept as it was found: the tap (the plain call behind it counts as the route IT takes), gather,
+    int8 / codes and the two stem routes of Conv2D, and the tap, codes and library routes of DepthwiseConv2D.  (The gather and codes
+    routes run in inference only, where no record exists; the stems read images.)"""
+    self.n_consumers += 1 if fuses else 2
+
+  @staticmethod
+  def sums_buffer(G: int, C: int, device):
+    """The [G][2][C] float32 partial sums a backward-data launch with the BN-backward epilogue fills."""
+    return torch.empty((G, 2, C), dtype=torch.float32, device=device)
+
+  def leave(self, partial, G: int, dx):
+    """After that launch: the sums of `dx`, for the BN node's backward to find (sums_for)."""
+    self.bwd_stats = (partial, G, dx.data_ptr())
+
 
 def _bn_enter(ctx, x, gamma, beta, layer, graph, training, slot, stats, rec=None, *more):
   """The forward prologue the BN nodes share: x in NHWC memory, the layer's scale / shift (_bn_scale_shift), and everything
@@ -870,7 +892,7 @@ class LazyAct(object):
 
   def materialize(self) -> torch.Tensor:
     if self._pf_bn is not None:
-      self._pf_bn.n_consumers += 2            # a materialised consumer: its gradient is summed by autograd
+      self._pf_bn.add_consumer(fuses=False)   # a materialised consumer: its gradient is summed by autograd
     if self._q is None:
       self._q = _Materialize.apply(self.x, self)
     return self._q
@@ -1102,6 +1124,19 @@ def _out_size(size: int, k: int, stride: int, pad_total: int) -> int:
   return (size + pad_total - k) // stride + 1
 
 
+def _wants_grad(w, x=None) -> bool:
+  """A layer call takes part in the backward pass: gradients are enabled and the kernel `w` or the input `x` asks for one.  (Without
+  `x`: the MobileNet stem, whose image never does.)"""
+  return torch.is_grad_enabled() and (w.requires_grad or (x is not None and x.requires_grad))
+
+
+def _library_conv_backward(dy, x, w, stride, pad, which: int):
+  """The library's backward of a dense convolution: the data gradient (`which` = 0) or the filter gradient (1).  What remains of it
+  are the A/B switches' other side, geometries outside the kernels' limits and the ResNet stem's image gradient."""
+  return torch.ops.aten.convolution_backward(dy, x, w.detach(), None, [stride, stride], list(pad), [1, 1], False, [0, 0], 1,
+                                             [which == 0, which == 1, False])[which]
+
+
 def _apply_with_stats(fn, *args):
   """`fn.apply(*args, box)` for the convolutions whose forward kernel leaves the BN statistics of its output: apply() wraps the
   result in a new tensor object, so forward hands `_pf_stats` over in `box` and it is put back on the tensor here."""
@@ -1148,6 +1183,45 @@ def _run_conv1x1(x, w2d, lazy, residual, want_stats, stride, out_bn=None):
   return y
 
 
+def _conv1x1_bwd_data_plan(lazy, bn, geom, act, M: int, N: int, K: int):
+  """How _FusedConv1x1.backward computes its input gradient: (launch, outcome, alloc), decided here and nowhere else, from the
+  producer's LazyAct and BnSums record (None: a materialised input / no training-mode BN), the row map `geom` of a strided layer,
+  the producer's activation, the GEMM shape and the switches as they stand at this call.
+    launch   the ONE launch:  'compact' | 'join_stats' | 'join' | 'bnstats' | 'residual' | 'plain' (with the row scatter when strided)
+    outcome  'parked' on the LazyAct for the second consumer | 'delivered' together with the parked gradient | 'plain'
+    alloc    dx is 'compact' ([B][K][Ho][Wo]) | 'empty' | 'zeros' (the row scatter writes every stride-th pixel)
+  'bnstats': the single consumer of a ReLU / ReLU6 BN leaves the BN-backward sums of its dx (BnSums), stride 1 only.
+  The join: an activation with exactly TWO fused consumers (bn1 of a projection block: shortcut convolution + conv1): the consumer
+  whose backward runs first parks its dq on the LazyAct and reports no gradient; the second takes it as the residual operand of its
+  backward-data kernel ('residual') -- the sum autograd would form with a separate add kernel (two reads and one write of the
+  4C-channel tensor) costs one extra read.  The block calls conv1 BEFORE the shortcut convolution, so the (possibly strided,
+  zero-filled) shortcut gradient comes first and the dense one joins it; a strided second consumer has no residual operand under its
+  row map and adds the parked gradient behind its launch.  Opt-in (`lazy.join_ok`, set by the bottleneck block): a parked gradient is
+  only delivered by the second consumer's backward, so both consumers must be known to reach the loss.
+  The projection join (pf_conv1x1_bwd_data_join), where the loaded library offers it and its plan takes the dense consumer's shape:
+  a strided first consumer parks a COMPACT [B][K][Ho][Wo] gradient -- a plain dense GEMM, no zero fill, no row scatter ('compact')
+  -- which the second reads through the inverse row map ('join'); and the second takes the BN-backward sums of the joined gradient
+  in the same launch ('join_stats'), so that _BnLazy.backward finds them (BnSums.bwd_stats) and skips its statistics pass."""
+  relu = act in ('Relu', 'Relu6')
+  join = JOIN_TWO_CONSUMERS and bn is not None and lazy.join_ok and bn.n_consumers == 2 and lazy.n_grad_consumers == 2
+  alloc = 'empty' if geom is None else 'zeros'
+  if not join:
+    fuse_stats = FUSE_BN_BWD_STATS and bn is not None and bn.n_consumers == 1 and geom is None and relu
+    return ('bnstats' if fuse_stats else 'plain'), 'plain', alloc
+  join_entry = getattr(hip, 'conv1x1_bwd_data_join', None) if PROJ_JOIN else None
+  if lazy.pending is None:                       # the first of the two
+    if geom is not None and join_entry is not None and lazy.dense_out is not None:
+      rows = M // (geom[0] * geom[1]) * geom[2] * geom[3]                      # pixels of the dense consumer's (= the full) map
+      if hip.conv1x1_join_plan(rows, lazy.dense_out, K) != 0:
+        return 'compact', 'parked', 'compact'
+    return 'plain', 'parked', alloc
+  if geom is not None:                           # the second, strided
+    return 'plain', 'delivered', alloc
+  if join_entry is not None and PROJ_JOIN_STATS and FUSE_BN_BWD_STATS and relu and hip.conv1x1_join_plan(M, N, K, True) != 0:
+    return 'join_stats', 'delivered', alloc
+  return ('join' if lazy.pending_geom is not None else 'residual'), 'delivered', alloc
+
+
 class _FusedConv1x1(torch.autograd.Function):
   """y = conv1x1(Q(x), W) [+ residual], Q = the producer BN's normalise/act/fake-quant (prologue)."""
 
@@ -1186,62 +1260,39 @@ class _FusedConv1x1(torch.autograd.Function):
       dw = _filter_grad(graph, ctx.w_leaf, ctx.w_var, (dy, x, w2d, ss, lazy), 'conv1x1_wrw', float((M * K + M * N) * 2), wrw)
     if ctx.needs_input_grad[0]:
       wt = _bwd_data_weight(graph, ctx.w_var, ctx.w_leaf).view(K, N)           # [K][N]
-      fuse_stats = FUSE_BN_BWD_STATS and bn is not None and bn.n_consumers == 1 and geom is None and act in ('Relu', 'Relu6')
-      # An activation with exactly TWO fused consumers (bn1 of a projection block: shortcut convolution + conv1): the
-      # consumer whose backward runs first parks its dq on the LazyAct and reports no gradient; the second takes it as the
-      # residual operand of its backward-data kernel -- the sum autograd would form with a separate add kernel (two reads
-      # and one write of the 4C-channel tensor) costs one extra read.  The block calls conv1 BEFORE the shortcut
-      # convolution, so the (possibly strided, zero-filled) shortcut gradient comes first and the dense one joins it.
-      # Opt-in (`lazy.join_ok`, set by the bottleneck block): a parked gradient is only delivered by the second consumer's
-      # backward, so both consumers must be known to reach the loss.
-      join = (JOIN_TWO_CONSUMERS and bn is not None and lazy.join_ok and bn.n_consumers == 2
-              and lazy.n_grad_consumers == 2)
-      second = join and lazy.pending is not None
-      res = lazy.pending if (second and geom is None) else None
-      # The projection join (pf_conv1x1_bwd_data_join), where the loaded library offers it and its plan takes the dense consumer's
-      # shape: a strided first consumer parks a COMPACT [B][K][Ho][Wo] gradient -- a plain dense GEMM, no zero fill, no row scatter --
-      # which the second reads through the inverse row map; and the second takes the BN-backward sums of the joined gradient in
-      # the same launch, so that _BnLazy.backward finds them (BnSums.bwd_stats) and skips its statistics pass.
-      join_entry = getattr(hip, 'conv1x1_bwd_data_join', None) if PROJ_JOIN else None
-      compact = (join and not second and geom is not None and join_entry is not None and lazy.dense_out is not None
-                 and hip.conv1x1_join_plan(x.shape[0] * x.shape[2] * x.shape[3], lazy.dense_out, K) != 0)
-      rgeom = lazy.pending_geom if res is not None else None
-      join_stats = (res is not None and join_entry is not None and PROJ_JOIN_STATS and FUSE_BN_BWD_STATS
-                    and act in ('Relu', 'Relu6') and hip.conv1x1_join_plan(M, N, K, True) != 0)
-      if compact:
+      launch, outcome, alloc = _conv1x1_bwd_data_plan(lazy, bn, geom, act, M, N, K)
+      if alloc == 'compact':
         dx = torch.empty((x.shape[0], K, geom[0], geom[1]), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-      elif geom is None:
-        dx = torch.empty_like(x)
       else:
-        dx = torch.zeros_like(x)
-      with region('conv1x1_bwd_data', float((M * K * (2 if (fuse_stats or res is not None) else 1) + M * N) * 2)):
-        if compact:
+        dx = torch.empty_like(x) if alloc == 'empty' else torch.zeros_like(x)
+      res = lazy.pending if launch in ('join_stats', 'join', 'residual') else None
+      with region('conv1x1_bwd_data', float((M * K * (1 if launch in ('compact', 'plain') else 2) + M * N) * 2)):
+        leaves_sums = launch in ('join_stats', 'bnstats')
+        if leaves_sums:
+          G = hip.conv1x1_stats_groups(M, K, N)
+          partial = bn.sums_buffer(G, K, x.device)
+        if launch == 'compact':
           hip.conv1x1_fwd(dy, wt, dx, M, K, N)
-        elif join_stats:
-          G = hip.conv1x1_stats_groups(M, K, N)
-          partial = torch.empty((G, 2, K), dtype=torch.float32, device=x.device)
-          join_entry(dy, wt, dx, res, M, N, K, rgeom=rgeom, bn_x=x, bn_scale_shift=bn.scale_shift,
-                     bn_mean_invstd=bn.mean_invstd, bn_act=act, partial=partial)
-          bn.bwd_stats = (partial, G, dx.data_ptr())
-        elif rgeom is not None:
-          join_entry(dy, wt, dx, res, M, N, K, rgeom=rgeom)
-        elif fuse_stats:
-          G = hip.conv1x1_stats_groups(M, K, N)
-          partial = torch.empty((G, 2, K), dtype=torch.float32, device=x.device)
+        elif launch == 'join_stats':
+          hip.conv1x1_bwd_data_join(dy, wt, dx, res, M, N, K, rgeom=lazy.pending_geom, bn_x=x, bn_scale_shift=bn.scale_shift,
+                                    bn_mean_invstd=bn.mean_invstd, bn_act=act, partial=partial)
+        elif launch == 'join':
+          hip.conv1x1_bwd_data_join(dy, wt, dx, res, M, N, K, rgeom=lazy.pending_geom)
+        elif launch == 'bnstats':
           hip.conv1x1_bwd_data_bnstats(dy, wt, dx, x, bn.scale_shift, bn.mean_invstd, act, partial, M, N, K)
-          bn.bwd_stats = (partial, G, dx.data_ptr())
-        elif res is not None:
+        elif launch == 'residual':
           hip.conv1x1_fwd(dy, wt, dx, M, K, N, R=res)
         else:
           hip.conv1x1_fwd(dy, wt, dx, M, K, N, geom=geom, ymap=geom is not None)
-      if join:
-        if not second:
-          lazy.pending, dx = dx, None           # parked: the second consumer delivers the sum
-          lazy.pending_geom = geom if compact else None
-        else:
-          if res is None:
-            dx = dx + lazy.pending              # the second one is the strided one: no residual operand under a row map
-          lazy.pending = lazy.pending_geom = None
+        if leaves_sums:
+          bn.leave(partial, G, dx)
+      if outcome == 'parked':
+        lazy.pending, dx = dx, None             # the second consumer delivers the sum
+        lazy.pending_geom = geom if launch == 'compact' else None
+      elif outcome == 'delivered':
+        if res is None:
+          dx = dx + lazy.pending                # the second one is the strided one: no residual operand under a row map
+        lazy.pending = lazy.pending_geom = None
     return dx, dw, (dy if has_res else None), None, None, None, None, None, None
 
 
@@ -1337,8 +1388,7 @@ class _Conv2dIgemm(torch.autograd.Function):
         dw = dwk.permute(0, 3, 1, 2)
       else:
         with region('conv2d_wrw', nbytes):
-          dw = torch.ops.aten.convolution_backward(dy, x, w.detach(), None, [stride, stride], list(pad), [1, 1], False,
-                                                   [0, 0], 1, [False, True, False])[1]
+          dw = _library_conv_backward(dy, x, w, stride, pad, 1)
     if ctx.needs_input_grad[0]:
       # backward-data = the same kernel with the roles of C and N swapped: its contraction runs over N in steps of 64
       mfma = N % 64 == 0 and C % 8 == 0 and igemm_limits_ok(dy.numel(), w.numel(), R * S)
@@ -1357,7 +1407,7 @@ class _Conv2dIgemm(torch.autograd.Function):
           if fuse:
             G = (hip.conv2d_stats_groups(B * H * W, C, geom=(B, H, W, N, C, R, S, 1, R - 1 - pad[0], S - 1 - pad[1], H, W))
                  if stride == 1 else hip.conv2d_bwd_data_strided_stats_groups(B, H, W, C, stride))
-            partial = torch.empty((G, 2, C), dtype=torch.float32, device=x.device)
+            partial = bn_sums.sums_buffer(G, C, x.device)
             bn = dict(partial=partial, bn_x=bn_sums.x, bn_scale_shift=bn_sums.scale_shift, bn_mean_invstd=bn_sums.mean_invstd,
                       bn_act=bn_sums.act)
           if stride == 1:
@@ -1365,7 +1415,7 @@ class _Conv2dIgemm(torch.autograd.Function):
           else:
             hip.conv2d_bwd_data_strided(dy, wb, dx, B, H, W, C, N, R, S, stride, pad[0], pad[1], Ho, Wo, **bn)
           if fuse:
-            bn_sums.bwd_stats = (partial, G, dx.data_ptr())
+            bn_sums.leave(partial, G, dx)
       elif OWN_CONV2D and OWN_CONV_GENERIC and x.is_cuda and dy.dtype == x.dtype and w.dtype == x.dtype:
         # geometries outside the MFMA kernels' limits (odd strided sizes, channel counts, 31-bit offsets): the general kernel
         dx = torch.empty_like(x)
@@ -1374,8 +1424,7 @@ class _Conv2dIgemm(torch.autograd.Function):
                              slab=_convg_slab(graph, x.dtype, B * H * W, C, R * S * N))
       else:
         with region('conv2d_bwd_data', float((dy.numel() + x.numel()) * 2)):
-          dx = torch.ops.aten.convolution_backward(dy, x, w.detach(), None, [stride, stride], list(pad), [1, 1], False,
-                                                   [0, 0], 1, [True, False, False])[0]
+          dx = _library_conv_backward(dy, x, w, stride, pad, 0)
     return dx, dw, None, None, None, None, None, None, None
 
 
@@ -1547,11 +1596,9 @@ class _StemConv(torch.autograd.Function):
         dw = _filter_grad(graph, w, w_var, (dy, x), 'conv_stem_wrw', nbytes, wrw)
       else:
         with region('conv_stem_wrw', nbytes):
-          dw = torch.ops.aten.convolution_backward(dy, x, w.detach(), None, [2, 2], [3, 3], [1, 1], False, [0, 0], 1,
-                                                   [False, True, False])[1]
+          dw = _library_conv_backward(dy, x, w, 2, (3, 3), 1)
     if ctx.needs_input_grad[0]:
-      dx = torch.ops.aten.convolution_backward(dy, x, w.detach(), None, [2, 2], [3, 3], [1, 1], False, [0, 0], 1,
-                                               [True, False, False])[0]
+      dx = _library_conv_backward(dy, x, w, 2, (3, 3), 0)
     return dx, dw, None, None
 
 
@@ -1598,45 +1645,14 @@ class _Stem3Conv(torch.autograd.Function):
     return None, dw, None, None, None, None
 
 
-def own_stem3_ok(x, conv, front_pads, out_hw) -> bool:
-  """The MobileNet stem on pf_stem3.hip: bf16 NHWC image batch, 3 -> 16 | 32 channels, 3x3 / stride 2, no bias, no image gradient."""
-  return (OWN_STEM and conv.bias is None and isinstance(x, torch.Tensor) and fusable_tensor(x) and x.dim() == 4 and conv.k == 3
-          and conv.graph.fuse_conv1x1 and not x.requires_grad and x.is_contiguous(memory_format=torch.channels_last)
-          and hip.conv_stem3_supported(x.shape[2], x.shape[3], x.shape[1], conv.kernel.ref_shape[3], conv.k, conv.stride,
-                                       front_pads[0], front_pads[1], out_hw[0], out_hw[1])
-          and hip.conv_stem3_wrw_slabs(x.shape[0], x.shape[2], x.shape[3], conv.kernel.ref_shape[3], front_pads[0], front_pads[1],
-                                       out_hw[0], out_hw[1]) > 0)
-
-
-def own_stem_ok(x, conv, pad) -> bool:
-  return (OWN_STEM and conv.bias is None and isinstance(x, torch.Tensor) and fusable_tensor(x) and x.dim() == 4
-          and pad[0] == pad[1] and conv.graph.fuse_conv1x1
-          and x.is_contiguous(memory_format=torch.channels_last)
-          and hip.conv_stem_supported(x.shape[2], x.shape[3], x.shape[1], conv.kernel.ref_shape[3], conv.k, conv.stride, pad[0]))
-
-
 def igemm_limits_ok(n_in_elems: int, n_kernel_elems: int, taps: int) -> bool:
   """Mirror of the argument checks of pf_conv2d_fwd (pf_igemm.hip): 31-bit byte offsets, 32-bit tap mask."""
   return n_in_elems < (1 << 30) and n_kernel_elems < (1 << 30) and taps <= 32
 
 
-def own_conv2d_ok(x, conv, pad) -> bool:
-  kh, kw, cin, cout = conv.kernel.ref_shape
-  return (OWN_CONV2D and conv.k > 1 and conv.bias is None and isinstance(x, torch.Tensor) and fusable_tensor(x)
-          and x.dim() == 4 and cin % 64 == 0 and cout % 8 == 0
-          and conv.graph.fuse_conv1x1 and igemm_limits_ok(x.numel(), kh * kw * cin * cout, kh * kw))
-
-
 def fusable_tensor(t: torch.Tensor) -> bool:
   """pf_conv.hip works on bf16 device tensors (the float32 parity mode keeps every activation materialised)."""
   return t.is_cuda and t.dtype == torch.bfloat16
-
-
-def fused_conv1x1_ok(x, conv) -> bool:
-  t = x.x if isinstance(x, LazyAct) else x
-  return (conv.k == 1 and conv.bias is None and fusable_tensor(t) and t.dim() == 4
-          and conv.kernel.ref_shape[2] % 8 == 0 and conv.kernel.ref_shape[3] % 8 == 0
-          and conv.padding in ('SAME', 'VALID', 0) and conv.graph.fuse_conv1x1)
 
 
 # =================================================================================================
@@ -1768,6 +1784,30 @@ _INT8_PAYS_STATIC = frozenset([(1, 256, 64, 1)])
 _INT8_DW_PAYS_STATIC = frozenset([(32, 1), (64, 2), (128, 1), (128, 2), (256, 1), (256, 2), (512, 1), (512, 2), (1024, 1)])
 
 
+# What Conv2D._route / DepthwiseConv2D._route decide for one call, a plain tuple (it is built once per layer call):
+#   (name, x, pad, out_hw, out_bn, geom)
+# `name`: the route; the layer launches it in `_call_<name>`.  `x`: the prepared input -- materialised where the route reads a tensor,
+# padded where its kernel pads both ends alike, never converted, so that it still carries the producer's tags.  `pad`: (pad_h, pad_w);
+# for the routes that take 'SAME' padding by its FRONT pads, those.  `out_bn`: the BatchNormAct the launch applies in its epilogue
+# (folded; on the int8 routes the requantising one).  `geom`: the int8 geometry.  What a route does not need is None.  The record
+# lives for the call and references inputs, never an output.
+ROUTE_NAME, ROUTE_X = 0, 1
+
+# the Conv2D routes that count themselves on the producer's BnSums (the table stands at BnSums.add_consumer)
+_CONV2D_COUNTED = frozenset(['conv1x1', 'igemm', 'im2col', 'general', 'library'])
+
+
+@contextlib.contextmanager
+def _plain_call(graph, fusion_off: bool = False):
+  """A layer's plain() runs its __call__ with the taps off (and, for Conv2D, fusion off): the switches are put back behind it."""
+  saved = graph.taps, graph.fuse_conv1x1
+  graph.taps, graph.fuse_conv1x1 = None, graph.fuse_conv1x1 and not fusion_off
+  try:
+    yield
+  finally:
+    graph.taps, graph.fuse_conv1x1 = saved
+
+
 class Conv2D:
   """tf.layers.conv2d / slim.conv2d: NHWC, kernel HWIO (stored KRSC), padding 'SAME' | 'VALID'."""
 
@@ -1789,70 +1829,128 @@ class Conv2D:
     BatchNormAct -- leave per-channel statistics of the output on the tensor (1x1 fused path only); `out_bn`: the ONLY
     consumer is that BatchNormAct in inference mode (`out_bn.folds_into_producer()`): the MFMA kernels apply it in their
     epilogue and tag the output, which the layer then passes through; any other route ignores the hint."""
-    w = self.kernel.tensor
-    # fixed activation ranges: a quantising consumer BatchNormAct goes into the epilogue of the kernel on codes (_call_int8) alone
+    r = self._route(x, residual, out_bn)
+    name = r[ROUTE_NAME]
+    if name in _CONV2D_COUNTED:                  # the ONE place a Conv2D counts itself on its producer (BnSums.add_consumer)
+      bn_sums = getattr(r[ROUTE_X], '_pf_bn', None)
+      if bn_sums is not None:
+        bn_sums.add_consumer(fuses=name == 'igemm' or (name == 'conv1x1' and isinstance(r[ROUTE_X], LazyAct)))
+    return getattr(self, '_call_' + name)(r, residual, want_stats)
+
+  def _route(self, x, residual, out_bn) -> tuple:
+    """Which kernel family takes this call -- the ONE place that decides it -- and what its launch needs (the route record above).  The checks run
+    in this order, and the order matters:
+      (narrowing)  `requant` (a quantising consumer BN on a graph with fixed ranges: for the kernel on codes alone) and `out_bn` (dropped
+                   with a residual, or where the BN does not fold) are settled before any route is asked.
+      tap          before everything: the channel pruner records the layer whatever route it would take (_tapped, which re-enters
+                   through plain() with taps and fusion off); a LazyAct is materialised for it.
+      gathered     a physically shrunk layer (Graph.apply_gathers): inference on pf_conv_gather.hip.
+      (int8)       a packed layer RAISES under gradients, whatever its input; then
+      int8         a CodesAct whose codes pf_conv_i8_fwd takes (_int8_geometry); any other CodesAct is materialised here -- the
+                   fake-quantised tensor of the apply pass, as without int8 -- and goes on down the list.
+      conv1x1      1x1 on pf_conv.hip, the producer BN's normalise / act / fake-quant in the prologue: the only route that reads a
+                   LazyAct, so it is asked before the input is materialised for all the others.
+      stem3        the MobileNet stem, asked BEFORE _symmetric_pads: its kernel takes the asymmetric 'SAME' pads by their front pads
+                   and must not see (or pay for) a padded copy of the image.  Asks about the image's gradient: it computes none.
+      stem         the ResNet stem, asked AFTER it: its kernel pads both ends alike.
+      igemm        RxS on the implicit-GEMM kernel (cin % 64 == 0).
+      im2col       few-channel RxS as im2col + the 1x1 kernels (im2col_conv_ok).
+      general      everything else our kernels take (convg_ok): pf_convg.hip.
+      library      the rest.
+    `out_bn` is honoured by the conv1x1 and igemm routes where they run without gradients and by the gathered route; every other
+    route ignores it and the BatchNormAct runs its own pass."""
+    g, w = self.graph, self.kernel.tensor
     requant = out_bn if (out_bn is not None and residual is None and out_bn.requantises()) else None
     if out_bn is not None and (residual is not None or not out_bn.folds_into_producer()):
       out_bn = None
-    if self.graph.taps is not None:
-      return _tapped(self, materialize(x), residual)
-    if self.kernel.gather_host is not None:      # a physically shrunk layer (Graph.apply_gathers): inference on pf_conv_gather.hip
-      return self._call_gathered(x, residual, out_bn)
-    if self.int8 is not None and torch.is_grad_enabled() and (w.requires_grad or (x.x if isinstance(x, LazyAct) else x).requires_grad):
+    if g.taps is not None:
+      return 'tap', materialize(x), None, None, None, None
+    if self.kernel.gather_host is not None:
+      return 'gathered', x, None, None, out_bn, None
+    if self.int8 is not None and _wants_grad(w, x.x if isinstance(x, LazyAct) else x):
       raise RuntimeError('%s: a convolution packed for int8 runs in inference only: call it under torch.no_grad() on a graph '
                          'finalised with requires_grad=False' % self.kernel.name)
     if isinstance(x, CodesAct):
       geom = self._int8_geometry(x.x.shape, x.x.is_cuda) if self.int8 is not None else None
       if geom is not None:
-        return self._call_int8(x, residual, requant, geom)
-      x = x.materialize()                        # every other consumer: the fake-quantised tensor of the apply pass, as without int8
-    if fused_conv1x1_ok(x, self):                # 1x1 on pf_conv.hip: the producer BN's normalise / act / fake-quant in the prologue
-      lazy = x if isinstance(x, LazyAct) else None
-      bn_sums = getattr(x, '_pf_bn', None)
-      if bn_sums is not None:                     # (a MATERIALISED BN output read by a 1x1: its BN-backward sums are not fused)
-        bn_sums.n_consumers += 1 if lazy is not None else 2
-      xin = lazy.x if lazy is not None else _nhwc(x)
-      if torch.is_grad_enabled() and (xin.requires_grad or w.requires_grad):
-        if lazy is not None and xin.requires_grad:
-          lazy.n_grad_consumers += 1
-          if self.stride == 1:
-            lazy.dense_out = int(w.shape[0])
-        return _apply_with_stats(_FusedConv1x1, xin, w, residual, lazy, want_stats, self.stride, self.graph, self.kernel)
-      w2d = w.detach().permute(0, 2, 3, 1).reshape(w.shape[0], w.shape[1])
-      return _run_conv1x1(xin, w2d, lazy, _nhwc(residual) if residual is not None else None, want_stats,
-                          self.stride, out_bn=out_bn)
+        return 'int8', x, None, None, requant, geom
+      x = x.materialize()
+    kh, kw, cin, cout = self.kernel.ref_shape
+    t = x.x if isinstance(x, LazyAct) else x
+    if (self.k == 1 and self.bias is None and fusable_tensor(t) and t.dim() == 4 and cin % 8 == 0 and cout % 8 == 0
+        and self.padding in ('SAME', 'VALID', 0) and g.fuse_conv1x1):
+      return 'conv1x1', x, None, None, out_bn, None
     x = materialize(x)
-    b = self.bias.tensor.to(x.dtype) if self.bias is not None else None
     ph, pw, out_hw = self._geometry(x.shape)
-    if (self.padding == 'SAME' and residual is None and x.shape[1] == 3 and self.k == 3 and self.stride == 2
-        and own_stem3_ok(x, self, (ph[0], pw[0]), out_hw)):    # the MobileNet stem: asymmetric 'SAME' pads without a padded image copy
-      if torch.is_grad_enabled() and w.requires_grad:
-        return _Stem3Conv.apply(x, w, self.graph, self.kernel, (ph[0], pw[0]), out_hw)
-      return _run_stem3(x, w, (ph[0], pw[0]), out_hw)
+    # what the stem and implicit-GEMM kernels ask alike: no bias, a 4-D bf16 device tensor, fusion on (a padded copy keeps all three)
+    mfma = self.bias is None and isinstance(x, torch.Tensor) and fusable_tensor(x) and x.dim() == 4 and g.fuse_conv1x1
+    if (mfma and OWN_STEM and self.padding == 'SAME' and residual is None and x.shape[1] == 3 and self.k == 3 and self.stride == 2
+        and not x.requires_grad and x.is_contiguous(memory_format=torch.channels_last)
+        and hip.conv_stem3_supported(x.shape[2], x.shape[3], 3, cout, 3, 2, ph[0], pw[0], out_hw[0], out_hw[1])
+        and hip.conv_stem3_wrw_slabs(x.shape[0], x.shape[2], x.shape[3], cout, ph[0], pw[0], out_hw[0], out_hw[1]) > 0):
+      return 'stem3', x, (ph[0], pw[0]), out_hw, None, None
     x, pad = _symmetric_pads(x, ph, pw)
-    if residual is None and own_stem_ok(x, self, pad):         # the ResNet stem
-      if torch.is_grad_enabled() and (x.requires_grad or w.requires_grad):
-        return _StemConv.apply(x, w, self.graph, self.kernel)
-      return _run_stem(x, w)
-    if own_conv2d_ok(x, self, pad):              # RxS on the implicit-GEMM kernel
-      bn_sums = getattr(x, '_pf_bn', None)
-      if bn_sums is not None:
-        bn_sums.n_consumers += 1
-      xin = _nhwc(x)
-      if torch.is_grad_enabled() and (xin.requires_grad or w.requires_grad):
-        y = _apply_with_stats(_Conv2dIgemm, xin, w, self.stride, pad, want_stats, self.graph, bn_sums, self.kernel)
-      else:
-        y = _run_conv2d(xin, w.detach().permute(0, 2, 3, 1), self.stride, pad, want_stats, out_bn=out_bn)
-      return y if residual is None else y + residual
-    bn_sums = getattr(x, '_pf_bn', None)
-    if bn_sums is not None:
-      bn_sums.n_consumers += 2                    # a consumer that cannot fuse the BN-backward sums
-    if im2col_conv_ok(x, self, pad):             # few-channel RxS as im2col + the 1x1 kernels
-      y = _ConvIm2col.apply(_nhwc(x), w, self.stride, pad, out_hw, self.graph, self.kernel)
-    elif convg_ok(x, w):                         # everything else on the general kernel
-      y = conv_generic(x, w, self.bias.tensor if self.bias is not None else None, self.stride, pad, out_hw, self.graph)
+    if (mfma and OWN_STEM and residual is None and pad[0] == pad[1] and x.is_contiguous(memory_format=torch.channels_last)
+        and hip.conv_stem_supported(x.shape[2], x.shape[3], x.shape[1], cout, self.k, self.stride, pad[0])):
+      return 'stem', x, pad, out_hw, None, None
+    if (mfma and OWN_CONV2D and self.k > 1 and cin % 64 == 0 and cout % 8 == 0
+        and igemm_limits_ok(x.numel(), kh * kw * cin * cout, kh * kw)):
+      return 'igemm', x, pad, out_hw, out_bn, None
+    if im2col_conv_ok(x, self, pad):
+      return 'im2col', x, pad, out_hw, None, None
+    return ('general' if convg_ok(x, w) else 'library'), x, pad, out_hw, None, None
+
+  def _call_tap(self, r, residual, want_stats):
+    return _tapped(self, r[ROUTE_X], residual)
+
+  def _call_conv1x1(self, r, residual, want_stats):
+    _, x, _, _, out_bn, _ = r
+    w = self.kernel.tensor
+    lazy = x if isinstance(x, LazyAct) else None
+    xin = lazy.x if lazy is not None else _nhwc(x)
+    if _wants_grad(w, xin):
+      if lazy is not None and xin.requires_grad:
+        lazy.n_grad_consumers += 1
+        if self.stride == 1:
+          lazy.dense_out = int(w.shape[0])
+      return _apply_with_stats(_FusedConv1x1, xin, w, residual, lazy, want_stats, self.stride, self.graph, self.kernel)
+    w2d = w.detach().permute(0, 2, 3, 1).reshape(w.shape[0], w.shape[1])
+    return _run_conv1x1(xin, w2d, lazy, _nhwc(residual) if residual is not None else None, want_stats, self.stride, out_bn=out_bn)
+
+  def _call_stem3(self, r, residual, want_stats):
+    _, x, front_pads, out_hw, _, _ = r
+    w = self.kernel.tensor
+    if _wants_grad(w):                           # (the route was refused to an image that asks for a gradient)
+      return _Stem3Conv.apply(x, w, self.graph, self.kernel, front_pads, out_hw)
+    return _run_stem3(x, w, front_pads, out_hw)
+
+  def _call_stem(self, r, residual, want_stats):
+    x, w = r[ROUTE_X], self.kernel.tensor
+    return _StemConv.apply(x, w, self.graph, self.kernel) if _wants_grad(w, x) else _run_stem(x, w)
+
+  def _call_igemm(self, r, residual, want_stats):
+    _, x, pad, _, out_bn, _ = r
+    w, xin = self.kernel.tensor, _nhwc(x)
+    if _wants_grad(w, xin):
+      y = _apply_with_stats(_Conv2dIgemm, xin, w, self.stride, pad, want_stats, self.graph, getattr(x, '_pf_bn', None), self.kernel)
     else:
-      y = F.conv2d(x, w, b, stride=self.stride, padding=pad)
+      y = _run_conv2d(xin, w.detach().permute(0, 2, 3, 1), self.stride, pad, want_stats, out_bn=out_bn)
+    return y if residual is None else y + residual
+
+  def _call_im2col(self, r, residual, want_stats):
+    _, x, pad, out_hw, _, _ = r
+    y = _ConvIm2col.apply(_nhwc(x), self.kernel.tensor, self.stride, pad, out_hw, self.graph, self.kernel)
+    return y if residual is None else y + residual
+
+  def _call_general(self, r, residual, want_stats):
+    _, x, pad, out_hw, _, _ = r
+    y = conv_generic(x, self.kernel.tensor, self.bias.tensor if self.bias is not None else None, self.stride, pad, out_hw, self.graph)
+    return y if residual is None else y + residual
+
+  def _call_library(self, r, residual, want_stats):
+    _, x, pad, _, _, _ = r
+    b = self.bias.tensor.to(x.dtype) if self.bias is not None else None
+    y = F.conv2d(x, self.kernel.tensor, b, stride=self.stride, padding=pad)
     return y if residual is None else y + residual
 
   def _geometry(self, shape):
@@ -1867,13 +1965,14 @@ class Conv2D:
     return ph, pw, (_out_size(shape[2], self.k, self.stride, ph[0] + ph[1]),
                     _out_size(shape[3], self.k, self.stride, pw[0] + pw[1]))
 
-  def _call_gathered(self, x, residual, out_bn) -> torch.Tensor:
+  def _call_gathered(self, r, residual, want_stats) -> torch.Tensor:
     """The shrunk layer: reduction over the kept input channels only (hip.conv_gather_fwd), with the epilogues the dense inference
     kernels have (bias, residual, the consumer's folded inference-mode BN + activation).  Training a shrunk model is out of scope."""
+    _, x, _, _, out_bn, _ = r
     var = self.kernel
     w = var.tensor
     x = materialize(x)
-    if torch.is_grad_enabled() and (w.requires_grad or x.requires_grad):
+    if _wants_grad(w, x):
       raise RuntimeError('%s: a shrunk (channel-gathered) convolution runs in inference only: call it under torch.no_grad() '
                          'on a graph finalised with requires_grad=False' % var.name)
     if x.dim() != 4 or x.shape[1] != var.cin_full:
@@ -1911,12 +2010,13 @@ class Conv2D:
       return None
     return ph[0], pw[0], Ho, Wo
 
-  def _call_int8(self, x: 'CodesAct', residual, requant, geom) -> torch.Tensor:
-    """The packed layer on the i8 matrix cores: the producer's codes times the signed weights, scales and offsets in the epilogue
-    (pocketflow_amd/int8.py states the formula), the residual added before the one rounding to the compute dtype.  `requant`: the
-    quantising BatchNormAct that alone consumes the output, on a graph with fixed ranges: applied in the epilogue (pf_conv_i8_fwd_q),
-    the output being that layer's output -- codes where ITS consumer multiplies codes, the fake-quantised tensor otherwise.  `geom`:
-    what _int8_geometry returned for x."""
+  def _call_int8(self, r, residual, want_stats) -> torch.Tensor:
+    """The packed layer on the i8 matrix cores: the producer's codes (the record's `x`, a CodesAct) times the signed weights, scales and offsets in
+    the epilogue (pocketflow_amd/int8.py states the formula), the residual added before the one rounding to the compute dtype.
+    `requant` (the record's `out_bn`): the quantising BatchNormAct that alone consumes the output, on a graph with fixed ranges: applied in the epilogue
+    (pf_conv_i8_fwd_q), the output being that layer's output -- codes where ITS consumer multiplies codes, the fake-quantised tensor
+    otherwise.  `geom`: what _int8_geometry returned for the input."""
+    _, x, _, _, requant, geom = r
     p, bits = self.int8, x.bits
     pad_h, pad_w, Ho, Wo = geom
     B, C, H, Wd = x.x.shape
@@ -1930,12 +2030,8 @@ class Conv2D:
 
   def plain(self, x: torch.Tensor) -> torch.Tensor:
     """The convolution alone on a materialised tensor (tracing / channel pruning)."""
-    taps, self.graph.taps = self.graph.taps, None
-    fuse, self.graph.fuse_conv1x1 = self.graph.fuse_conv1x1, False
-    try:
+    with _plain_call(self.graph, fusion_off=True):
       return self(x)
-    finally:
-      self.graph.taps, self.graph.fuse_conv1x1 = taps, fuse
 
 
 def _run_on_codes(layer, x: 'CodesAct', shape, name: str, requant, residual, launch, launch_q):
@@ -2048,52 +2144,75 @@ class DepthwiseConv2D:
     graph.depthwise_layers.append(self)
 
   def plain(self, x):
-    taps, self.graph.taps = self.graph.taps, None
-    try:
+    with _plain_call(self.graph):
       return self(x)
-    finally:
-      self.graph.taps = taps
 
   def takes_codes(self, shape, is_cuda: bool) -> bool:
     """This layer will multiply the CODES of an input of this NCHW shape: it is packed and no tap takes the call."""
     return self.int8 is not None and self.graph.taps is None and len(shape) == 4 and bool(is_cuda) and shape[1] == self.channels
 
+  def _geometry(self, shape):
+    """TF 'SAME' for an input of NCHW `shape`, as Conv2D._geometry: ((top, bottom), (left, right), (Ho, Wo)).  The kernels of this
+    layer take the FRONT pads."""
+    return (_same_pads(shape[2], self.k, self.stride), _same_pads(shape[3], self.k, self.stride),
+            (-(-shape[2] // self.stride), -(-shape[3] // self.stride)))
+
   def __call__(self, x, want_stats: bool = False, out_bn=None) -> torch.Tensor:
     """`want_stats`: the consumer is a BatchNormAct -- leave the per-channel statistics of the output on the tensor.  `out_bn`: the
     ONLY consumer is that BatchNormAct; on a graph with fixed activation ranges the packed layer applies it in its epilogue
     (pf_dw_i8_fwd_q), any other route ignores the hint."""
-    if self.int8 is not None and self.graph.taps is None:
-      if torch.is_grad_enabled() and (self.kernel.tensor.requires_grad or (x.x if isinstance(x, LazyAct) else x).requires_grad):
+    r = self._route(x, out_bn)
+    name = r[ROUTE_NAME]
+    if name == 'own':                            # the ONE place a DepthwiseConv2D counts itself on its producer (BnSums.add_consumer)
+      bn_sums = getattr(r[ROUTE_X], '_pf_bn', None)
+      if bn_sums is not None:
+        bn_sums.add_consumer(fuses=False)
+    return getattr(self, '_call_' + name)(r, want_stats)
+
+  def _route(self, x, out_bn) -> tuple:
+    """As Conv2D._route, in this order: a packed layer that no tap takes RAISES under gradients, then `int8` for the CodesAct it takes
+    (takes_codes; `out_bn` narrowed to a requantising one); every other input is materialised -- a CodesAct too: the fake-quantised
+    tensor of the apply pass, as without int8 --; `tap`; `own` (pf_depthwise.hip); `library`."""
+    g, w = self.graph, self.kernel.tensor
+    if self.int8 is not None and g.taps is None:
+      if _wants_grad(w, x.x if isinstance(x, LazyAct) else x):
         raise RuntimeError('%s: a depthwise convolution packed for int8 runs in inference only: call it under torch.no_grad() on a '
                            'graph finalised with requires_grad=False' % self.kernel.name)
       if isinstance(x, CodesAct) and self.takes_codes(x.x.shape, x.x.is_cuda):
-        return self._call_int8(x, out_bn if (out_bn is not None and out_bn.requantises()) else None)
-    x = materialize(x)                           # a CodesAct too: the fake-quantised tensor of the apply pass, as without int8
-    if self.graph.taps is not None:
-      return _tapped(self, x)
-    ph = _same_pads(x.shape[2], self.k, self.stride)
-    pw = _same_pads(x.shape[3], self.k, self.stride)
-    w = self.kernel.tensor
-    if (OWN_DEPTHWISE and (x.is_cuda or DEPTHWISE_ANY_DEVICE) and x.dim() == 4 and x.dtype in (torch.float32, torch.bfloat16) and w.dtype == x.dtype
-        and hip.depthwise_supported(self.channels, self.k, self.stride)):
-      Ho, Wo = -(-x.shape[2] // self.stride), -(-x.shape[3] // self.stride)
-      bn_sums = getattr(x, '_pf_bn', None)
-      if bn_sums is not None:
-        bn_sums.n_consumers += 2                    # a consumer that does not fuse the BN-backward sums of its producer
-      if torch.is_grad_enabled() and (x.requires_grad or w.requires_grad):
-        return _apply_with_stats(_Depthwise, x, w, self.stride, ph[0], pw[0], Ho, Wo, want_stats, self.graph, self.kernel)
-      return _run_depthwise(_nhwc(x), w, self.stride, ph[0], pw[0], Ho, Wo, want_stats)
+        ph, pw, out_hw = self._geometry(x.x.shape)
+        return 'int8', x, (ph[0], pw[0]), out_hw, (out_bn if (out_bn is not None and out_bn.requantises()) else None), None
+    x = materialize(x)
+    if g.taps is not None:
+      return 'tap', x, None, None, None, None
+    ph, pw, out_hw = self._geometry(x.shape)
+    if (OWN_DEPTHWISE and (x.is_cuda or DEPTHWISE_ANY_DEVICE) and x.dim() == 4 and x.dtype in (torch.float32, torch.bfloat16)
+        and w.dtype == x.dtype and hip.depthwise_supported(self.channels, self.k, self.stride)):
+      return 'own', x, (ph[0], pw[0]), out_hw, None, None
     x, pad = _symmetric_pads(x, ph, pw)
+    return 'library', x, pad, None, None, None
+
+  def _call_tap(self, r, want_stats):
+    return _tapped(self, r[ROUTE_X])
+
+  def _call_own(self, r, want_stats):
+    _, x, (ph, pw), (Ho, Wo), _, _ = r
+    w = self.kernel.tensor
+    if _wants_grad(w, x):
+      return _apply_with_stats(_Depthwise, x, w, self.stride, ph, pw, Ho, Wo, want_stats, self.graph, self.kernel)
+    return _run_depthwise(_nhwc(x), w, self.stride, ph, pw, Ho, Wo, want_stats)
+
+  def _call_library(self, r, want_stats):
+    _, x, pad, _, _, _ = r
     return F.conv2d(x, self.kernel.tensor, None, stride=self.stride, padding=pad, groups=self.channels)
 
-  def _call_int8(self, x: 'CodesAct', requant=None) -> torch.Tensor:
-    """The packed layer on pf_dw_i8_fwd: the producer's codes times the kernel's codes in integers, scales and offsets in the epilogue
-    (pocketflow_amd/int8.py states the formula), one rounding to the compute dtype.  The BatchNorm behind it makes its own statistics
-    pass (the output carries none).  `requant`: as in Conv2D._call_int8 (pf_dw_i8_fwd_q)."""
+  def _call_int8(self, r, want_stats) -> torch.Tensor:
+    """The packed layer on pf_dw_i8_fwd: the producer's codes (the record's `x`, a CodesAct) times the kernel's codes in integers, scales and
+    offsets in the epilogue (pocketflow_amd/int8.py states the formula), one rounding to the compute dtype.  The BatchNorm behind it
+    makes its own statistics pass (the output carries none).  `requant`: as in Conv2D._call_int8 (pf_dw_i8_fwd_q)."""
+    _, x, (ph, pw), (Ho, Wo), requant, _ = r
     p, bits = self.int8, x.bits
     B, C, H, Wd = x.x.shape
-    Ho, Wo = -(-H // self.stride), -(-Wd // self.stride)
-    dims = (B, H, Wd, C, self.stride, _same_pads(H, self.k, self.stride)[0], _same_pads(Wd, self.k, self.stride)[0], Ho, Wo)
+    dims = (B, H, Wd, C, self.stride, ph, pw, Ho, Wo)
     return _run_on_codes(
         self, x, (B, C, Ho, Wo), 'dw_i8_fwd', requant, None,
         lambda codes, ab, y, res: hip.dw_i8_fwd(codes, p['wcol'], p['scale_beta'], ab, bits, y, *dims),
@@ -2114,27 +2233,28 @@ class Dense:
 
   def __call__(self, x) -> torch.Tensor:
     g = self.graph
+    x = materialize(x)
     if g.taps is not None and g.tap_dense:
-      x = materialize(x)
       y = self.plain(x)
       g.taps[self] = (x, y, None)
       if g.tap_stop is self:
         raise TapStop()
       return y + self.bias.tensor.to(x.dtype)
-    x = materialize(x)
-    if x.dim() == 2 and convg_ok(x, self.kernel.tensor, dense=True):
-      # tf.layers.dense = the 1x1 convolution of a [B][1][1][in] tensor (+ BiasAdd in the epilogue): pf_convg.hip
-      w4 = self.kernel.tensor.view(self.kernel.tensor.shape[0], self.kernel.tensor.shape[1], 1, 1)
-      y = _ConvGeneric.apply(x.contiguous().view(x.shape[0], x.shape[1], 1, 1), w4, self.bias.tensor, 1, (0, 0), (1, 1), self.graph)
-      return y.view(x.shape[0], -1)
-    return F.linear(x, self.kernel.tensor, self.bias.tensor.to(x.dtype))
+    return self._matmul(x, self.bias.tensor)
 
   def plain(self, x: torch.Tensor) -> torch.Tensor:
     """The MatMul op alone (no BiasAdd)."""
-    if x.dim() == 2 and convg_ok(x, self.kernel.tensor, dense=True):
-      w4 = self.kernel.tensor.view(self.kernel.tensor.shape[0], self.kernel.tensor.shape[1], 1, 1)
-      return _ConvGeneric.apply(x.contiguous().view(x.shape[0], x.shape[1], 1, 1), w4, None, 1, (0, 0), (1, 1), self.graph).view(x.shape[0], -1)
-    return F.linear(x, self.kernel.tensor)
+    return self._matmul(x, None)
+
+  def _matmul(self, x, bias):
+    """x W^T [+ bias]: tf.layers.dense = the 1x1 convolution of a [B][1][1][in] tensor (+ BiasAdd in the epilogue) on pf_convg.hip,
+    the library for what that kernel does not take."""
+    w = self.kernel.tensor
+    if x.dim() == 2 and convg_ok(x, w, dense=True):
+      y = _ConvGeneric.apply(x.contiguous().view(x.shape[0], x.shape[1], 1, 1), w.view(w.shape[0], w.shape[1], 1, 1), bias, 1,
+                             (0, 0), (1, 1), self.graph)
+      return y.view(x.shape[0], -1)
+    return F.linear(x, w, bias.to(x.dtype) if bias is not None else None)
 
 
 class Activation:

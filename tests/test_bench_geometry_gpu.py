@@ -6,7 +6,8 @@ statistics-group counts than the 802 816-row launches of the bench).
 One test per layer geometry and pass, with the operands the step gives the kernel (`pocketflow_amd/graph.py`):
   forward        1x1: BN + ReLU + 8-bit fake-quant prologue, [residual], statistics epilogue        (_run_conv1x1)
                  3x3: plain operands, statistics epilogue                                           (_run_conv2d)
-  backward-data  1x1: plain / BN-backward sums of the producer BN in the epilogue / strided row map (_FusedConv1x1.backward)
+  backward-data  1x1: plain / BN-backward sums of the producer BN in the epilogue / strided row map (_FusedConv1x1.backward,
+                                                                                                     _conv1x1_bwd_data_plan)
                  3x3: flipped kernel + BN-backward sums / parity classes for stride 2               (_Conv2dIgemm.backward,
                                                                                                      _bwd_data_weight)
   backward-filter 1x1 with the prologue recomputed on the fly; 3x3 stride 1 / 2                     (the `wrw` launches of those two
