@@ -191,7 +191,13 @@ int pf_ce_combine(const void* dz_hard, const void* dz_soft, const float* g0, con
  * finalize: mean/var -> scale/shift, moving averages (unbiased variance), and -- because
  *   y = act(scale*x+shift) is monotone in x per channel -- the exact whole-tensor min/max of y
  *   from the per-channel min/max of x, written into the activation's min/max slot.
- * pass 2 (pf_bn_act_quant_apply): read x, write q = fake_quant(act(scale*x+shift)).            */
+ * pass 2 (pf_bn_act_quant_apply): read x, write q = fake_quant(act(scale*x+shift)).
+ * pf_bn_vector_ok(C): 1 where the passes of this section, pf_bn_act_quant_codes and pf_bn_act_quant_static
+ *   take their 16-byte route on 16-byte aligned tensors (a lane owns 8 consecutive channels of a row):
+ *   C % 8 == 0 and 8 <= C <= 2048.  Any other C, or a misaligned tensor, runs their scalar loops:
+ *   the same bits out of the element-wise passes, another summation order in the two reductions.
+ *   (pf_bn_act_quant_pool takes its vector form only where C / 8 is a power of two as well.)     */
+int pf_bn_vector_ok(int C);
 int pf_bn_stats(const void* x, int dtype, int64_t rows, int C, float* partial /*[nblk][4][C]*/,
                 int n_blocks, void* stream);
 int pf_bn_finalize(const float* partial, int n_blocks, int64_t rows, int C, const void* x_row0,
@@ -423,7 +429,7 @@ int pf_conv_stem3_wrw(const void* dY, const void* X, void* dW, int dw_dtype, flo
 /* ---- K12 (MobileNet): depthwise 3x3 convolutions, NHWC float32 / bf16, kernel [C][3][3] in the activation dtype ----------
  * replaces DepthwiseConv2dNative / ...BackpropInput / ...BackpropFilter behind slim.separable_conv2d(num_outputs=None)
  * (utils/external/mobilenet_v1.py:264-292).  stride 1 | 2; pad_h / pad_w are TensorFlow's FRONT pads of 'SAME'
- * (floor(total / 2); the rest behind is implied by Ho / Wo).  C % 8 == 0 and 256 % (C / 8) == 0 (pf_depthwise_supported).
+ * (floor(total / 2); the rest behind is implied by Ho / Wo).  C % 8 == 0 and 8 <= C <= 2048 (pf_depthwise_supported).
  * pf_depthwise_fwd: partial (may be NULL) receives the per-channel {sum, sum of squares, min, max} of the stored outputs,
  * [G][4][C] with G = pf_depthwise_groups(B, Ho, Wo, C) -- the statistics of the BatchNorm behind the layer (pf_bn_finalize).
  * pf_depthwise_wrw: slabs = workspace of (pf_depthwise_groups(B, Ho, Wo, C) + 32) * C * 9 floats; fixed-order reduction.  */

@@ -4,15 +4,11 @@
 // stem, residual sums, a float-kernel producer, the network head.
 //
 // One read of x (float32 / bf16), one write: uint8 codes, or the fake-quantised value in float32 / bf16.  The thread -> (row, 8
-// channels) map of k_bn_codes where C % 8 == 0 and C / 8 divides the workgroup, a scalar loop otherwise.  HBM-bound; no LDS, no
+// channels) map of k_bn_codes where C % 8 == 0 and C <= 2048 (pf_bn_vector_ok), a scalar loop otherwise.  HBM-bound; no LDS, no
 // atomics, deterministic.
 #include "pf_act_static.h"
 
-static inline bool static_fast_ok(int C) {     // the thread -> (row, 8 channels) map of k_bn_apply / k_bn_codes
-  if (C % 8) return false;
-  const int G = C / 8;
-  return G <= PF_THREADS && (PF_THREADS % G) == 0;
-}
+static inline bool static_fast_ok(int C) { return pf_vec8_ok(C); }   // the thread -> (row, 8 channels) map of k_bn_apply / k_bn_codes
 
 template <typename T, typename TO, int ACT, bool FAST>
 __global__ __launch_bounds__(PF_THREADS) void k_bn_static(const T* __restrict__ x, TO* __restrict__ out, int64_t rows, int C,
@@ -26,7 +22,7 @@ __global__ __launch_bounds__(PF_THREADS) void k_bn_static(const T* __restrict__ 
 #pragma unroll
     for (int j = 0; j < 8; ++j) { sc[j] = scale_shift[(cg << 3) + j]; sh[j] = scale_shift[C + (cg << 3) + j]; }
 #pragma unroll 2
-    for (int64_t r = (int64_t)blockIdx.x * RPS + rsub; r < rows; r += (int64_t)gridDim.x * RPS) {
+    for (int64_t r = pf_vec8_first_row(rsub, RPS, rows); r < rows; r += (int64_t)gridDim.x * RPS) {
       float v[8];
       const int64_t off = r * C + (cg << 3);
       load8<T>(x + off, v);

@@ -17,14 +17,11 @@
 //   learners/uniform_quantization/utils.py:51-79  activation fake-quant after every Relu / Relu6
 #include "pf_common.h"
 
-// Fast path: C % 8 == 0, G = C/8 <= 256, 256 % G == 0 (C = 8 .. 2048, powers of two): a thread owns
-// one group of 8 consecutive channels and walks rows; a wavefront reads 1 KiB contiguous.
-static inline bool bn_fast_ok(int C) {
-  if (C % 8) return false;
-  const int G = C / 8;
-  if (G < 8) return (8 % G) == 0;                        // C = 8, 16, 32: a single slab
-  return (C % 64) == 0 && G <= 256 && (256 % G) == 0;    // streaming kernels keep the (256 % G) map
-}
+// Fast path: C % 8 == 0, G = C/8 <= 256 (C = 8 .. 2048): a thread owns one group of 8 consecutive
+// channels and walks rows; a wavefront reads 1 KiB contiguous.  Where G does not divide the
+// workgroup, the left-over lanes idle (pf_common.h); for the powers of two nothing changed.
+static inline bool bn_fast_ok(int C) { return pf_vec8_ok(C); }
+extern "C" int pf_bn_vector_ok(int C) { return bn_fast_ok(C) ? 1 : 0; }
 
 // The storage type of an extern "C" entry: f is called with a null T* (T = float / bf16_t) and returns the entry's status.
 template <typename F> static inline int bn_with_dtype(int dtype, F&& f) {
@@ -37,11 +34,19 @@ template <typename F> static inline int bn_with_dtype(int dtype, F&& f) {
 // forward pass 1
 // ---------------------------------------------------------------------------------------------
 // 2-D decomposition: a 1024-thread workgroup (16 wavefronts) owns a SLAB of up to 64 channels
-// (CG = min(C/8, 8) groups of 8 channels, 16 B per lane) and one of `nsplit` interleaved row ranges;
+// (CG <= 8 groups of 8 channels, 16 B per lane) and one of `nsplit` interleaved row ranges;
 // 1024/CG row-lanes walk the rows.  Per-workgroup partials are only 4 x 64 floats, so the partial
 // buffer [nsplit][4][C] stays ~1000x smaller than the tensor and the finalize pass is a few us.
+// CG is a power of two (the butterfly of bn_wave_reduce8): G = C/8 itself for 1, 2, 4, the next power of two for 3, 5, 6, 7,
+// and 8 beyond, with nslab = ceil(G / CG) slabs.  The lanes of a group >= G (in the last slab only, and only where CG does not
+// divide G) load nothing -- no pivot, no row -- carry the identity of every statistic through the reductions, and no thread
+// writes a channel >= C.
 #define BN_BIG 1024
-__host__ __device__ __forceinline__ int bn_cg_of(int C) { return (C >> 3) < 8 ? (C >> 3) : 8; }
+__host__ __device__ __forceinline__ int bn_cg_of(int C) {
+  const int G = C >> 3;
+  return G >= 8 ? 8 : (G <= 2 ? G : (G <= 4 ? 4 : 8));
+}
+static inline int bn_nslab_of(int C) { return ((C >> 3) + bn_cg_of(C) - 1) / bn_cg_of(C); }
 
 // KIND per statistic: 0 = sum, 1 = min, 2 = max
 template <int KIND> __device__ __forceinline__ float bn_comb(float a, float b) {
@@ -82,22 +87,25 @@ __global__ __launch_bounds__(BN_BIG) void k_bn_stats_fast(const T* __restrict__ 
   const int slab = blockIdx.x % nslab, split = blockIdx.x / nslab;
   const int cg = threadIdx.x % CG, rl = threadIdx.x / CG;
   const int c0 = slab * slabC + cg * 8;
+  const bool live = c0 < C;                       // false: a group >= G of the guarded last slab
   float piv[8];
-  load8<T>(x + c0, piv);                          // pivot = row 0 (shifted sums: no cancellation)
   float s[8], ss[8], mn[8], mx[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) { s[j] = 0.f; ss[j] = 0.f; mn[j] = INFINITY; mx[j] = -INFINITY; }
+  if (live) {
+    load8<T>(x + c0, piv);                        // pivot = row 0 (shifted sums: no cancellation)
 #pragma unroll 2
-  for (int64_t r = (int64_t)split * RL + rl; r < rows; r += (int64_t)nsplit * RL) {
-    float v[8];
-    load8<T>(x + r * C + c0, v);
+    for (int64_t r = (int64_t)split * RL + rl; r < rows; r += (int64_t)nsplit * RL) {
+      float v[8];
+      load8<T>(x + r * C + c0, v);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float d = v[j] - piv[j];
-      s[j] += d;
-      ss[j] = fmaf(d, d, ss[j]);
-      mn[j] = pf_acc_min(mn[j], v[j]);
-      mx[j] = pf_acc_max(mx[j], v[j]);
+      for (int j = 0; j < 8; ++j) {
+        const float d = v[j] - piv[j];
+        s[j] += d;
+        ss[j] = fmaf(d, d, ss[j]);
+        mn[j] = pf_acc_min(mn[j], v[j]);
+        mx[j] = pf_acc_max(mx[j], v[j]);
+      }
     }
   }
   bn_wave_reduce8<0>(s, CG); bn_wave_reduce8<0>(ss, CG); bn_wave_reduce8<1>(mn, CG); bn_wave_reduce8<2>(mx, CG);
@@ -105,10 +113,11 @@ __global__ __launch_bounds__(BN_BIG) void k_bn_stats_fast(const T* __restrict__ 
   bn_lds_put<1>(mn, 2, 4, CG, lds); bn_lds_put<2>(mx, 3, 4, CG, lds);
   __syncthreads();
   float* out = partial + (int64_t)split * 4 * C + slab * slabC;
-  bn_lds_finish<0>(0, 4, slabC, lds, out);
-  bn_lds_finish<0>(1, 4, slabC, lds, out + C);
-  bn_lds_finish<1>(2, 4, slabC, lds, out + 2 * C);
-  bn_lds_finish<2>(3, 4, slabC, lds, out + 3 * C);
+  const int nC = min(slabC, C - slab * slabC);    // channels of this slab that exist
+  bn_lds_finish<0>(0, 4, nC, lds, out);
+  bn_lds_finish<0>(1, 4, nC, lds, out + C);
+  bn_lds_finish<1>(2, 4, nC, lds, out + 2 * C);
+  bn_lds_finish<2>(3, 4, nC, lds, out + 3 * C);
 }
 
 template <typename T>
@@ -136,7 +145,7 @@ extern "C" int pf_bn_stats(const void* x, int dtype, int64_t rows, int C, float*
   return bn_with_dtype(dtype, [&](auto* t) {
     using T = std::remove_pointer_t<decltype(t)>;
     if (bn_fast_ok(C) && pf_aligned16(x)) {
-      const int nslab = C / (bn_cg_of(C) * 8);
+      const int nslab = bn_nslab_of(C);
       k_bn_stats_fast<T><<<nslab * n_blocks, BN_BIG, 0, st>>>((const T*)x, rows, C, partial, nslab, n_blocks);
     } else {
       dim3 grid((C + PF_THREADS - 1) / PF_THREADS, n_blocks);
@@ -306,7 +315,7 @@ __global__ __launch_bounds__(PF_THREADS) void k_bn_apply(const T* __restrict__ x
 #pragma unroll
     for (int j = 0; j < 8; ++j) { sc[j] = scale_shift[(cg << 3) + j]; sh[j] = scale_shift[C + (cg << 3) + j]; }
 #pragma unroll 2
-    for (int64_t r = (int64_t)blockIdx.x * RPS + rsub; r < rows; r += (int64_t)gridDim.x * RPS) {
+    for (int64_t r = pf_vec8_first_row(rsub, RPS, rows); r < rows; r += (int64_t)gridDim.x * RPS) {
       float v[8];
       const int64_t off = r * C + (cg << 3);
       load8<T>(x + off, v);
@@ -408,10 +417,15 @@ __global__ __launch_bounds__(PF_THREADS) void k_bn_apply_pool(const T* __restric
   }
 }
 
+// The pooled pass keeps the channel counts it took before the vector map was opened to every C % 8 == 0 (G = C / 8 a power of two):
+// its FAST form has B * G threads walk HW pixels one after the other, and at 256 x 49 x 768 (bf16) that lost to the scalar form's
+// eight times as many threads, 45.0 against 21.3 us (profiles/odd_channel_layers.txt).
+static inline bool bn_pool_fast_ok(int C) { return bn_fast_ok(C) && ((C >> 3) & ((C >> 3) - 1)) == 0; }
+
 template <typename T>
 static int launch_bn_apply_pool(const T* x, T* pooled, int64_t rows, int C, int HW, const float* ss, int act,
                                 const uint32_t* slot, float k, int quantize, hipStream_t st) {
-  const bool fast = bn_fast_ok(C) && pf_aligned16(x) && pf_aligned16(pooled);
+  const bool fast = bn_pool_fast_ok(C) && pf_aligned16(x) && pf_aligned16(pooled);
   const int64_t B = rows / HW;
   const int64_t items = fast ? B * (C / 8) : B * C;
   const int64_t grid = (items + PF_THREADS - 1) / PF_THREADS;
@@ -479,16 +493,17 @@ __global__ __launch_bounds__(BN_BIG) void k_bn_bwd_stats_fast(const T* __restric
   const int slab = blockIdx.x % nslab, split = blockIdx.x / nslab;
   const int cg = threadIdx.x % CG, rl = threadIdx.x / CG;
   const int c0 = slab * slabC + cg * 8;
+  const bool live = c0 < C;                       // false: a group >= G of the guarded last slab
   float sc[8], sh[8], mu[8], is[8], s1[8], s2[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    const int c = c0 + j;
+    const int c = live ? c0 + j : j;              // an idle lane reads channel j's constants and never uses them
     sc[j] = scale_shift[c]; sh[j] = scale_shift[C + c];
     mu[j] = mean_invstd[c]; is[j] = mean_invstd[C + c];
     s1[j] = 0.f; s2[j] = 0.f;
   }
 #pragma unroll 2
-  for (int64_t r = (int64_t)split * RL + rl; r < rows; r += (int64_t)nsplit * RL) {
+  for (int64_t r = live ? (int64_t)split * RL + rl : rows; r < rows; r += (int64_t)nsplit * RL) {
     float g[8], v[8];
     const int64_t off = r * C + c0;
     if (POOLED) pooled_dq8<T>(dq, r, C, c0, HW, g);
@@ -505,8 +520,9 @@ __global__ __launch_bounds__(BN_BIG) void k_bn_bwd_stats_fast(const T* __restric
   bn_lds_put<0>(s1, 0, 2, CG, lds); bn_lds_put<0>(s2, 1, 2, CG, lds);
   __syncthreads();
   float* out = partial + (int64_t)split * 2 * C + slab * slabC;
-  bn_lds_finish<0>(0, 2, slabC, lds, out);
-  bn_lds_finish<0>(1, 2, slabC, lds, out + C);
+  const int nC = min(slabC, C - slab * slabC);    // channels of this slab that exist
+  bn_lds_finish<0>(0, 2, nC, lds, out);
+  bn_lds_finish<0>(1, 2, nC, lds, out + C);
 }
 
 template <typename T, int ACT, bool POOLED>
@@ -535,7 +551,7 @@ template <typename T>
 static int launch_bn_bwd_stats(const T* dq, const T* x, int64_t rows, int C, int HW, const float* ss,
                                const float* mi, int act, float* partial, int n_blocks, hipStream_t st) {
   const bool fast = bn_fast_ok(C) && pf_aligned16(x) && pf_aligned16(dq);
-  const int nslab = fast ? C / (bn_cg_of(C) * 8) : 1;
+  const int nslab = fast ? bn_nslab_of(C) : 1;
   dim3 ggrid((C + PF_THREADS - 1) / PF_THREADS, n_blocks);
   pf_with_act(act, [&](auto A) {
     pf_with_bool(HW > 0, [&](auto P) {
@@ -630,7 +646,7 @@ __global__ __launch_bounds__(PF_THREADS) void k_bn_bwd_apply(const T* __restrict
       a[j] = dbeta[c] * inv_n; b[j] = dgamma[c] * inv_n;
     }
 #pragma unroll 2
-    for (int64_t r = (int64_t)blockIdx.x * RPS + rsub; r < rows; r += (int64_t)gridDim.x * RPS) {
+    for (int64_t r = pf_vec8_first_row(rsub, RPS, rows); r < rows; r += (int64_t)gridDim.x * RPS) {
       float g[8], v[8];
       const int64_t off = r * C + (cg << 3);
       if (POOLED) pooled_dq8<T>(dq, r, C, cg << 3, HW, g);

@@ -227,3 +227,12 @@ static inline int pf_grid_for(int64_t n, int per_block) {
   if (g > PF_MAX_GRID) g = PF_MAX_GRID;
   return (int)g;
 }
+
+// ---- the (row, 8-channel) vector map of the BN / quantiser passes (pf_bn_vector_ok) ------------
+// A lane owns one group of 8 consecutive channels of one row (16 bytes of bf16); a 256-thread workgroup covers RPS = 256 / G rows
+// per trip, G = C / 8, rounded down.  Where G does not divide 256 the 256 - RPS * G left-over lanes (rsub == RPS) idle: they start
+// behind the last row.
+static inline bool pf_vec8_ok(int C) { return C >= 8 && (C % 8) == 0 && C <= 2048; }
+__device__ __forceinline__ int64_t pf_vec8_first_row(int rsub, int RPS, int64_t rows) {
+  return rsub < RPS ? (int64_t)blockIdx.x * RPS + rsub : rows;
+}

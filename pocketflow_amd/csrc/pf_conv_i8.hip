@@ -26,11 +26,7 @@ __device__ __forceinline__ uint32_t uq_code(float t, float alpha, float beta, fl
   return (uint32_t)fminf(fmaxf(rintf(xn * k), 0.0f), k);
 }
 
-static inline bool codes_fast_ok(int C) {     // the thread -> (row, 8 channels) map of k_bn_apply
-  if (C % 8) return false;
-  const int G = C / 8;
-  return G <= PF_THREADS && (PF_THREADS % G) == 0;
-}
+static inline bool codes_fast_ok(int C) { return pf_vec8_ok(C); }   // the thread -> (row, 8 channels) map of k_bn_apply
 
 template <typename T, int ACT, bool FAST>
 __global__ __launch_bounds__(PF_THREADS) void k_bn_codes(const T* __restrict__ x, uint8_t* __restrict__ codes, int64_t rows, int C,
@@ -47,7 +43,7 @@ __global__ __launch_bounds__(PF_THREADS) void k_bn_codes(const T* __restrict__ x
 #pragma unroll
     for (int j = 0; j < 8; ++j) { sc[j] = scale_shift[(cg << 3) + j]; sh[j] = scale_shift[C + (cg << 3) + j]; }
 #pragma unroll 2
-    for (int64_t r = (int64_t)blockIdx.x * RPS + rsub; r < rows; r += (int64_t)gridDim.x * RPS) {
+    for (int64_t r = pf_vec8_first_row(rsub, RPS, rows); r < rows; r += (int64_t)gridDim.x * RPS) {
       float v[8];
       const int64_t off = r * C + (cg << 3);
       load8<T>(x + off, v);

@@ -19,6 +19,12 @@
 // in partial[G][4][C], reduced in a fixed order: one pass over the tensor less per layer, deterministic.  Backward-filter
 // keeps 9 x 8 float32 accumulators per lane, combines the lanes of a workgroup through LDS and writes one [C][9] slab per
 // workgroup; a second launch adds the slabs in a fixed order (bit-reproducible, like pf_wrw_reduce).
+//
+// Channel counts: any C % 8 == 0, 8 <= C <= 2048.  A workgroup covers SPB = 256 / (C / 8) strips (pixels in k_dw_bwd_data) per pass,
+// rounded down.  Where C / 8 divides 256 every lane has a strip (GEN = false: the kernels as they were for the powers of two).
+// Otherwise (GEN = true; 24, 48, 96 ... channels) the 256 - SPB * (C / 8) left-over lanes have sl == SPB: they take no strip -- it
+// would be the first strip of the NEXT workgroup, computed and counted in the statistics twice --, write nothing to LDS, whose
+// reductions read sl < SPB only, and reach every barrier.  255 of 256 lanes work at C = 24, 252 at 96, 240 at 384, 192 at 768.
 #include "pf_common.h"
 
 #define DW_T 256
@@ -85,11 +91,12 @@ template <> __device__ __forceinline__ float dw_round<float>(float v) { return v
 template <> __device__ __forceinline__ float dw_round<bf16_t>(float v) { return bf16_to_f32(f32_to_bf16(v)); }
 
 // forward (and stride-1 backward-data, which is the same sum over the flipped kernel with front pads k-1-p)
-template <typename T, int ST>
+template <typename T, int ST, bool GEN>
 __global__ __launch_bounds__(DW_T) void k_dw_fwd(const DwArgs a) {
   __shared__ float red[4 * DW_T * 8];
   const int C8 = a.C >> 3, SPB = DW_T / C8;
   const int cg = threadIdx.x % C8, sl = threadIdx.x / C8;
+  const bool idle = GEN && sl >= SPB;
   const dw_rsrc_t rsx = DW_MAKE_RSRC(a.x, a.x_bytes);
   const T* __restrict__ w = (const T*)a.w;
   T* __restrict__ y = (T*)a.y;
@@ -102,7 +109,7 @@ __global__ __launch_bounds__(DW_T) void k_dw_fwd(const DwArgs a) {
 #pragma unroll
   for (int j = 0; j < 8; ++j) { st_s[j] = 0.f; st_q[j] = 0.f; st_mn[j] = INFINITY; st_mx[j] = -INFINITY; }
   constexpr int NV = (DW_PW - 1) * ST + 3;
-  for (int64_t strip = (int64_t)blockIdx.x * SPB + sl; strip < a.total; strip += (int64_t)gridDim.x * SPB) {
+  for (int64_t strip = idle ? a.total : (int64_t)blockIdx.x * SPB + sl; strip < a.total; strip += (int64_t)gridDim.x * SPB) {
     const int sw = (int)(strip % a.strips_w);
     const int64_t t = strip / a.strips_w;
     const int ho = (int)(t % a.Ho), b = (int)(t / a.Ho);
@@ -156,12 +163,14 @@ __global__ __launch_bounds__(DW_T) void k_dw_fwd(const DwArgs a) {
   }
   if (a.partial != nullptr) {
     // lanes with equal channel group (sl = 0 .. SPB-1) -> one row of partial, fixed order
+    if (!idle) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      red[(0 * SPB + sl) * a.C + cg * 8 + j] = st_s[j];
-      red[(1 * SPB + sl) * a.C + cg * 8 + j] = st_q[j];
-      red[(2 * SPB + sl) * a.C + cg * 8 + j] = st_mn[j];
-      red[(3 * SPB + sl) * a.C + cg * 8 + j] = st_mx[j];
+      for (int j = 0; j < 8; ++j) {
+        red[(0 * SPB + sl) * a.C + cg * 8 + j] = st_s[j];
+        red[(1 * SPB + sl) * a.C + cg * 8 + j] = st_q[j];
+        red[(2 * SPB + sl) * a.C + cg * 8 + j] = st_mn[j];
+        red[(3 * SPB + sl) * a.C + cg * 8 + j] = st_mx[j];
+      }
     }
     __syncthreads();
     for (int i = threadIdx.x; i < 4 * a.C; i += DW_T) {
@@ -177,10 +186,11 @@ __global__ __launch_bounds__(DW_T) void k_dw_fwd(const DwArgs a) {
 }
 
 // backward-data for any stride (gather form): one lane = 8 channels of one INPUT pixel
-template <typename T>
+template <typename T, bool GEN>
 __global__ __launch_bounds__(DW_T) void k_dw_bwd_data(const DwArgs a) {
   const int C8 = a.C >> 3, SPB = DW_T / C8;
   const int cg = threadIdx.x % C8, sl = threadIdx.x / C8;
+  const bool idle = GEN && sl >= SPB;
   const dw_rsrc_t rsy = DW_MAKE_RSRC(a.x, a.x_bytes);
   const T* __restrict__ w = (const T*)a.w;
   T* __restrict__ dx = (T*)a.y;
@@ -190,7 +200,7 @@ __global__ __launch_bounds__(DW_T) void k_dw_bwd_data(const DwArgs a) {
 #pragma unroll
     for (int t = 0; t < 9; ++t) wr[t][j] = load_one<T>(w + (int64_t)(cg * 8 + j) * 9 + t);
   const int64_t npix = (int64_t)a.B * a.H * a.W;
-  for (int64_t pix = (int64_t)blockIdx.x * SPB + sl; pix < npix; pix += (int64_t)gridDim.x * SPB) {
+  for (int64_t pix = idle ? npix : (int64_t)blockIdx.x * SPB + sl; pix < npix; pix += (int64_t)gridDim.x * SPB) {
     const int wi = (int)(pix % a.W);
     const int64_t t = pix / a.W;
     const int hi = (int)(t % a.H), b = (int)(t / a.H);
@@ -224,11 +234,12 @@ __global__ __launch_bounds__(DW_T) void k_dw_bwd_data(const DwArgs a) {
 }
 
 // backward-filter: strips of 4 output pixels as in the forward kernel; slab [G][C][9]
-template <typename T, int ST>
+template <typename T, int ST, bool GEN>
 __global__ __launch_bounds__(DW_T) void k_dw_wrw(const DwArgs a) {
   __shared__ float red[DW_T * 8];                       // one tap at a time: [SPB][C]
   const int C8 = a.C >> 3, SPB = DW_T / C8;
   const int cg = threadIdx.x % C8, sl = threadIdx.x / C8;
+  const bool idle = GEN && sl >= SPB;
   const dw_rsrc_t rsx = DW_MAKE_RSRC(a.x, a.x_bytes);
   const dw_rsrc_t rsy = DW_MAKE_RSRC(a.dy, a.dy_bytes);
   float acc[9][8];
@@ -237,7 +248,7 @@ __global__ __launch_bounds__(DW_T) void k_dw_wrw(const DwArgs a) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[t][j] = 0.f;
   constexpr int NV = (DW_PW - 1) * ST + 3;
-  for (int64_t strip = (int64_t)blockIdx.x * SPB + sl; strip < a.total; strip += (int64_t)gridDim.x * SPB) {
+  for (int64_t strip = idle ? a.total : (int64_t)blockIdx.x * SPB + sl; strip < a.total; strip += (int64_t)gridDim.x * SPB) {
     const int sw = (int)(strip % a.strips_w);
     const int64_t t = strip / a.strips_w;
     const int ho = (int)(t % a.Ho), b = (int)(t / a.Ho);
@@ -279,7 +290,8 @@ __global__ __launch_bounds__(DW_T) void k_dw_wrw(const DwArgs a) {
 #pragma unroll
   for (int t = 0; t < 9; ++t) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) red[sl * a.C + cg * 8 + j] = acc[t][j];
+    for (int j = 0; j < 8; ++j)
+      if (!idle) red[sl * a.C + cg * 8 + j] = acc[t][j];
     __syncthreads();
     for (int c = threadIdx.x; c < a.C; c += DW_T) {
       float v = red[c];
@@ -291,7 +303,9 @@ __global__ __launch_bounds__(DW_T) void k_dw_wrw(const DwArgs a) {
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
-static bool dw_shape_ok(int C, int k) { return k == 3 && C >= 8 && (C % 8) == 0 && C <= 2048 && (DW_T % (C / 8)) == 0; }
+static bool dw_shape_ok(int C, int k) { return k == 3 && C >= 8 && (C % 8) == 0 && C <= 2048; }
+// C / 8 does not divide the workgroup: the GEN instantiations, whose left-over lanes idle
+static bool dw_general(int C) { return (DW_T % (C / 8)) != 0; }
 
 extern "C" int pf_depthwise_supported(int C, int k, int stride) { return (dw_shape_ok(C, k) && (stride == 1 || stride == 2)) ? 1 : 0; }
 
@@ -341,8 +355,11 @@ extern "C" int pf_depthwise_fwd(const void* X, const void* W, void* Y, int dtype
   hipStream_t st = (hipStream_t)stream;
 #define PF_DW(TT)                                                                     \
   do {                                                                                \
-    if (stride == 1) k_dw_fwd<TT, 1><<<grid, DW_T, 0, st>>>(a);                       \
-    else k_dw_fwd<TT, 2><<<grid, DW_T, 0, st>>>(a);                                   \
+    if (dw_general(C)) {                                                              \
+      if (stride == 1) k_dw_fwd<TT, 1, true><<<grid, DW_T, 0, st>>>(a);               \
+      else k_dw_fwd<TT, 2, true><<<grid, DW_T, 0, st>>>(a);                           \
+    } else if (stride == 1) k_dw_fwd<TT, 1, false><<<grid, DW_T, 0, st>>>(a);         \
+    else k_dw_fwd<TT, 2, false><<<grid, DW_T, 0, st>>>(a);                            \
   } while (0)
   if (dtype == PF_F32) PF_DW(float);
   else if (dtype == PF_BF16) PF_DW(bf16_t);
@@ -366,8 +383,9 @@ extern "C" int pf_depthwise_bwd_data(const void* dY, const void* W, void* dX, in
     a.x = dY; a.w = W; a.y = dX; a.dy = nullptr; a.partial = nullptr; a.flip = 1;
     if (!dw_set_bytes(a, dtype, (int64_t)B * Ho * Wo * C, 0)) return (int)hipErrorInvalidValue;
     const int grid1 = dw_groups(a.total, C);
-    if (dtype == PF_F32) k_dw_fwd<float, 1><<<grid1, DW_T, 0, st>>>(a);
-    else if (dtype == PF_BF16) k_dw_fwd<bf16_t, 1><<<grid1, DW_T, 0, st>>>(a);
+    const bool gen1 = dw_general(C);
+    if (dtype == PF_F32) { if (gen1) k_dw_fwd<float, 1, true><<<grid1, DW_T, 0, st>>>(a); else k_dw_fwd<float, 1, false><<<grid1, DW_T, 0, st>>>(a); }
+    else if (dtype == PF_BF16) { if (gen1) k_dw_fwd<bf16_t, 1, true><<<grid1, DW_T, 0, st>>>(a); else k_dw_fwd<bf16_t, 1, false><<<grid1, DW_T, 0, st>>>(a); }
     else return (int)hipErrorInvalidValue;
     PF_LAUNCH_CHECK();
     return 0;
@@ -378,8 +396,9 @@ extern "C" int pf_depthwise_bwd_data(const void* dY, const void* W, void* dX, in
   if (!dw_set_bytes(a, dtype, (int64_t)B * Ho * Wo * C, 0)) return (int)hipErrorInvalidValue;
   const int64_t npix = (int64_t)B * H * Wd;
   const int grid = dw_groups(npix, C);
-  if (dtype == PF_F32) k_dw_bwd_data<float><<<grid, DW_T, 0, st>>>(a);
-  else if (dtype == PF_BF16) k_dw_bwd_data<bf16_t><<<grid, DW_T, 0, st>>>(a);
+  const bool gen = dw_general(C);
+  if (dtype == PF_F32) { if (gen) k_dw_bwd_data<float, true><<<grid, DW_T, 0, st>>>(a); else k_dw_bwd_data<float, false><<<grid, DW_T, 0, st>>>(a); }
+  else if (dtype == PF_BF16) { if (gen) k_dw_bwd_data<bf16_t, true><<<grid, DW_T, 0, st>>>(a); else k_dw_bwd_data<bf16_t, false><<<grid, DW_T, 0, st>>>(a); }
   else return (int)hipErrorInvalidValue;
   PF_LAUNCH_CHECK();
   return 0;
@@ -402,8 +421,11 @@ extern "C" int pf_depthwise_wrw(const void* dY, const void* X, void* dW, int dty
   hipStream_t st = (hipStream_t)stream;
 #define PF_DWW(TT)                                                                    \
   do {                                                                                \
-    if (stride == 1) k_dw_wrw<TT, 1><<<grid, DW_T, 0, st>>>(a);                       \
-    else k_dw_wrw<TT, 2><<<grid, DW_T, 0, st>>>(a);                                   \
+    if (dw_general(C)) {                                                              \
+      if (stride == 1) k_dw_wrw<TT, 1, true><<<grid, DW_T, 0, st>>>(a);               \
+      else k_dw_wrw<TT, 2, true><<<grid, DW_T, 0, st>>>(a);                           \
+    } else if (stride == 1) k_dw_wrw<TT, 1, false><<<grid, DW_T, 0, st>>>(a);         \
+    else k_dw_wrw<TT, 2, false><<<grid, DW_T, 0, st>>>(a);                            \
   } while (0)
   if (dtype == PF_F32) PF_DWW(float);
   else if (dtype == PF_BF16) PF_DWW(bf16_t);

@@ -40,6 +40,7 @@ import torch.nn.functional as F
 
 from pocketflow_amd import hip
 from pocketflow_amd.hip import check_gather
+from pocketflow_amd.hip import bn_vector_ok as _bn_vector_ok   # bound here: the tests' stand-ins for `hip` emulate launches only
 from pocketflow_amd.plan import WeightDesc
 from pocketflow_amd.profiling import region
 
@@ -599,21 +600,17 @@ def _nhwc(x: torch.Tensor) -> torch.Tensor:
 
 
 def _bn_fast_ok(C: int) -> bool:
-  """Mirror of bn_fast_ok() in csrc/pf_bn.hip."""
-  if C % 8:
-    return False
-  G = C // 8
-  if G < 8:
-    return 8 % G == 0
-  return C % 64 == 0 and G <= 256 and 256 % G == 0
+  """bn_fast_ok() of csrc/pf_bn.hip, asked of the library (pf_bn_vector_ok: a host query, no device work)."""
+  return _bn_vector_ok(C)
 
 
 def _bn_blocks(rows: int, C: int) -> int:
   """Number of row splits of the BN statistics passes (= entries per channel the finalize kernel
   reduces).  Fast path: 1024-thread workgroups over (channel slab x row split); ~256 workgroups."""
   if _bn_fast_ok(C):
-    cg = min(C // 8, 8)
-    nslab = C // (cg * 8)
+    G = C // 8
+    cg = 8 if G >= 8 else (G if G <= 2 else (4 if G <= 4 else 8))   # bn_cg_of(): a power of two, the last slab guarded
+    nslab = -(-G // cg)
     row_lanes = 1024 // cg
     return int(max(1, min(256 // nslab, rows // (row_lanes * 2))))
   return int(min(256, max(1, rows // 64)))

@@ -60,6 +60,7 @@ SYMBOLS = [
     'pf_dw_i8_supported', 'pf_dw_i8_fwd',
     'pf_bn_act_quant_static', 'pf_conv_i8_fwd_q', 'pf_dw_i8_fwd_q',
     'pf_bn_add_act_groups', 'pf_bn_add_act_fwd', 'pf_bn_add_act_bwd_gate', 'pf_bn_add_act_bwd_gate_add',
+    'pf_bn_vector_ok',
 ]
 
 
@@ -432,6 +433,11 @@ def ce_combine(dz_hard, dz_soft, g0, g1, dz) -> None:
 # ------------------------------------------------------------------------------------------------
 # fused BN + act + fake-quant
 # ------------------------------------------------------------------------------------------------
+
+def bn_vector_ok(C: int) -> bool:
+  """Whether the BN / quantiser passes take their 16-byte (row, 8-channel) route at C channels on aligned tensors."""
+  return bool(_lib.pf_bn_vector_ok(c_int(C)))
+
 
 def bn_stats(x, rows: int, C: int, partial, n_blocks: int) -> None:
   _check(_lib.pf_bn_stats(_ptr(x), c_int(dtype_code(x)), c_int64(rows), c_int(C), _ptr(partial), c_int(n_blocks),
