@@ -321,6 +321,22 @@ int pf_conv1x1_fwd_affine(const void* X, const void* W, void* Y, const float* sc
 int pf_conv1x1_bwd_data_bnstats(const void* dY, const void* Wt, void* dQ, const void* bn_x,
                                 const float* bn_scale_shift, const float* bn_mean_invstd, int bn_act,
                                 float* partial, int M, int N, int K, void* stream);
+/* The same backward-data for a consumer that needs only the BN backward of dQ (an identity bottleneck block: bn1's apply pass is
+ * dQ's one reader), as a PAIR of launches that never stores dQ (bf16 only):
+ *   pf_conv1x1_bwd_data_bnsums   the launch above without its store: the same partial[G][2][K], bit for bit;
+ *   (pf_bn_bwd_finalize on the partials: dgamma, dbeta)
+ *   pf_conv1x1_bwd_data_bnapply  the product again, with pf_bn_bwd_apply_add as its row pass on the tile rounded to bf16 as it would
+ *                                have been stored: dx[M][K] = bf16( scale * (dy - dbeta/M - xhat * dgamma/M) [+ addend] ), the bits of
+ *                                the three-launch route.  act: PF_ACT_RELU / PF_ACT_RELU6.  addend ([M][K], the shortcut's gradient)
+ *                                may be NULL: then nothing is added.
+ * pf_conv1x1_bwd_apply_plan(M, N, K): non-zero where the pair is offered -- the plan of the launch above names the resident kernel
+ * in a compiled slice width, and K >= 2 * N.  Elsewhere both entries return hipErrorInvalidValue; the three launches remain.   */
+int pf_conv1x1_bwd_apply_plan(int M, int N, int K);
+int pf_conv1x1_bwd_data_bnsums(const void* dY, const void* Wt, const void* bn_x, const float* bn_scale_shift,
+                               const float* bn_mean_invstd, int bn_act, float* partial, int M, int N, int K, void* stream);
+int pf_conv1x1_bwd_data_bnapply(const void* dY, const void* Wt, const void* x, const float* scale_shift,
+                                const float* mean_invstd, int act, const float* dgamma, const float* dbeta,
+                                const void* addend, void* dx, int M, int N, int K, void* stream);
 /* backward-data of a stride-1 1x1 convolution that JOINS the gradient of a second consumer of Q (a projection block: conv1 and the
  * shortcut convolution both read bn1's output):  dQ[m][k] = bf16( sum_n dY[m][n] * W[n][k] + R(m)[k] ), one rounding.
  *   r_stride == 1: R is dense, [M][K], R(m) = R[m] (the other arguments of the geometry are ignored).

@@ -653,11 +653,7 @@ __global__ __launch_bounds__(PF_THREADS) void k_bn_bwd_apply(const T* __restrict
       else load8<T>(dq + off, g);
       load8<T>(x + off, v);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float dy = g[j] * act_mask<ACT>(fmaf(sc[j], v[j], sh[j]));
-        const float xh = (v[j] - mu[j]) * is[j];
-        g[j] = sc[j] * (dy - a[j] - xh * b[j]);
-      }
+      for (int j = 0; j < 8; ++j) g[j] = bn_bwd_dx<ACT>(g[j], v[j], sc[j], sh[j], mu[j], is[j], a[j], b[j]);
       if (!POOLED && addend != nullptr) {
         float ad[8];
         load8<T>(addend + off, ad);

@@ -158,6 +158,16 @@ template <int ACT> __device__ __forceinline__ float act_mask(float u) {
   return 1.0f;
 }
 
+// One element of the BN-backward apply pass: dx = scale * (dy - dbeta/n - xhat * dgamma/n), dy = g * act'(scale * v + shift),
+// a = dbeta / n, b = dgamma / n.  ONE definition for k_bn_bwd_apply (pf_bn.hip) and the 1x1 backward-data kernel that recomputes g
+// in its row pass (pf_conv_stream.hip), so that both give the same bits for the same g.
+template <int ACT>
+__device__ __forceinline__ float bn_bwd_dx(float g, float v, float sc, float sh, float mu, float is, float a, float b) {
+  const float dy = g * act_mask<ACT>(fmaf(sc, v, sh));
+  const float xh = (v - mu) * is;
+  return sc * (dy - a - xh * b);
+}
+
 // ---- the fake-quant point function (uq utils.py:182-187, 245): exactly five roundings --------
 __device__ __forceinline__ float uq_point(float t, float alpha, float beta, float k) {
   float xn = (t - beta) / alpha;

@@ -305,6 +305,8 @@ static int conv_bn_of(int N) {
 // the other kernels' parts of the plan, and their launchers (a: filled here, p: conv1x1_plan's answer)
 bool pf_conv_stream_plan(const Conv1x1Req& q, Conv1x1Plan* p);     // pf_conv_stream.hip: the barrier-free variant for kernels that fit the LDS
 int pf_conv_stream_launch(const ConvArgs& a, const Conv1x1Plan& p, hipStream_t st);
+bool pf_conv_stream_bn_pair_ok(const Conv1x1Plan& p);              // the pair without dQ (BV_SUMS / BV_APPLY): variants compiled for this plan?
+int pf_conv_stream_launch_bn_pair(const ConvArgs& a, const Conv1x1Plan& p, int variant, int act, const BnApplyArgs& ap, hipStream_t st);
 bool pf_igemm_conv1x1_plan(const Conv1x1Req& q, Conv1x1Plan* p);   // pf_igemm.hip: direct-to-LDS staged GEMM
 int pf_igemm_conv1x1(const ConvArgs& a, const Conv1x1Plan& p, hipStream_t st);
 
@@ -495,6 +497,54 @@ extern "C" int pf_conv1x1_bwd_data_bnstats(const void* dY, const void* Wt, void*
   ConvArgs a = conv_args(dY, Wt, dQ, M, K, N);
   conv_args_bnstats(a, bn_x, bn_scale_shift, bn_mean_invstd, bn_act, partial);
   return conv_fwd_launch(a, false, stream);
+}
+
+// ---- the same backward-data WITHOUT its dQ: "pf_conv1x1_bwd_data_bnstats, pf_bn_bwd_finalize, pf_bn_bwd_apply_add" as the pair
+// pf_conv1x1_bwd_data_bnsums, pf_bn_bwd_finalize, pf_conv1x1_bwd_data_bnapply.  The second launch runs the (nearly free) product
+// again and applies the BN backward to the tile in its row pass: dQ, one write and one read of the 4C-wide tensor, never exists.
+// Offered where the plan of the bnstats launch names the resident kernel in a slice width the variants are compiled for, and
+// K >= 2 * N (below that the second read of dY eats the saving).  The plan of the launch IS the plan of the query; a shape it does
+// not take gets hipErrorInvalidValue from both entries (there is no slower route behind them: the caller keeps the three launches).
+static bool conv_bn_pair_plan(int M, int N, int K, Conv1x1Plan* p) {
+  if (M <= 0 || N <= 0 || K <= 0 || (K % 8) || (N % 8) || K < 2 * N) return false;
+  Conv1x1Req q = conv_query_req(M, K, N, false);
+  q.bwd = true;
+  *p = conv1x1_plan(q);
+  return pf_conv_stream_bn_pair_ok(*p);
+}
+extern "C" int pf_conv1x1_bwd_apply_plan(int M, int N, int K) {
+  Conv1x1Plan p;
+  return conv_bn_pair_plan(M, N, K, &p) ? 1 : 0;
+}
+
+// partial[G][2][K] of pf_conv1x1_bwd_data_bnstats (same G, same bits), nothing else written
+extern "C" int pf_conv1x1_bwd_data_bnsums(const void* dY, const void* Wt, const void* bn_x, const float* bn_scale_shift,
+                                          const float* bn_mean_invstd, int bn_act, float* partial, int M, int N, int K,
+                                          void* stream) {
+  Conv1x1Plan p;
+  if (!conv_bn_pair_plan(M, N, K, &p)) return (int)hipErrorInvalidValue;
+  if (dY == nullptr || Wt == nullptr || bn_x == nullptr || bn_scale_shift == nullptr || bn_mean_invstd == nullptr || partial == nullptr ||
+      !pf_aligned16(dY) || !pf_aligned16(Wt) || !pf_aligned16(bn_x))
+    return (int)hipErrorInvalidValue;
+  ConvArgs a = conv_args(dY, Wt, nullptr, M, K, N);
+  conv_args_bnstats(a, bn_x, bn_scale_shift, bn_mean_invstd, bn_act, partial);
+  return pf_conv_stream_launch_bn_pair(a, p, BV_SUMS, bn_act, BnApplyArgs{nullptr, nullptr, nullptr}, (hipStream_t)stream);
+}
+
+// dx[M][K] = what pf_bn_bwd_apply_add(dQ, x, addend, ...) makes of the dQ pf_conv1x1_bwd_data_bnstats would have stored, bit for bit
+// (bf16; act: PF_ACT_RELU / PF_ACT_RELU6).  dgamma / dbeta: the finalised sums (pf_bn_bwd_finalize).  addend may be null.
+extern "C" int pf_conv1x1_bwd_data_bnapply(const void* dY, const void* Wt, const void* x, const float* scale_shift,
+                                           const float* mean_invstd, int act, const float* dgamma, const float* dbeta,
+                                           const void* addend, void* dx, int M, int N, int K, void* stream) {
+  Conv1x1Plan p;
+  if (!conv_bn_pair_plan(M, N, K, &p)) return (int)hipErrorInvalidValue;
+  if (dY == nullptr || Wt == nullptr || x == nullptr || scale_shift == nullptr || mean_invstd == nullptr || dgamma == nullptr ||
+      dbeta == nullptr || dx == nullptr || !pf_aligned16(dY) || !pf_aligned16(Wt) || !pf_aligned16(x) || !pf_aligned16(dx) ||
+      !pf_aligned16(addend) || (act != PF_ACT_RELU && act != PF_ACT_RELU6))
+    return (int)hipErrorInvalidValue;
+  ConvArgs a = conv_args(dY, Wt, dx, M, K, N);
+  conv_args_bnstats(a, x, scale_shift, mean_invstd, act, nullptr);
+  return pf_conv_stream_launch_bn_pair(a, p, BV_APPLY, act, BnApplyArgs{(const bf16_t*)addend, dgamma, dbeta}, (hipStream_t)stream);
 }
 
 // backward-data of a stride-1 1x1 convolution joined with the gradient R of a second consumer of Q (include/pocketflow_hip.h):

@@ -61,6 +61,16 @@ struct ConvArgs {
   int rHo, rWo, rH, rW, rstride;
 };
 
+// The pair that replaces "backward-data with BN-backward sums, then the BN-backward apply pass" without ever storing dq
+// (pf_conv1x1_bwd_data_bnsums / pf_conv1x1_bwd_data_bnapply; kernel variants in pf_conv_stream.hip).  BV_STORE is the one launch.
+enum { BV_STORE = 0, BV_SUMS = 1, BV_APPLY = 2 };
+struct BnApplyArgs {        // BV_APPLY only
+  const bf16_t* addend;     // [M][N] added to dx in fp32 before its one rounding, or null: no add at all (not + 0)
+  const float* dgamma;      // [N] finalised sum dy * xhat
+  const float* dbeta;       // [N] finalised sum dy
+};
+struct ConvArgsBn : ConvArgs { BnApplyArgs ap; };     // the argument block of the BV_APPLY kernel
+
 // workgroups of a persistent tiled launch and (G) the row-tile groups they form: about `slots` resident workgroups (512: 2 per CU),
 // G a multiple of 8 so that the column tiles of one row panel share an XCD
 static inline int pf_conv_grid(int slots, int tiles_m, int tiles_n, int* G_out) {

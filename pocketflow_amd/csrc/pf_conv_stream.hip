@@ -38,8 +38,21 @@
 // BR: backward-data with the BN-backward sums AND a residual (BWD alone has none): the residual lands on the accumulators, they are
 // rounded once and staged, and the row pass takes the sums from the staged values -- the arithmetic of BWD on the value a separate
 // statistics pass would read back.  The sums keep no min / max, whose registers pay for the residual's.
-template <int NW, bool PRO, bool BWD, bool MAP, bool AFF = false, bool RMAP = false, bool BR = false>
-__global__ __launch_bounds__(ST_THREADS) void k_conv1x1_stream(const ConvArgs a, const int nsplit) {
+// BV (BWD without BR): what the row pass does with the staged dq tile.  BV_STORE: stores it and takes the sums (the one launch of
+// pf_conv1x1_bwd_data_bnstats).  The other two are the PAIR that never writes dq (pf_conv1x1_bwd_data_bnsums / _bnapply): BV_SUMS is
+// BV_STORE without its store; BV_APPLY runs the same product again after the sums were finalised and its row pass is the BN-backward
+// apply pass of pf_bn.hip (bn_bwd_dx<ACT> on the staged, rounded dq, + the shortcut's gradient, one rounding) whose result goes
+// to a.Y.  dq is rounded to bf16 in the staging either way, so the pair gives the bits of launch + k_bn_bwd_apply.  BV_APPLY alone
+// takes the longer argument block (ConvArgsBn): every other instantiation keeps its arguments, offsets and instructions.
+template <int BV> struct StreamArgs { typedef ConvArgs type; };
+template <> struct StreamArgs<BV_APPLY> { typedef ConvArgsBn type; };
+__device__ __forceinline__ BnApplyArgs stream_bn_apply_args(const ConvArgs&) { return BnApplyArgs{nullptr, nullptr, nullptr}; }
+__device__ __forceinline__ BnApplyArgs stream_bn_apply_args(const ConvArgsBn& a) { return a.ap; }
+template <int NW, bool PRO, bool BWD, bool MAP, bool AFF = false, bool RMAP = false, bool BR = false, int BV = BV_STORE,
+          int ACT = PF_ACT_NONE>
+__global__ __launch_bounds__(ST_THREADS) void k_conv1x1_stream(const typename StreamArgs<BV>::type a, const int nsplit) {
+  [[maybe_unused]] const BnApplyArgs ap = stream_bn_apply_args(a);
+  static_assert(BV == BV_STORE || (BWD && !BR), "BV is a variant of the plain BWD row pass");
   constexpr int JM = (NW == 256) ? 1 : 2;           // 16-pixel blocks per strip
   constexpr int RS = 16 * JM;                       // pixel rows per strip
   constexpr int NI = NW / 16;                       // 16-channel blocks
@@ -57,8 +70,9 @@ __global__ __launch_bounds__(ST_THREADS) void k_conv1x1_stream(const ConvArgs a,
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int K = a.K, KC = K >> 6, KV = K >> 3;
   bf16_t* Wl = reinterpret_cast<bf16_t*>(smem);                          // [NW][K], 16-byte groups XOR-swizzled
-  float* aux = reinterpret_cast<float*>(smem + (size_t)NW * K * 2);      // PRO: scale | shift [2][K];  BWD: [4][NW]
-  const int aux_fl = PRO ? 2 * K : (BWD ? 4 * NW : 0);
+  float* aux = reinterpret_cast<float*>(smem + (size_t)NW * K * 2);      // PRO: scale | shift [2][K];  BWD: [4][NW], BV_APPLY: [6][NW]
+  constexpr int BQ = (BV == BV_APPLY) ? 6 : 4;                          // scale | shift | mean | invstd (| dbeta / n | dgamma / n)
+  const int aux_fl = PRO ? 2 * K : (BWD ? BQ * NW : 0);
   bf16_t* Cs_all = reinterpret_cast<bf16_t*>(smem + (size_t)NW * K * 2 + (size_t)aux_fl * 4);
   float* red = reinterpret_cast<float*>(Cs_all);                         // final statistics reduction [4][8][NW]
 
@@ -96,6 +110,15 @@ __global__ __launch_bounds__(ST_THREADS) void k_conv1x1_stream(const ConvArgs a,
       if (c < a.N) v = (qq < 2) ? a.bss[qq * a.N + c] : a.bmi[(qq - 2) * a.N + c];
       aux[i] = v;
     }
+    if constexpr (BV == BV_APPLY) {
+      const float inv_n = 1.0f / (float)(int64_t)a.M;                    // as k_bn_bwd_apply forms them
+      for (int i = tid; i < 2 * NW; i += ST_THREADS) {
+        const int qq = i / NW, c = n0 + (i - qq * NW);
+        float v = 0.f;
+        if (c < a.N) v = (qq == 0 ? ap.dbeta[c] : ap.dgamma[c]) * inv_n;
+        aux[4 * NW + i] = v;
+      }
+    }
   }
   __syncthreads();
 
@@ -108,6 +131,7 @@ __global__ __launch_bounds__(ST_THREADS) void k_conv1x1_stream(const ConvArgs a,
   f32x4 acc[NI][JM];
   uint4 ring[D][NR];
   uint4 rres[NP];
+  uint4 radd[BV == BV_APPLY ? NP : 1];                                   // BV_APPLY: the addend of the CURRENT strip (issue_add)
   uint2 rr[NI][JM];                                                      // residual of the NEXT strip, accumulator layout
   float st_s[8], st_q[8], st_mn[BR ? 1 : 8], st_mx[BR ? 1 : 8];
 #pragma unroll
@@ -137,6 +161,12 @@ __global__ __launch_bounds__(ST_THREADS) void k_conv1x1_stream(const ConvArgs a,
       v = *reinterpret_cast<const uint4*>(side + orow * a.N + n);
     }
     rres[p] = v;
+  };
+  auto issue_add = [&](int s, int p) {                                   // BV_APPLY: the addend in the row-pass layout, as `side`
+    const int m = s * RS + p * RPP + wrow, n = n0 + wvec * 8;
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (m < a.M && n < a.N) v = *reinterpret_cast<const uint4*>(ap.addend + (int64_t)m * a.N + n);
+    radd[BV == BV_APPLY ? p : 0] = v;
   };
 
   // residual of strip s in the accumulator layout (this lane: pixel (j, l15), four channels of block i = 8 bytes)
@@ -170,6 +200,7 @@ __global__ __launch_bounds__(ST_THREADS) void k_conv1x1_stream(const ConvArgs a,
 #pragma unroll
     for (int p = 0; p < NP; ++p) issue_side(s_first, p);
   }
+  const bool has_add = (BV == BV_APPLY) && ap.addend != nullptr;
 
   int cs = s_first, ckc = 0;                                             // compute-side cursor
   int slot = 0;                                                          // ring slot of chunk t (wave-uniform)
@@ -288,21 +319,32 @@ __global__ __launch_bounds__(ST_THREADS) void k_conv1x1_stream(const ConvArgs a,
         const uint2 w = make_uint2(pack_bf16x2(acc[i][j][0], acc[i][j][1]), pack_bf16x2(acc[i][j][2], acc[i][j][3]));
         *reinterpret_cast<uint2*>(Cs + (j * 16 + l15) * CS_LD + i * 16 + q * 4) = w;
       }
+    // BV_APPLY: the addend is requested HERE, into the registers the staged accumulators have just left, not under the main loop
+    // beside the BN-input vectors: with a second set of NP vectors travelling there the kernel spilled 35 registers (the sums'
+    // 16 registers do not pay for 32).  One round trip per strip and wavefront, the first passes' LDS reads and the other
+    // wavefronts of the CU in front of it -- the RLATE arrangement.
+    if constexpr (BV == BV_APPLY) {
+      if (has_add) {
+#pragma unroll
+        for (int p = 0; p < NP; ++p) issue_add(s, p);
+      }
+    }
     const bool more = (cs < NS);                                         // this wavefront has another strip
     if (has_r && !RLATE && more) issue_res(cs);                                 // next strip's residual travels under its main loop
-    float bpr[32];                                                       // BWD: this lane's 8 channels of scale | shift | mean | invstd
+    float bpr[8 * BQ];                                                   // BWD: this lane's 8 channels of scale | shift | mean | invstd
     // BR: the residual's registers take the room of the hoisted constants -- they are read from LDS in every pass, as at NW = 128
-    constexpr bool BPL = (NW == 128) || BR;
+    // BV_APPLY: six vectors of constants, hoisted, spilled 113 registers beside the addend's -- from LDS as well
+    constexpr bool BPL = (NW == 128) || BR || BV == BV_APPLY;
     if (BWD && !BPL) {
 #pragma unroll
-      for (int qq = 0; qq < 4; ++qq)
+      for (int qq = 0; qq < BQ; ++qq)
 #pragma unroll
         for (int j = 0; j < 8; ++j) bpr[qq * 8 + j] = aux[qq * NW + wvec * 8 + j];
     } else if (BWD) {
 #pragma unroll
-      for (int i = 0; i < 32; ++i) bpr[i] = 0.f;
+      for (int i = 0; i < 8 * BQ; ++i) bpr[i] = 0.f;
     }
-    constexpr int CB = (NW == 128 || (BR && NW == 256)) ? 1 : (BR ? 2 : 4);                  // scheduling experiment: rows requested CB at a time
+    constexpr int CB = (NW == 128 || (BR && NW == 256)) ? 1 : ((BR || BV == BV_APPLY) ? 2 : 4);                 // scheduling experiment: rows requested CB at a time
     uint4 cv[CB];                                                        // (NW = 128 has no registers to spare: it spills as it is)
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
@@ -316,9 +358,29 @@ __global__ __launch_bounds__(ST_THREADS) void k_conv1x1_stream(const ConvArgs a,
       uint4 c = cv[p % CB];
       const uint4 sv = rres[p];
       if (side != nullptr && more) issue_side(cs, p);                    // next strip's vector into the freed register
+      [[maybe_unused]] uint4 av = make_uint4(0, 0, 0, 0);
+      if constexpr (BV == BV_APPLY) {
+        av = radd[p];
+      }
       if (m < a.M && n < a.N) {
         const int64_t orow = (MAP && a.ymap) ? map_row(a, m) : (int64_t)m;
-        if constexpr (BWD) {
+        if constexpr (BV == BV_APPLY) {
+          float f[8], xv[8];
+          unpack8(c, f);
+          unpack8(sv, xv);
+          const float* bp = BPL ? (aux + wvec * 8) : bpr;
+          constexpr int BPS = BPL ? NW : 8;
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            f[j] = bn_bwd_dx<ACT>(f[j], xv[j], bp[j], bp[BPS + j], bp[2 * BPS + j], bp[3 * BPS + j], bp[4 * BPS + j], bp[5 * BPS + j]);
+          if (has_add) {
+            float ad[8];
+            unpack8(av, ad);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) f[j] += ad[j];
+          }
+          c = pack8(f);
+        } else if constexpr (BWD) {
           float f[8], xv[8];
           unpack8(c, f);
           unpack8(sv, xv);
@@ -345,13 +407,13 @@ __global__ __launch_bounds__(ST_THREADS) void k_conv1x1_stream(const ConvArgs a,
           }
         }
         if constexpr (AFF) c = out_affine8(c, a.oss, a.N, n, a.oact);
-        *reinterpret_cast<uint4*>(a.Y + orow * a.N + n) = c;
+        if constexpr (BV != BV_SUMS) *reinterpret_cast<uint4*>(a.Y + orow * a.N + n) = c;
       }
     }
   }
 
   // ---- statistics: lanes with equal column group -> wavefronts -> partial[g][stat][n0 + c], fixed order --------
-  if (a.partial != nullptr) {
+  if (BV != BV_APPLY && a.partial != nullptr) {
 #pragma unroll
     for (int o = VPR; o < 64; o <<= 1) {
 #pragma unroll
@@ -418,15 +480,33 @@ bool pf_conv_stream_plan(const Conv1x1Req& q, Conv1x1Plan* p) {
   return true;
 }
 
-template <int NW, bool PRO, bool BWD, bool MAP, bool AFF = false, bool RMAP = false, bool BR = false>
-static int stream_launch_t(const ConvArgs& a, int nsplit, hipStream_t st) {
+template <int NW, bool PRO, bool BWD, bool MAP, bool AFF = false, bool RMAP = false, bool BR = false, int BV = BV_STORE,
+          int ACT = PF_ACT_NONE>
+static int stream_launch_t(const typename StreamArgs<BV>::type& a, int nsplit, hipStream_t st) {
   const int JM = (NW == 256) ? 1 : 2, RS = 16 * JM;
-  const size_t aux_fl = PRO ? 2 * (size_t)a.K : (BWD ? 4 * (size_t)NW : 0);
+  const size_t aux_fl = PRO ? 2 * (size_t)a.K : (BWD ? (BV == BV_APPLY ? 6 : 4) * (size_t)NW : 0);
   const size_t lds = (size_t)NW * a.K * 2 + aux_fl * 4 + (size_t)ST_WAVES * RS * (NW + 8) * 2;
-  if (int e = pf_require_lds(reinterpret_cast<const void*>(&k_conv1x1_stream<NW, PRO, BWD, MAP, AFF, RMAP, BR>), lds)) return e;
-  k_conv1x1_stream<NW, PRO, BWD, MAP, AFF, RMAP, BR><<<ST_GRID, ST_THREADS, lds, st>>>(a, nsplit);
+  if (int e = pf_require_lds(reinterpret_cast<const void*>(&k_conv1x1_stream<NW, PRO, BWD, MAP, AFF, RMAP, BR, BV, ACT>), lds)) return e;
+  k_conv1x1_stream<NW, PRO, BWD, MAP, AFF, RMAP, BR, BV, ACT><<<ST_GRID, ST_THREADS, lds, st>>>(a, nsplit);
   PF_LAUNCH_CHECK();
   return 0;
+}
+
+// The pair without dq: is the plan `p` of a backward-data launch with BN-backward sums (q.bwd) one whose kernel variants are compiled?
+// The 256-wide slice, stride 1 (stages 1-2 of the bottleneck networks: N = 64 -> K = 256, N = 128 -> K = 512 in two slices).
+bool pf_conv_stream_bn_pair_ok(const Conv1x1Plan& p) { return p.kernel == CONV_STREAM && p.nw == 256; }
+
+// variant: BV_SUMS (a.partial set, a.Y unused) or BV_APPLY (a.Y = dx, a.partial null, act = the BN's ReLU-type activation)
+int pf_conv_stream_launch_bn_pair(const ConvArgs& a, const Conv1x1Plan& p, int variant, int act, const BnApplyArgs& ap, hipStream_t st) {
+  if (!pf_conv_stream_bn_pair_ok(p) || a.bx == nullptr || a.R != nullptr || a.stride != 1) return (int)hipErrorInvalidValue;
+  if (variant == BV_SUMS) return stream_launch_t<256, false, true, false, false, false, false, BV_SUMS>(a, p.nsplit, st);
+  if (variant != BV_APPLY) return (int)hipErrorInvalidValue;
+  ConvArgsBn ab;
+  static_cast<ConvArgs&>(ab) = a;
+  ab.ap = ap;
+  if (act == PF_ACT_RELU) return stream_launch_t<256, false, true, false, false, false, false, BV_APPLY, PF_ACT_RELU>(ab, p.nsplit, st);
+  if (act == PF_ACT_RELU6) return stream_launch_t<256, false, true, false, false, false, false, BV_APPLY, PF_ACT_RELU6>(ab, p.nsplit, st);
+  return (int)hipErrorInvalidValue;
 }
 
 // a: filled by conv_fwd_launch (pf_conv.hip), p: its plan (kernel == CONV_STREAM)

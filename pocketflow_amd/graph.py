@@ -625,11 +625,12 @@ class BnSums(object):
   grad_fn -> ctx which only Python's cyclic collector frees -- one step's activations (~10 GB at B = 256) alive for a random number
   of further steps, the caching allocator at the memory ceiling (measured: 26 GB reserved after 5 steps, 52 GB after 13; DESIGN.md
   section 6)."""
-  __slots__ = ('x', 'scale_shift', 'mean_invstd', 'act', 'n_consumers', 'bwd_stats')
+  __slots__ = ('x', 'scale_shift', 'mean_invstd', 'act', 'n_consumers', 'bwd_stats', 'deferred')
 
   def __init__(self):
     self.n_consumers = 0
     self.bwd_stats = None                        # (partial, n_blocks, data_ptr of the dq they are the sums of)
+    self.deferred = None                         # (dy, wt, M, N, K, placeholder): that dq was never written (defer)
 
   def sums_for(self, dq):
     """(partial, n_blocks) where the single consumer's backward-data kernel already reduced THIS dq, else None."""
@@ -658,6 +659,24 @@ class BnSums(object):
     """After that launch: the sums of `dx`, for the BN node's backward to find (sums_for)."""
     self.bwd_stats = (partial, G, dx.data_ptr())
 
+  def defer(self, partial, G: int, dy, wt, M: int, N: int, K: int, like):
+    """After the sums-only launch (conv1x1_bwd_data_bnsums): the sums as `leave`, and what the BN node's apply pass needs to
+    recompute dq = dy * wt in its own launch (conv1x1_bwd_data_bnapply), referenced until it ran.  Returns the gradient autograd
+    carries to that node instead: a placeholder of x's shape that owns one element (a zero-stride expand), recognised there by its
+    address (deferred_for) and never read."""
+    placeholder = torch.empty(1, dtype=like.dtype, device=like.device).expand(like.shape)
+    self.bwd_stats = (partial, G, placeholder.data_ptr())
+    self.deferred = (dy, wt, M, N, K, placeholder)
+    return placeholder
+
+  def deferred_for(self, dq):
+    """(dy, wt, M, N, K) where `dq` is the placeholder `defer` handed out, else None.  Taken once: the references go with it."""
+    d = self.deferred
+    if d is None or d[5].data_ptr() != dq.data_ptr():
+      return None
+    self.deferred = None
+    return d[:5]
+
 
 def _bn_enter(ctx, x, gamma, beta, layer, graph, training, slot, stats, rec=None, *more):
   """The forward prologue the BN nodes share: x in NHWC memory, the layer's scale / shift (_bn_scale_shift), and everything
@@ -680,6 +699,10 @@ def _bn_leave(ctx, dq, pre=None, **kw):
   act, graph, rows, C, params, frozen, rec = ctx.bn
   if rec is not None:
     pre = rec.sums_for(dq)
+    if pre is not None:
+      kw['deferred'] = rec.deferred_for(dq)
+    if rec.deferred is not None:                 # a placeholder went out and something else came back: there is no dq to fall back on
+      raise RuntimeError('BN backward: the deferred input gradient of the consuming convolution did not arrive as handed out')
   return _bn_backward(dq, x, scale_shift, mean_invstd, act, graph, rows, C, params=params, pre=pre, frozen=frozen, **kw)
 
 
@@ -1034,16 +1057,22 @@ def _grad_view(t: Optional[torch.Tensor], n: int):
 
 
 def _bn_backward(dq, x, scale_shift, mean_invstd, act, graph, rows, C, addend=None, params=None, pre=None,
-                 frozen=False, pool_hw=None):
+                 frozen=False, pool_hw=None, deferred=None):
   """Returns (dx, dgamma, dbeta); when `params` = (gamma leaf, beta leaf) carry flat-buffer gradient views,
   dgamma / dbeta are written there by pf_bn_bwd_finalize and None is returned for them (no accumulation
   kernels; every BN layer is applied once per step and the buffers are zeroed by the optimiser).
   `frozen`: inference-mode BN (moving statistics are constants): the batch-statistics terms of dx vanish,
   dx = scale * dy -- the same apply kernel fed with zero sums.
-  `pool_hw`: dq is the [B][C] gradient of the POOLED tensor (_BnActPool); both passes rebuild the per-pixel value from it."""
-  dq = _nhwc(dq)
-  if dq.dtype != x.dtype:
-    dq = dq.to(x.dtype)
+  `pool_hw`: dq is the [B][C] gradient of the POOLED tensor (_BnActPool); both passes rebuild the per-pixel value from it.
+  `deferred` = (dy, wt, M, N, K) (BnSums.defer; with `pre`, training mode, not pooled): dq is a placeholder -- the single consumer's
+  backward-data left the sums and no dq, and the apply pass is that GEMM again with the BN backward as its row pass
+  (conv1x1_bwd_data_bnapply: the same bits as the stored dq through bn_bwd_apply, without its write and read)."""
+  if deferred is not None:
+    assert pre is not None and not frozen and pool_hw is None
+  else:
+    dq = _nhwc(dq)
+    if dq.dtype != x.dtype:
+      dq = dq.to(x.dtype)
   if addend is not None:
     addend = _nhwc(addend)
     if addend.dtype != x.dtype:
@@ -1074,6 +1103,12 @@ def _bn_backward(dq, x, scale_shift, mean_invstd, act, graph, rows, C, addend=No
   dx = torch.empty_like(x)
   zero = graph.zero_row(C)[:C] if frozen else None
   name, traffic, launch, hw, tail = apply_pass
+  if deferred is not None:
+    dy, wt, M, N, K = deferred
+    # reads dy (N of K channels wide), x and the addend, writes dx
+    with region(name, (3 if addend is not None else 2) * nbytes + float(dy.numel() * dy.element_size())):
+      hip.conv1x1_bwd_data_bnapply(dy, wt, x, scale_shift, mean_invstd, act, dgamma, dbeta, addend, dx, M, N, K)
+    return (dx, None, None) if direct else (dx, dgamma, dbeta)
   with region(name, traffic):
     launch(dq, x, dx, rows, C, *hw, scale_shift, mean_invstd, zero if frozen else dgamma, zero if frozen else dbeta, act,
            *tail)
@@ -1180,14 +1215,18 @@ def _run_conv1x1(x, w2d, lazy, residual, want_stats, stride, out_bn=None):
   return y
 
 
-def _conv1x1_bwd_data_plan(lazy, bn, geom, act, M: int, N: int, K: int):
+def _conv1x1_bwd_data_plan(lazy, bn, geom, act, M: int, N: int, K: int, dtype=None):
   """How _FusedConv1x1.backward computes its input gradient: (launch, outcome, alloc), decided here and nowhere else, from the
   producer's LazyAct and BnSums record (None: a materialised input / no training-mode BN), the row map `geom` of a strided layer,
   the producer's activation, the GEMM shape and the switches as they stand at this call.
-    launch   the ONE launch:  'compact' | 'join_stats' | 'join' | 'bnstats' | 'residual' | 'plain' (with the row scatter when strided)
+    launch   the ONE launch:  'compact' | 'join_stats' | 'join' | 'bnstats' | 'bnsums' | 'residual' | 'plain' (with the row scatter
+             when strided)
     outcome  'parked' on the LazyAct for the second consumer | 'delivered' together with the parked gradient | 'plain'
-    alloc    dx is 'compact' ([B][K][Ho][Wo]) | 'empty' | 'zeros' (the row scatter writes every stride-th pixel)
+    alloc    dx is 'compact' ([B][K][Ho][Wo]) | 'empty' | 'zeros' (the row scatter writes every stride-th pixel) | 'deferred' (none)
   'bnstats': the single consumer of a ReLU / ReLU6 BN leaves the BN-backward sums of its dx (BnSums), stride 1 only.
+  'bnsums': the same sums WITHOUT the dx (where the loaded library offers the pair and its plan takes the shape and `dtype`, bfloat16:
+  conv1 of an identity bottleneck block in stages 1-2).  The BN node's apply pass is dx's one reader; it recomputes the product in
+  its own launch (BnSums.defer, _bn_backward), so the 4C-wide dx is neither written nor read.  PF_BN1_RECOMPUTE=0: 'bnstats'.
   The join: an activation with exactly TWO fused consumers (bn1 of a projection block: shortcut convolution + conv1): the consumer
   whose backward runs first parks its dq on the LazyAct and reports no gradient; the second takes it as the residual operand of its
   backward-data kernel ('residual') -- the sum autograd would form with a separate add kernel (two reads and one write of the
@@ -1204,6 +1243,11 @@ def _conv1x1_bwd_data_plan(lazy, bn, geom, act, M: int, N: int, K: int):
   alloc = 'empty' if geom is None else 'zeros'
   if not join:
     fuse_stats = FUSE_BN_BWD_STATS and bn is not None and bn.n_consumers == 1 and geom is None and relu
+    if fuse_stats and BN1_RECOMPUTE and dtype is not None:
+      pair_plan = getattr(hip, 'conv1x1_bwd_apply_plan', None)          # (the library's: zero for anything but bfloat16)
+      if (pair_plan is not None and getattr(hip, 'conv1x1_bwd_data_bnsums', None) is not None
+          and getattr(hip, 'conv1x1_bwd_data_bnapply', None) is not None and pair_plan(M, N, K, dtype) != 0):
+        return 'bnsums', 'plain', 'deferred'
     return ('bnstats' if fuse_stats else 'plain'), 'plain', alloc
   join_entry = getattr(hip, 'conv1x1_bwd_data_join', None) if PROJ_JOIN else None
   if lazy.pending is None:                       # the first of the two
@@ -1257,14 +1301,14 @@ class _FusedConv1x1(torch.autograd.Function):
       dw = _filter_grad(graph, ctx.w_leaf, ctx.w_var, (dy, x, w2d, ss, lazy), 'conv1x1_wrw', float((M * K + M * N) * 2), wrw)
     if ctx.needs_input_grad[0]:
       wt = _bwd_data_weight(graph, ctx.w_var, ctx.w_leaf).view(K, N)           # [K][N]
-      launch, outcome, alloc = _conv1x1_bwd_data_plan(lazy, bn, geom, act, M, N, K)
+      launch, outcome, alloc = _conv1x1_bwd_data_plan(lazy, bn, geom, act, M, N, K, x.dtype)
       if alloc == 'compact':
         dx = torch.empty((x.shape[0], K, geom[0], geom[1]), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-      else:
+      elif alloc != 'deferred':
         dx = torch.empty_like(x) if alloc == 'empty' else torch.zeros_like(x)
       res = lazy.pending if launch in ('join_stats', 'join', 'residual') else None
-      with region('conv1x1_bwd_data', float((M * K * (1 if launch in ('compact', 'plain') else 2) + M * N) * 2)):
-        leaves_sums = launch in ('join_stats', 'bnstats')
+      with region('conv1x1_bwd_data', float((M * K * {'compact': 1, 'plain': 1, 'bnsums': 1}.get(launch, 2) + M * N) * 2)):
+        leaves_sums = launch in ('join_stats', 'bnstats', 'bnsums')
         if leaves_sums:
           G = hip.conv1x1_stats_groups(M, K, N)
           partial = bn.sums_buffer(G, K, x.device)
@@ -1277,11 +1321,15 @@ class _FusedConv1x1(torch.autograd.Function):
           hip.conv1x1_bwd_data_join(dy, wt, dx, res, M, N, K, rgeom=lazy.pending_geom)
         elif launch == 'bnstats':
           hip.conv1x1_bwd_data_bnstats(dy, wt, dx, x, bn.scale_shift, bn.mean_invstd, act, partial, M, N, K)
+        elif launch == 'bnsums':
+          hip.conv1x1_bwd_data_bnsums(dy, wt, x, bn.scale_shift, bn.mean_invstd, act, partial, M, N, K)
         elif launch == 'residual':
           hip.conv1x1_fwd(dy, wt, dx, M, K, N, R=res)
         else:
           hip.conv1x1_fwd(dy, wt, dx, M, K, N, geom=geom, ymap=geom is not None)
-        if leaves_sums:
+        if launch == 'bnsums':
+          dx = bn.defer(partial, G, dy, wt, M, N, K, x)
+        elif leaves_sums:
           bn.leave(partial, G, dx)
       if outcome == 'parked':
         lazy.pending, dx = dx, None             # the second consumer delivers the sum
@@ -1299,6 +1347,9 @@ JOIN_TWO_CONSUMERS = os.environ.get('PF_JOIN_TWO_CONSUMERS', '1') != '0'
 # map (0: the zero-filled full-size tensor and the row scatter); ..._STATS: the BN-backward sums of bn1 in that launch (0: pf_bn_bwd_stats)
 PROJ_JOIN = os.environ.get('PF_PROJ_JOIN', '1') != '0'
 PROJ_JOIN_STATS = os.environ.get('PF_PROJ_JOIN_STATS', '1') != '0'
+# identity blocks of stages 1-2: conv1's input gradient is never written -- sums-only backward-data, then bn1's apply pass recomputes
+# the product in its own launch (0: the backward-data that stores it + pf_bn_bwd_apply_add, for A/B runs)
+BN1_RECOMPUTE = os.environ.get('PF_BN1_RECOMPUTE', '1') != '0'
 USE_SEG_TRANSPOSE = os.environ.get('PF_SEG_TRANSPOSE', '1') != '0'   # backward-data kernel layouts in one launch (0: aten)
 OWN_POOL = os.environ.get('PF_OWN_POOL', '1') != '0'         # stem max-pooling on pf_pool.hip (0: aten, for A/B runs)
 # backward-filter of the RxS convolutions on pf_wrw.hip (shared-tile kernel); PF_OWN_CONV2D_WRW=0: MIOpen, for A/B runs

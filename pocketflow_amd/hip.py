@@ -61,6 +61,7 @@ SYMBOLS = [
     'pf_bn_act_quant_static', 'pf_conv_i8_fwd_q', 'pf_dw_i8_fwd_q',
     'pf_bn_add_act_groups', 'pf_bn_add_act_fwd', 'pf_bn_add_act_bwd_gate', 'pf_bn_add_act_bwd_gate_add',
     'pf_bn_vector_ok',
+    'pf_conv1x1_bwd_apply_plan', 'pf_conv1x1_bwd_data_bnsums', 'pf_conv1x1_bwd_data_bnapply',
 ]
 
 
@@ -570,6 +571,40 @@ def conv1x1_bwd_data_bnstats(dY, Wt, dQ, bn_x, bn_scale_shift, bn_mean_invstd, b
   _check(_lib.pf_conv1x1_bwd_data_bnstats(_ptr(dY), _ptr(Wt), _ptr(dQ), _ptr(bn_x), _ptr(bn_scale_shift),
                                           _ptr(bn_mean_invstd), c_int(ACT_CODES[bn_act]), _ptr(partial), c_int(M),
                                           c_int(N), c_int(K), _stream()), 'pf_conv1x1_bwd_data_bnstats')
+
+
+def conv1x1_bwd_apply_plan(M: int, N: int, K: int, dtype=torch.bfloat16) -> int:
+  """Non-zero when the pair conv1x1_bwd_data_bnsums / conv1x1_bwd_data_bnapply is offered for dQ[M][K] = dY[M][N] * W: the plan of
+  conv1x1_bwd_data_bnstats names the resident kernel in a compiled slice width, K >= 2 * N, bfloat16."""
+  if dtype != torch.bfloat16:
+    return 0
+  return int(_lib.pf_conv1x1_bwd_apply_plan(c_int(M), c_int(N), c_int(K)))
+
+
+def _bf16_only(what: str, *tensors) -> None:
+  for t in tensors:
+    if t is not None and t.dtype != torch.bfloat16:
+      raise RuntimeError('%s failed: bfloat16 only (got %s)' % (what, t.dtype))
+
+
+def conv1x1_bwd_data_bnsums(dY, Wt, bn_x, bn_scale_shift, bn_mean_invstd, bn_act, partial, M: int, N: int, K: int) -> None:
+  """conv1x1_bwd_data_bnstats without its dQ: the same partial [G][2][K], G = conv1x1_stats_groups(M, K, N), bit for bit.  Only
+  where conv1x1_bwd_apply_plan(M, N, K) is non-zero (an error elsewhere)."""
+  _dev(dY)
+  _bf16_only('pf_conv1x1_bwd_data_bnsums', dY, Wt, bn_x)
+  _check(_lib.pf_conv1x1_bwd_data_bnsums(_ptr(dY), _ptr(Wt), _ptr(bn_x), _ptr(bn_scale_shift), _ptr(bn_mean_invstd),
+                                         c_int(ACT_CODES[bn_act]), _ptr(partial), c_int(M), c_int(N), c_int(K), _stream()),
+         'pf_conv1x1_bwd_data_bnsums')
+
+
+def conv1x1_bwd_data_bnapply(dY, Wt, x, scale_shift, mean_invstd, act, dgamma, dbeta, addend, dx, M: int, N: int, K: int) -> None:
+  """dx[M][K] = bn_bwd_apply(dQ, x, ..., addend) of the dQ = dY * W that conv1x1_bwd_data_bnstats would have stored, recomputed in the
+  launch and never written.  dgamma / dbeta: finalised (bn_bwd_finalize); addend may be None.  Shapes as conv1x1_bwd_data_bnsums."""
+  _dev(dY)
+  _bf16_only('pf_conv1x1_bwd_data_bnapply', dY, Wt, x, addend, dx)
+  _check(_lib.pf_conv1x1_bwd_data_bnapply(_ptr(dY), _ptr(Wt), _ptr(x), _ptr(scale_shift), _ptr(mean_invstd),
+                                          c_int(ACT_CODES[act]), _ptr(dgamma), _ptr(dbeta), _ptr(addend), _ptr(dx), c_int(M),
+                                          c_int(N), c_int(K), _stream()), 'pf_conv1x1_bwd_data_bnapply')
 
 
 def conv1x1_join_plan(M: int, N: int, K: int, with_stats: bool = False) -> int:
