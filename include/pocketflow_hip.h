@@ -457,6 +457,18 @@ int pf_depthwise_bwd_data(const void* dY, const void* W, void* dX, int dtype, in
                           int stride, int pad_h, int pad_w, int Ho, int Wo, void* stream);
 int pf_depthwise_wrw(const void* dY, const void* X, void* dW, int dtype, int dw_dtype, float* slabs, int B, int H, int Wd,
                      int C, int k, int stride, int pad_h, int pad_w, int Ho, int Wo, void* stream);
+/* MobileNet-v2 (the 6x expansion has the depthwise layer as its only reader): pf_depthwise_fwd / pf_depthwise_wrw with the producer
+ * BatchNorm's normalise / activation / fake-quant as their prologue, the argument set of the 1x1 prologue (pf_conv1x1_fwd).  X is the
+ * RAW tensor in front of the BatchNorm, scale_shift float32 [2][C], act PF_ACT_NONE | PF_ACT_RELU6 (no ReLU form is built: refused), slot the quantiser's range (NULL: no quantiser;
+ * bits 1..32 with one).  A tap inside the image has exactly the value pf_bn_act_quant_apply would have stored (rounded to the storage
+ * type); a tap outside contributes 0.  Outputs, statistics, slabs and reduction orders are those of the plain entries: bit-identical
+ * to pf_bn_act_quant_apply followed by pf_depthwise_fwd / pf_depthwise_wrw.                                                        */
+int pf_depthwise_fwd_act(const void* X, const float* scale_shift, int act, const uint32_t* slot, int bits, const void* W, void* Y,
+                         int dtype, float* partial, int B, int H, int Wd, int C, int k, int stride, int pad_h, int pad_w, int Ho,
+                         int Wo, void* stream);
+int pf_depthwise_wrw_act(const void* dY, const void* X, const float* scale_shift, int act, const uint32_t* slot, int bits, void* dW,
+                         int dtype, int dw_dtype, float* slabs, int B, int H, int Wd, int C, int k, int stride, int pad_h, int pad_w,
+                         int Ho, int Wo, void* stream);
 
 /* ---- K13: input pipeline tail -----------------------------------------------------------
  * replaces, per image, the preprocessing chain of utils/external/imagenet_preprocessing.py:226-260 behind the JPEG

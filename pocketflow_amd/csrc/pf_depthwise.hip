@@ -84,14 +84,38 @@ struct DwArgs {
   int strips_w;        // strips per output row
   int64_t total;       // strips in the tensor
   uint32_t x_bytes, dy_bytes;   // sizes of the tensors behind `x` / `dy` (buffer descriptors; < 2^31)
+  // the *_act entries: `x` is the RAW tensor in front of a BatchNorm, the kernels read act(scale * x + shift) [fake-quantised]
+  const float* ss;     // scale_shift [2][C]
+  const uint32_t* slot;   // the quantiser's min / max slot (PRO == DW_PRO_QUANT)
+  float qk;            // 2^bits - 1
 };
 
 template <typename T> __device__ __forceinline__ float dw_round(float v);
 template <> __device__ __forceinline__ float dw_round<float>(float v) { return v; }
 template <> __device__ __forceinline__ float dw_round<bf16_t>(float v) { return bf16_to_f32(f32_to_bf16(v)); }
 
+// The prologue of pf_depthwise_fwd_act / pf_depthwise_wrw_act: the value of a tap INSIDE the image is what pf_bn_act_quant_apply
+// would have stored there -- act(fmaf(scale, x, shift)), uq_point() with the slot's range when quantising, one rounding to T: the
+// same float32 operations in the same order (k_bn_apply, pf_bn.hip) -- and a tap OUTSIDE contributes 0, not act(shift): the zeros
+// the buffer descriptor returns there go through the affine map like any other value, so the validity the address computation
+// already has (one bit per vector of the strip, `okm`) selects 0 BEHIND the activation.  A register select (v_cndmask), never a
+// branch around a load: the loads of a strip stay back to back behind one wait.
+#define DW_PRO_NONE 0
+#define DW_PRO_AFFINE 1
+#define DW_PRO_QUANT 2
+template <typename T, int PRO, int ACT>
+__device__ __forceinline__ void dw_prologue(float* v, const float* sc, const float* sh, float alpha, float beta, float k, bool ok) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    float y = apply_act<ACT>(fmaf(sc[j], v[j], sh[j]));
+    if (PRO == DW_PRO_QUANT) y = uq_point(y, alpha, beta, k);
+    y = round_to<T>(y);
+    v[j] = ok ? y : 0.f;
+  }
+}
+
 // forward (and stride-1 backward-data, which is the same sum over the flipped kernel with front pads k-1-p)
-template <typename T, int ST, bool GEN>
+template <typename T, int ST, bool GEN, int PRO = DW_PRO_NONE, int ACT = PF_ACT_NONE>
 __global__ __launch_bounds__(DW_T) void k_dw_fwd(const DwArgs a) {
   __shared__ float red[4 * DW_T * 8];
   const int C8 = a.C >> 3, SPB = DW_T / C8;
@@ -105,6 +129,12 @@ __global__ __launch_bounds__(DW_T) void k_dw_fwd(const DwArgs a) {
   for (int j = 0; j < 8; ++j)
 #pragma unroll
     for (int t = 0; t < 9; ++t) wr[t][j] = load_one<T>(w + (int64_t)(cg * 8 + j) * 9 + (a.flip ? 8 - t : t));
+  float sc[8], sh[8], qa = 1.f, qb = 0.f;
+  if (PRO != DW_PRO_NONE) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { sc[j] = a.ss[cg * 8 + j]; sh[j] = a.ss[a.C + cg * 8 + j]; }
+    if (PRO == DW_PRO_QUANT) slot_alpha_beta(a.slot, qa, qb);
+  }
   float st_s[8], st_q[8], st_mn[8], st_mx[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) { st_s[j] = 0.f; st_q[j] = 0.f; st_mn[j] = INFINITY; st_mx[j] = -INFINITY; }
@@ -121,6 +151,7 @@ __global__ __launch_bounds__(DW_T) void k_dw_fwd(const DwArgs a) {
       for (int j = 0; j < 8; ++j) acc[p][j] = 0.f;
     // all 3 x NV vectors of the strip are requested before the first one is used (positions outside the image: zeros)
     DwRaw<T> raw[3][NV];
+    uint32_t okm = 0u;                             // PRO: bit r * NV + i = vector (r, i) lies inside the image
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
       const int hi = ho * ST + r - a.ph;
@@ -131,13 +162,17 @@ __global__ __launch_bounds__(DW_T) void k_dw_fwd(const DwArgs a) {
         const int wi = wo0 * ST - a.pw + i;
         const bool ok = rok && (unsigned)wi < (unsigned)a.W;
         dw_fetch<T>(rsx, ok ? rbase + (uint32_t)(wi * a.C * (int)sizeof(T)) : DW_OOB, raw[r][i]);
+        if (PRO != DW_PRO_NONE) okm |= ok ? (1u << (r * NV + i)) : 0u;
       }
     }
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
       float v[NV][8];
 #pragma unroll
-      for (int i = 0; i < NV; ++i) dw_unpack<T>(raw[r][i], v[i]);
+      for (int i = 0; i < NV; ++i) {
+        dw_unpack<T>(raw[r][i], v[i]);
+        if (PRO != DW_PRO_NONE) dw_prologue<T, PRO, ACT>(v[i], sc, sh, qa, qb, a.qk, ((okm >> (r * NV + i)) & 1u) != 0u);
+      }
 #pragma unroll
       for (int p = 0; p < DW_PW; ++p)
 #pragma unroll
@@ -234,7 +269,7 @@ __global__ __launch_bounds__(DW_T) void k_dw_bwd_data(const DwArgs a) {
 }
 
 // backward-filter: strips of 4 output pixels as in the forward kernel; slab [G][C][9]
-template <typename T, int ST, bool GEN>
+template <typename T, int ST, bool GEN, int PRO = DW_PRO_NONE, int ACT = PF_ACT_NONE>
 __global__ __launch_bounds__(DW_T) void k_dw_wrw(const DwArgs a) {
   __shared__ float red[DW_T * 8];                       // one tap at a time: [SPB][C]
   const int C8 = a.C >> 3, SPB = DW_T / C8;
@@ -247,6 +282,12 @@ __global__ __launch_bounds__(DW_T) void k_dw_wrw(const DwArgs a) {
   for (int t = 0; t < 9; ++t)
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[t][j] = 0.f;
+  float sc[8], sh[8], qa = 1.f, qb = 0.f;
+  if (PRO != DW_PRO_NONE) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { sc[j] = a.ss[cg * 8 + j]; sh[j] = a.ss[a.C + cg * 8 + j]; }
+    if (PRO == DW_PRO_QUANT) slot_alpha_beta(a.slot, qa, qb);
+  }
   constexpr int NV = (DW_PW - 1) * ST + 3;
   for (int64_t strip = idle ? a.total : (int64_t)blockIdx.x * SPB + sl; strip < a.total; strip += (int64_t)gridDim.x * SPB) {
     const int sw = (int)(strip % a.strips_w);
@@ -255,6 +296,7 @@ __global__ __launch_bounds__(DW_T) void k_dw_wrw(const DwArgs a) {
     const int wo0 = sw * DW_PW;
     // the 4 gradient vectors and the 3 x NV input vectors of the strip, requested at once
     DwRaw<T> graw[DW_PW], raw[3][NV];
+    uint32_t okm = 0u;                             // as in k_dw_fwd
 #pragma unroll
     for (int p = 0; p < DW_PW; ++p)
       dw_fetch<T>(rsy, (wo0 + p < a.Wo) ? (uint32_t)((((int64_t)(b * a.Ho + ho) * a.Wo + wo0 + p) * a.C + cg * 8) * (int)sizeof(T)) : DW_OOB, graw[p]);
@@ -268,6 +310,7 @@ __global__ __launch_bounds__(DW_T) void k_dw_wrw(const DwArgs a) {
         const int wi = wo0 * ST - a.pw + i;
         const bool ok = rok && (unsigned)wi < (unsigned)a.W;
         dw_fetch<T>(rsx, ok ? rbase + (uint32_t)(wi * a.C * (int)sizeof(T)) : DW_OOB, raw[r][i]);
+        if (PRO != DW_PRO_NONE) okm |= ok ? (1u << (r * NV + i)) : 0u;
       }
     }
     float g[DW_PW][8];
@@ -277,7 +320,10 @@ __global__ __launch_bounds__(DW_T) void k_dw_wrw(const DwArgs a) {
     for (int r = 0; r < 3; ++r) {
       float v[NV][8];
 #pragma unroll
-      for (int i = 0; i < NV; ++i) dw_unpack<T>(raw[r][i], v[i]);
+      for (int i = 0; i < NV; ++i) {
+        dw_unpack<T>(raw[r][i], v[i]);
+        if (PRO != DW_PRO_NONE) dw_prologue<T, PRO, ACT>(v[i], sc, sh, qa, qb, a.qk, ((okm >> (r * NV + i)) & 1u) != 0u);
+      }
 #pragma unroll
       for (int p = 0; p < DW_PW; ++p)
 #pragma unroll
@@ -337,6 +383,7 @@ static int dw_fill(DwArgs& a, int B, int H, int W, int C, int Ho, int Wo, int st
   if (B <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0 || ph < 0 || pw < 0 || ph > 2 || pw > 2) return (int)hipErrorInvalidValue;
   a.B = B; a.H = H; a.W = W; a.C = C; a.Ho = Ho; a.Wo = Wo; a.stride = stride; a.ph = ph; a.pw = pw;
   a.flip = 0;
+  a.ss = nullptr; a.slot = nullptr; a.qk = 0.f;
   a.strips_w = (Wo + DW_PW - 1) / DW_PW;
   a.total = (int64_t)B * Ho * a.strips_w;
   return 0;
@@ -437,4 +484,83 @@ extern "C" int pf_depthwise_wrw(const void* dY, const void* X, void* dW, int dty
   // thread per output over all G <= 1024 slabs (271 us per launch, 14.6 % of the C3 step); measured in round 5's first GPU call
   // (profiles/r05_first_call_ab.txt): C3 13 602 -> 16 140 images/s with this one, the old kernel is gone.
   return pf_wrw_reduce(slabs, grid, (int64_t)n, dW, dw_dtype, st);
+}
+
+// ---- the producer BatchNorm's normalise / activation / fake-quant in the prologue (MobileNet-v2: the 6x expansion) -------------
+// X is the RAW tensor in front of the BatchNorm; everything else as pf_depthwise_fwd / pf_depthwise_wrw (same grids, same statistics
+// and slab layouts, same reduction orders).  A null slot: no quantiser.
+template <typename T, int PRO, int ACT>
+static void dw_fwd_act_launch(const DwArgs& a, int grid, hipStream_t st) {
+  if (dw_general(a.C)) {
+    if (a.stride == 1) k_dw_fwd<T, 1, true, PRO, ACT><<<grid, DW_T, 0, st>>>(a);
+    else k_dw_fwd<T, 2, true, PRO, ACT><<<grid, DW_T, 0, st>>>(a);
+  } else if (a.stride == 1) k_dw_fwd<T, 1, false, PRO, ACT><<<grid, DW_T, 0, st>>>(a);
+  else k_dw_fwd<T, 2, false, PRO, ACT><<<grid, DW_T, 0, st>>>(a);
+}
+template <typename T, int PRO, int ACT>
+static void dw_wrw_act_launch(const DwArgs& a, int grid, hipStream_t st) {
+  if (dw_general(a.C)) {
+    if (a.stride == 1) k_dw_wrw<T, 1, true, PRO, ACT><<<grid, DW_T, 0, st>>>(a);
+    else k_dw_wrw<T, 2, true, PRO, ACT><<<grid, DW_T, 0, st>>>(a);
+  } else if (a.stride == 1) k_dw_wrw<T, 1, false, PRO, ACT><<<grid, DW_T, 0, st>>>(a);
+  else k_dw_wrw<T, 2, false, PRO, ACT><<<grid, DW_T, 0, st>>>(a);
+}
+
+// the prologue operands the two entries check alike
+static bool dw_act_ok(DwArgs& a, const float* scale_shift, int act, const uint32_t* slot, int bits, int dtype) {
+  if (scale_shift == nullptr || (dtype != PF_F32 && dtype != PF_BF16)) return false;
+  if (act != PF_ACT_NONE && act != PF_ACT_RELU6) return false;   // the producers of a depthwise layer: ReLU6 (MobileNet) or none; no ReLU forms are built
+  if (slot != nullptr && (bits < 1 || bits > 32 || ((uintptr_t)slot & 7u) != 0)) return false;
+  a.ss = scale_shift; a.slot = slot; a.qk = uq_k_of_bits(slot != nullptr ? bits : 8);
+  return true;
+}
+
+extern "C" int pf_depthwise_fwd_act(const void* X, const float* scale_shift, int act, const uint32_t* slot, int bits, const void* W,
+                                    void* Y, int dtype, float* partial, int B, int H, int Wd, int C, int k, int stride, int pad_h,
+                                    int pad_w, int Ho, int Wo, void* stream) {
+  if (!pf_depthwise_supported(C, k, stride)) return (int)hipErrorInvalidValue;
+  if (!pf_aligned16(X) || !pf_aligned16(Y) || X == nullptr || W == nullptr || Y == nullptr) return (int)hipErrorInvalidValue;
+  DwArgs a;
+  const int r = dw_fill(a, B, H, Wd, C, Ho, Wo, stride, pad_h, pad_w);
+  if (r) return r;
+  if (!dw_act_ok(a, scale_shift, act, slot, bits, dtype)) return (int)hipErrorInvalidValue;
+  a.x = X; a.w = W; a.y = Y; a.dy = nullptr; a.partial = partial;
+  if (!dw_set_bytes(a, dtype, (int64_t)B * H * Wd * C, 0)) return (int)hipErrorInvalidValue;
+  const int grid = dw_groups(a.total, C);
+  hipStream_t st = (hipStream_t)stream;
+  pf_with_bool(act == PF_ACT_RELU6, [&](auto R6) {
+    pf_with_bool(slot != nullptr, [&](auto Q) {
+      constexpr int PRO = decltype(Q)::value ? DW_PRO_QUANT : DW_PRO_AFFINE;
+      constexpr int ACT = decltype(R6)::value ? PF_ACT_RELU6 : PF_ACT_NONE;
+      if (dtype == PF_F32) dw_fwd_act_launch<float, PRO, ACT>(a, grid, st);
+      else dw_fwd_act_launch<bf16_t, PRO, ACT>(a, grid, st);
+    });
+  });
+  PF_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int pf_depthwise_wrw_act(const void* dY, const void* X, const float* scale_shift, int act, const uint32_t* slot, int bits,
+                                    void* dW, int dtype, int dw_dtype, float* slabs, int B, int H, int Wd, int C, int k, int stride,
+                                    int pad_h, int pad_w, int Ho, int Wo, void* stream) {
+  if (!pf_depthwise_supported(C, k, stride)) return (int)hipErrorInvalidValue;
+  if (!pf_aligned16(dY) || !pf_aligned16(X) || dY == nullptr || X == nullptr || dW == nullptr || slabs == nullptr)
+    return (int)hipErrorInvalidValue;
+  DwArgs a;
+  const int r = dw_fill(a, B, H, Wd, C, Ho, Wo, stride, pad_h, pad_w);
+  if (r) return r;
+  if (!dw_act_ok(a, scale_shift, act, slot, bits, dtype)) return (int)hipErrorInvalidValue;
+  a.x = X; a.w = nullptr; a.y = nullptr; a.dy = dY; a.partial = slabs;
+  if (!dw_set_bytes(a, dtype, (int64_t)B * H * Wd * C, (int64_t)B * Ho * Wo * C)) return (int)hipErrorInvalidValue;
+  const int grid = dw_groups(a.total, C);
+  hipStream_t st = (hipStream_t)stream;
+  pf_with_bool(act == PF_ACT_RELU6, [&](auto R6) {
+    pf_with_bool(slot != nullptr, [&](auto Q) {
+      constexpr int PRO = decltype(Q)::value ? DW_PRO_QUANT : DW_PRO_AFFINE;
+      constexpr int ACT = decltype(R6)::value ? PF_ACT_RELU6 : PF_ACT_NONE;
+      if (dtype == PF_F32) dw_wrw_act_launch<float, PRO, ACT>(a, grid, st);
+      else dw_wrw_act_launch<bf16_t, PRO, ACT>(a, grid, st);
+    });
+  });
+  return pf_wrw_reduce(slabs, grid, (int64_t)(C * 9), dW, dw_dtype, st);
 }

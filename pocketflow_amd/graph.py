@@ -796,7 +796,9 @@ class _BnAddActQuant(torch.autograd.Function):
     ctx.set_materialize_grads(False)               # an unused alias must arrive as None, not as a zeros tensor
     r = _nhwc(shortcut)
     # the BN (layer.bn) has no activation of its own and its output alone is never quantised: no slot for the finalize pass
-    x, rows, C, scale_shift = _bn_enter(ctx, x, gamma, beta, layer.bn, graph, training, None, stats, None, r)
+    # (without an activation no gate reads the shortcut in backward: it is not kept)
+    x, rows, C, scale_shift = _bn_enter(ctx, x, gamma, beta, layer.bn, graph, training, None, stats, None,
+                                        *((r,) if layer.act is not None else ()))
     ctx.act = layer.act
     quantize = bits is not None
     nbytes = float(x.numel() * x.element_size())
@@ -808,11 +810,15 @@ class _BnAddActQuant(torch.autograd.Function):
     if quantize:
       with region('uq_apply', 2 * nbytes):
         hip.uq_apply(u, u, slot, bits, None)         # in place; the activation is already applied
-    return u, u.view_as(u)
+    # TWO views of u, as _BnLazy and _Fork return of their input -- never u and a view of it: the caller hangs the second alias on the
+    # first (`_pf_skip`), and a view keeps its base alive from the C++ side, so `u._pf_skip = view of u` closes a cycle that not
+    # even the cyclic collector sees; every step's block outputs stayed allocated for good (found at batch 256: out of memory
+    # after some thirty steps of MobileNet-v2)
+    return u.view_as(u), u.view_as(u)
 
   @staticmethod
   def backward(ctx, dq, dskip):
-    x, scale_shift, mean_invstd, r = ctx.saved_tensors
+    x, scale_shift, mean_invstd = ctx.saved_tensors[:3]
     graph, rows, C = ctx.bn[1:4]
     if dq is None:
       dq, dskip = dskip, None
@@ -824,6 +830,21 @@ class _BnAddActQuant(torch.autograd.Function):
       return t if t.dtype == x.dtype else t.to(x.dtype)
     dq = as_x(dq)
     dskip = as_x(dskip) if dskip is not None else None
+    if ctx.act is None:
+      # no gate: g is the arriving gradient -- with ONE consumer as it stands (no launch; the BN takes its own statistics pass),
+      # with two their sum, formed by the gate pass's ADD form, which leaves the BN-backward sums as well.  That pass reads dq, the
+      # addend and x and writes g; its shortcut operand is never loaded without an activation (x stands in for the pointer).
+      if dskip is None:
+        dx, dgamma, dbeta = _bn_leave(ctx, dq)
+        return dx, dq, dgamma, dbeta, None, None, None, None, None, None
+      nblk = hip.bn_add_act_groups(rows, C)
+      partial = graph.scratch(nblk * 2 * C)
+      g = torch.empty_like(x)
+      with region('bn_add_act_bwd_gate', 4.0 * x.numel() * x.element_size()):
+        hip.bn_add_act_bwd_gate(dq, x, x, g, rows, C, scale_shift, mean_invstd, None, partial, addend=dskip)
+      dx, dgamma, dbeta = _bn_leave(ctx, g, pre=(partial, nblk))
+      return dx, g, dgamma, dbeta, None, None, None, None, None, None
+    r = ctx.saved_tensors[3]
     nblk = hip.bn_add_act_groups(rows, C)
     partial = graph.scratch(nblk * 2 * C)
     g = torch.empty_like(x)
@@ -1365,6 +1386,10 @@ CONVG_BF16_NARROW = os.environ.get('PF_CONVG_BF16_NARROW', '0') != '0'
 FOLD_EVAL_BN = os.environ.get('PF_FOLD_EVAL_BN', '1') != '0'
 OWN_CONV_GENERIC = os.environ.get('PF_OWN_CONV_GENERIC', '1') != '0'   # every other convolution / dense layer on pf_convg.hip (0: MIOpen / rocBLAS)
 DEPTHWISE_ANY_DEVICE = False     # tests: run the depthwise plumbing on CPU tensors (the HIP entry points are emulated there)
+# a depthwise layer applies its producer's BN + activation (+ fake-quant) in its own prologue instead of reading a materialised tensor
+# (pf_depthwise_fwd_act / pf_depthwise_wrw_act).  PF_DW_LAZY=1: every layer that can; 0: none; unset: where `dw_lazy_pays` says so
+DW_LAZY_ACTS = (None, 'Relu6')     # the activations pf_depthwise_*_act are built for (a ReLU producer materialises)
+DW_LAZY: Optional[bool] = {'0': False, '1': True}.get(os.environ.get('PF_DW_LAZY', ''))
 
 
 def _run_conv2d(x, w_krsc, stride, pad, want_stats, out_bn=None):
@@ -1832,6 +1857,33 @@ _INT8_PAYS_STATIC = frozenset([(1, 256, 64, 1)])
 _INT8_DW_PAYS_STATIC = frozenset([(32, 1), (64, 2), (128, 1), (128, 2), (256, 1), (256, 2), (512, 1), (512, 2), (1024, 1)])
 
 
+def dw_lazy_pays(C: int, stride: int, quantised: bool, dtype) -> bool:
+  """Should a depthwise 3x3 layer whose input is a LazyAct apply the producer's BN + activation (+ fake-quant) in its prologue
+  (pf_depthwise_fwd_act / pf_depthwise_wrw_act: True) or have it materialised first (pf_bn_act_quant_apply + the plain kernels: False)?
+
+  profiles/dw_lazy_layers.txt (tools/gpu/dw_lazy_layers.py: the ten depthwise shapes of MobileNet-v2 1.0 at B = 256 / 224 x 224, bf16,
+  ReLU6, with and without an 8-bit quantiser, medians of three alternating rounds in one build): the fused launch LOSES on every row.
+  Forward, no quantiser: apply + pf_depthwise_fwd over pf_depthwise_fwd_act 0.46 - 0.90 (the 0.90 is the 96-channel stride-2 layer at
+  112 x 112: 430 against 476 us); backward-filter 0.52 - 0.97; with the quantiser 0.31 - 0.57.  One training step of a layer (the apply
+  pass runs ONCE for both directions): 0.44 - 0.65 without, 0.25 - 0.39 with the quantiser; all 17 layers 3.22 against 6.47 ms and
+  3.56 against 11.87 ms, spreads at most 2.8 us.  The parent kernels are not HBM-bound (0.2 - 0.6 of their byte bound): they are
+  bound by issue and latency at two wavefronts per SIMD, and the prologue -- fmaf, clamp, the rounding to bf16 and the select, run
+  once per output ROW that reads an element, three times at stride 1, plus two correctly rounded divisions with a quantiser -- costs
+  more instructions than the multiply-adds it feeds and takes the kernels to one wavefront per SIMD (profiles/dw_lazy_registers.txt).
+  So no row pays and every layer materialises by default; PF_DW_LAZY=1 runs the route (bit-identical results) for A/B runs.  float32
+  has not been timed."""
+  return dtype == torch.bfloat16 and (C, stride, bool(quantised)) in _DW_LAZY_PAYS
+
+
+# (C, stride, quantised) of the rows of profiles/dw_lazy_layers.txt on which the fused pair of launches (forward + backward-filter) won
+_DW_LAZY_PAYS = frozenset([])
+
+
+def dw_lazy_on(C: int, stride: int, quantised: bool, dtype) -> bool:
+  """The switch of the lazy depthwise route for one layer: PF_DW_LAZY forces it either way, otherwise the measured table decides."""
+  return dw_lazy_pays(C, stride, quantised, dtype) if DW_LAZY is None else DW_LAZY
+
+
 # What Conv2D._route / DepthwiseConv2D._route decide for one call, a plain tuple (it is built once per layer call):
 #   (name, x, pad, out_hw, out_bn, geom)
 # `name`: the route; the layer launches it in `_call_<name>`.  `x`: the prepared input -- materialised where the route reads a tensor,
@@ -2178,6 +2230,65 @@ class _Depthwise(torch.autograd.Function):
     return dx, dw, None, None, None, None, None, None, None, None, None
 
 
+def _run_depthwise_act(x, lazy, w, stride, ph, pw, Ho, Wo, want_stats):
+  """_run_depthwise on the un-materialised output of a BatchNormAct: x is the RAW tensor, the kernel applies `lazy` on the fly."""
+  B, C, H, W = x.shape
+  k = w.shape[2]
+  y = torch.empty((B, C, Ho, Wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+  partial = None
+  if want_stats:
+    G = hip.depthwise_groups(B, Ho, Wo, C)
+    partial = torch.empty((G, 4, C), dtype=torch.float32, device=x.device)
+  quant = lazy.bits is not None
+  with region('depthwise_fwd_act', float((x.numel() + y.numel()) * x.element_size())):
+    hip.depthwise_fwd_act(x, lazy.scale_shift, lazy.act, lazy.slot if quant else None, lazy.bits if quant else 8,
+                          w.detach().reshape(C, k, k), y, B, H, W, C, k, stride, ph, pw, Ho, Wo, partial=partial)
+  if want_stats:
+    y._pf_stats = (partial, G)
+  return y
+
+
+class _DepthwiseAct(torch.autograd.Function):
+  """_Depthwise reading a LazyAct: y = depthwise_conv3x3(Q(x), W), Q the producer BN's normalise / act / fake-quant, applied in the
+  prologue of pf_depthwise_fwd_act and again in pf_depthwise_wrw_act (the raw x and Q's operands are what is saved: the activated
+  tensor never exists).  Backward-data never reads x: it is pf_depthwise_bwd_data as it stands, and its result is the gradient with
+  respect to Q(x), which flows into x's node (_BnLazy) as it does from the fused 1x1 convolutions."""
+
+  @staticmethod
+  def forward(ctx, x, w, lazy, stride, ph, pw, Ho, Wo, want_stats, graph, w_var, box):
+    y = _run_depthwise_act(x, lazy, w, stride, ph, pw, Ho, Wo, want_stats)
+    ctx.save_for_backward(x, w)
+    ctx.meta = (lazy, stride, ph, pw, Ho, Wo, graph, w_var)
+    box.append(getattr(y, '_pf_stats', None))
+    return y
+
+  @staticmethod
+  def backward(ctx, dy):
+    x, w = ctx.saved_tensors
+    lazy, stride, ph, pw, Ho, Wo, graph, w_var = ctx.meta
+    dy = _nhwc(dy)
+    if dy.dtype != x.dtype:
+      dy = dy.to(x.dtype)
+    B, C, H, W = x.shape
+    k = w.shape[2]
+    dx = dw = None
+    if ctx.needs_input_grad[1]:
+      G = hip.depthwise_groups(B, Ho, Wo, C)
+      quant = lazy.bits is not None
+      ss = lazy.scale_shift
+
+      def wrw(dwk, scratch):                       # dwk: [C][k][k][1] memory = [C][k][k]
+        hip.depthwise_wrw_act(dy, x, ss, lazy.act, lazy.slot if quant else None, lazy.bits if quant else 8, dwk,
+                              scratch((G + 32) * C * k * k), B, H, W, C, k, stride, ph, pw, Ho, Wo)
+      # (the producer BN's constants belong to ITS node, which runs right behind this one: kept referenced until the join)
+      dw = _filter_grad(graph, w, w_var, (dy, x, ss, lazy), 'depthwise_wrw_act', float((x.numel() + dy.numel()) * x.element_size()), wrw)
+    if ctx.needs_input_grad[0]:
+      dx = torch.empty_like(x)
+      with region('depthwise_bwd_data', float((x.numel() + dy.numel()) * x.element_size())):
+        hip.depthwise_bwd_data(dy, w.detach().reshape(C, k, k), dx, B, H, W, C, k, stride, ph, pw, Ho, Wo)
+    return (dx, dw) + (None,) * 10
+
+
 class DepthwiseConv2D:
   """slim.separable_conv2d(num_outputs=None, depth_multiplier=1): DepthwiseConv2dNative."""
 
@@ -2211,7 +2322,7 @@ class DepthwiseConv2D:
     (pf_dw_i8_fwd_q), any other route ignores the hint."""
     r = self._route(x, out_bn)
     name = r[ROUTE_NAME]
-    if name == 'own':                            # the ONE place a DepthwiseConv2D counts itself on its producer (BnSums.add_consumer)
+    if name in ('own', 'lazy'):                  # the ONE place a DepthwiseConv2D counts itself on its producer (BnSums.add_consumer)
       bn_sums = getattr(r[ROUTE_X], '_pf_bn', None)
       if bn_sums is not None:
         bn_sums.add_consumer(fuses=False)
@@ -2220,7 +2331,9 @@ class DepthwiseConv2D:
   def _route(self, x, out_bn) -> tuple:
     """As Conv2D._route, in this order: a packed layer that no tap takes RAISES under gradients, then `int8` for the CodesAct it takes
     (takes_codes; `out_bn` narrowed to a requantising one); every other input is materialised -- a CodesAct too: the fake-quantised
-    tensor of the apply pass, as without int8 --; `tap`; `own` (pf_depthwise.hip); `library`."""
+    tensor of the apply pass, as without int8 --; `tap`; `own` (pf_depthwise.hip); `library`.  In front of the materialisation:
+    `lazy`, a LazyAct (never a CodesAct) this layer reads raw, with the producer's BN + activation + fake-quant in the prologue of
+    pf_depthwise_fwd_act / pf_depthwise_wrw_act (takes_lazy: what `own` asks, no taps, the switch)."""
     g, w = self.graph, self.kernel.tensor
     if self.int8 is not None and g.taps is None:
       if _wants_grad(w, x.x if isinstance(x, LazyAct) else x):
@@ -2229,6 +2342,10 @@ class DepthwiseConv2D:
       if isinstance(x, CodesAct) and self.takes_codes(x.x.shape, x.x.is_cuda):
         ph, pw, out_hw = self._geometry(x.x.shape)
         return 'int8', x, (ph[0], pw[0]), out_hw, (out_bn if (out_bn is not None and out_bn.requantises()) else None), None
+    if (isinstance(x, LazyAct) and not isinstance(x, CodesAct) and x.act in DW_LAZY_ACTS
+        and self.takes_lazy(x.x, x.bits is not None)):
+      ph, pw, out_hw = self._geometry(x.x.shape)
+      return 'lazy', x, (ph[0], pw[0]), out_hw, None, None
     x = materialize(x)
     if g.taps is not None:
       return 'tap', x, None, None, None, None
@@ -2248,6 +2365,23 @@ class DepthwiseConv2D:
     if _wants_grad(w, x):
       return _apply_with_stats(_Depthwise, x, w, self.stride, ph, pw, Ho, Wo, want_stats, self.graph, self.kernel)
     return _run_depthwise(_nhwc(x), w, self.stride, ph, pw, Ho, Wo, want_stats)
+
+  def takes_lazy(self, t, quantised: bool) -> bool:
+    """This layer will read the RAW tensor `t` behind a LazyAct and apply the producer itself: everything the `own` route asks, no
+    tap, no packed kernel, a library (or test double) with the entry points, and the switch (dw_lazy_on)."""
+    w = self.kernel.tensor
+    return (OWN_DEPTHWISE and self.graph.taps is None and self.int8 is None and isinstance(t, torch.Tensor)
+            and (t.is_cuda or DEPTHWISE_ANY_DEVICE) and t.dim() == 4 and t.dtype in (torch.float32, torch.bfloat16)
+            and w.dtype == t.dtype and t.shape[1] == self.channels and hasattr(hip, 'depthwise_fwd_act')
+            and hasattr(hip, 'depthwise_wrw_act') and hip.depthwise_supported(self.channels, self.k, self.stride)
+            and dw_lazy_on(self.channels, self.stride, quantised, t.dtype))
+
+  def _call_lazy(self, r, want_stats):
+    _, lazy, (ph, pw), (Ho, Wo), _, _ = r
+    w, x = self.kernel.tensor, lazy.x
+    if _wants_grad(w, x):
+      return _apply_with_stats(_DepthwiseAct, x, w, lazy, self.stride, ph, pw, Ho, Wo, want_stats, self.graph, self.kernel)
+    return _run_depthwise_act(x, lazy, w, self.stride, ph, pw, Ho, Wo, want_stats)
 
   def _call_library(self, r, want_stats):
     _, x, pad, _, _, _ = r
@@ -2338,13 +2472,15 @@ class BatchNormAct:
   def __init__(self, graph: Graph, name: str, channels: int, act: Optional[str], momentum: float, eps: float,
                l2: bool = False, act_name: Optional[str] = None, names=('gamma', 'beta', 'moving_mean',
                                                                        'moving_variance'), lazy_ok: bool = False,
-               codes_ok: Optional[bool] = None):
+               codes_ok: Optional[bool] = None, beta_first: bool = False):
     self.graph, self.act, self.momentum, self.eps, self.C = graph, act, momentum, eps, channels
     self.lazy_ok = lazy_ok                    # every consumer is a Conv2D: the output may stay un-materialised
     # every consumer is a Conv2D or a DepthwiseConv2D, for the int8 inference route alone (CodesAct): also set where the training path
     # keeps the output materialised (a BN in front of a 3x3 or a depthwise convolution)
     self.codes_ok = lazy_ok if codes_ok is None else codes_ok
     st = graph.store
+    if beta_first:                            # slim.batch_norm creates beta in front of gamma (creation order = checkpoint order)
+      self.beta = st.add(name + '/' + names[1], (channels,), 'bn_beta', True, l2, constant_init((channels,), 0.0))
     self.gamma = st.add(name + '/' + names[0], (channels,), 'bn_gamma', True, l2, constant_init((channels,), 1.0))
     self.beta = st.add(name + '/' + names[1], (channels,), 'bn_beta', True, l2, constant_init((channels,), 0.0))
     self.moving_mean = st.add(name + '/' + names[2], (channels,), 'bn_mean', False, False,
@@ -2382,6 +2518,13 @@ class BatchNormAct:
       if bits is not None:
         raise NotImplementedError('inference-mode BN with gradients and activation quantisation (no learner needs it)')
     return BN_EVAL_GRAD, None, None
+
+  def _feeds_lazy_depthwise(self, x) -> bool:
+    """The ONE consumer the network code named is a depthwise layer that will read this layer's raw input and apply the layer itself
+    (DepthwiseConv2D.takes_lazy): the output may stay un-materialised in float32 too, where no 1x1 kernel has a prologue."""
+    c = self.consumer
+    return (isinstance(c, DepthwiseConv2D) and x.dim() == 4 and self.act in DW_LAZY_ACTS
+            and c.takes_lazy(x, self.op is not None and self.op.bits is not None))
 
   def _static(self) -> bool:
     """Inference on a graph with fixed activation ranges, this layer quantising: the clamping kernels, no statistics pass."""
@@ -2426,7 +2569,7 @@ class BatchNormAct:
       y = x
     else:
       mode, bits, slot = self._mode(x)
-      lazy = self.lazy_ok and g.fuse_conv1x1 and isinstance(x, torch.Tensor) and fusable_tensor(x)
+      lazy = self.lazy_ok and isinstance(x, torch.Tensor) and ((g.fuse_conv1x1 and fusable_tensor(x)) or self._feeds_lazy_depthwise(x))
       if mode == BN_TRAIN:
         stats = getattr(x, '_pf_stats', None)    # left by the fused convolution that produced x
         rec = BnSums()                           # lets a single consuming convolution fuse the BN-backward sums
@@ -2523,19 +2666,23 @@ class BatchNormAddAct:
   C % 8 != 0 -- runs the composition of the v1 basic block: BatchNormAct, torch add, Activation.
   Not covered by the int8 / fixed-range loaders: such a graph is refused with a ValueError that names this layer."""
 
-  def __init__(self, graph: Graph, name: str, channels: int, act: str, momentum: float, eps: float, act_name: str,
-               l2: bool = False):
-    if act not in ('Relu',):
+  def __init__(self, graph: Graph, name: str, channels: int, act: Optional[str], momentum: float, eps: float,
+               act_name: Optional[str] = None, l2: bool = False, names=('gamma', 'beta', 'moving_mean', 'moving_variance'),
+               beta_first: bool = False):
+    if act not in ('Relu', None):
       raise ValueError('%s: the join kernels apply Relu (or nothing), not %s' % (name, act))
     self.graph, self.name, self.act, self.C = graph, name, act, channels
-    self.bn = BatchNormAct(graph, name, channels, None, momentum, eps, l2=l2)
-    self.relu = Activation(graph, act_name, act)   # registers the op; also the activation of the composition
-    self.op = self.relu.op
+    self.bn = BatchNormAct(graph, name, channels, None, momentum, eps, l2=l2, names=names, beta_first=beta_first)
+    # `act` None (the linear bottleneck of MobileNet-v2): no activation op, hence no slot and no quantiser behind the sum
+    self.relu = Activation(graph, act_name, act) if act is not None else None   # registers the op; also the activation of the composition
+    self.op = self.relu.op if self.relu is not None else None
     graph.join_layers.append(self)
 
   def refusal(self) -> str:
     return ('%s/%s: the BN + shortcut + %s joins of the ResNet-v1 blocks are not covered by the int8 / static-range loaders'
-            % (self.graph.scope, self.name, self.act))
+            % (self.graph.scope, self.name, self.act) if self.act is not None else
+            '%s/%s: the BN + shortcut joins of the MobileNet-v2 blocks are not covered by the int8 / static-range loaders'
+            % (self.graph.scope, self.name))
 
   def takes(self, x, shortcut) -> bool:
     return (bn_join_tensor_ok(x) and isinstance(shortcut, torch.Tensor) and shortcut.dtype == x.dtype
@@ -2547,7 +2694,8 @@ class BatchNormAddAct:
       raise ValueError(self.refusal())
     x, shortcut = materialize(x), materialize(shortcut)
     if not self.takes(x, shortcut):
-      return self.relu(self.bn(x) + shortcut)
+      y = self.bn(x) + shortcut
+      return self.relu(y) if self.relu is not None else y
     mode, bits, slot = self.bn._mode(x, shortcut, op=self.op)
     if mode != BN_EVAL:
       u, skip = _BnAddActQuant.apply(x, shortcut, self.bn.gamma.tensor, self.bn.beta.tensor, self, g, mode == BN_TRAIN, slot, bits,

@@ -62,6 +62,7 @@ SYMBOLS = [
     'pf_bn_add_act_groups', 'pf_bn_add_act_fwd', 'pf_bn_add_act_bwd_gate', 'pf_bn_add_act_bwd_gate_add',
     'pf_bn_vector_ok',
     'pf_conv1x1_bwd_apply_plan', 'pf_conv1x1_bwd_data_bnsums', 'pf_conv1x1_bwd_data_bnapply',
+    'pf_depthwise_fwd_act', 'pf_depthwise_wrw_act',
 ]
 
 
@@ -720,6 +721,28 @@ def depthwise_wrw(dY, X, dW, slabs, B: int, H: int, Wd: int, C: int, k: int, str
   _check(_lib.pf_depthwise_wrw(_ptr(dY), _ptr(X), _ptr(dW), c_int(dtype_code(X)), c_int(dtype_code(dW)), _ptr(slabs), c_int(B),
                                c_int(H), c_int(Wd), c_int(C), c_int(k), c_int(stride), c_int(pad_h), c_int(pad_w), c_int(Ho),
                                c_int(Wo), _stream()), 'pf_depthwise_wrw')
+
+
+def depthwise_fwd_act(X, scale_shift, act, slot, bits: int, W, Y, B: int, H: int, Wd: int, C: int, k: int, stride: int, pad_h: int,
+                      pad_w: int, Ho: int, Wo: int, partial=None) -> None:
+  """depthwise_fwd of fake_quant(act(scale * X + shift)) rounded to X's dtype, X the RAW tensor in front of the BatchNorm (the prologue
+  of the fused 1x1 kernels: scale_shift float32 [2][C], `slot` None = no quantiser); taps outside the image contribute 0."""
+  _dev(X)
+  _check(_lib.pf_depthwise_fwd_act(_ptr(X), _ptr(scale_shift), c_int(ACT_CODES[act]), _ptr(slot), c_int(bits), _ptr(W), _ptr(Y),
+                                   c_int(dtype_code(X)), _ptr(partial), c_int(B), c_int(H), c_int(Wd), c_int(C), c_int(k),
+                                   c_int(stride), c_int(pad_h), c_int(pad_w), c_int(Ho), c_int(Wo), _stream()), 'pf_depthwise_fwd_act')
+
+
+def depthwise_wrw_act(dY, X, scale_shift, act, slot, bits: int, dW, slabs, B: int, H: int, Wd: int, C: int, k: int, stride: int,
+                      pad_h: int, pad_w: int, Ho: int, Wo: int) -> None:
+  """depthwise_wrw with the same prologue on X; dW and slabs as there."""
+  _dev(X)
+  if slabs.dtype != torch.float32 or slabs.numel() < (depthwise_groups(B, Ho, Wo, C) + 32) * C * k * k:
+    raise TypeError('depthwise_wrw_act: float32 workspace of (groups + 32) * C * k * k elements')
+  _check(_lib.pf_depthwise_wrw_act(_ptr(dY), _ptr(X), _ptr(scale_shift), c_int(ACT_CODES[act]), _ptr(slot), c_int(bits), _ptr(dW),
+                                   c_int(dtype_code(X)), c_int(dtype_code(dW)), _ptr(slabs), c_int(B), c_int(H), c_int(Wd), c_int(C),
+                                   c_int(k), c_int(stride), c_int(pad_h), c_int(pad_w), c_int(Ho), c_int(Wo), _stream()),
+         'pf_depthwise_wrw_act')
 
 
 def conv2d_bwd_data_strided_stats_groups(B: int, H: int, Wd: int, C: int, stride: int) -> int:

@@ -1,7 +1,8 @@
-"""Model helper for MobileNet-v1 on ILSVRC-12 (reference nets/mobilenet_at_ilsvrc12.py:32-148):
+"""Model helper for MobileNet-v1 / -v2 on ILSVRC-12 (reference nets/mobilenet_at_ilsvrc12.py:32-148):
 loss = CE + loss_w_dcy * L2 over every trainable whose name lacks 'batch_normalization' -- which for
 slim's `BatchNorm/*` names means ALL of them, BN gamma/beta and depthwise kernels included
-(SURVEY A.6); 100 epochs, LR x0.1 at 30/60/80/90, batch_size_norm 96, lrn_rate_init 0.045."""
+(SURVEY A.6); v1: 100 epochs, LR x0.1 at 30/60/80/90; v2: 412 epochs, LR x 0.98^2.5 every 2.5 epochs (:127-132);
+batch_size_norm 96, lrn_rate_init 0.045."""
 import torch
 
 from pocketflow_amd import losses
@@ -10,6 +11,8 @@ from pocketflow_amd.flags import FLAGS, flags
 from pocketflow_amd.graph import get_default_graph
 from pocketflow_amd.nets.abstract_model_helper import AbstractModelHelper
 from pocketflow_amd.utils.external import mobilenet_v1 as MobileNetV1
+from pocketflow_amd.utils.external import mobilenet_v2 as MobileNetV2
+from pocketflow_amd.utils.lrn_rate_utils import setup_lrn_rate_exponential_decay
 from pocketflow_amd.utils.lrn_rate_utils import setup_lrn_rate_piecewise_constant
 from pocketflow_amd.utils.multi_gpu_wrapper import MultiGpuWrapper as mgw
 
@@ -23,13 +26,13 @@ flags.DEFINE_float('loss_w_dcy', 4e-5, 'weight decaying loss\'s coefficient')
 
 
 def forward_fn(inputs, is_train):
-  if FLAGS.mobilenet_version != 1:
-    raise ValueError('invalid MobileNet version: {} (only v1 is on the hot path)'.format(FLAGS.mobilenet_version))
+  if FLAGS.mobilenet_version not in (1, 2):
+    raise ValueError('invalid MobileNet version: {}'.format(FLAGS.mobilenet_version))
   graph = get_default_graph()
   net = graph.nets.get('mobilenet')
   if net is None:
-    net = graph.nets['mobilenet'] = MobileNetV1.MobilenetV1(
-        graph, num_classes=FLAGS.nb_classes, depth_multiplier=FLAGS.mobilenet_depth_mult)
+    net_cls = MobileNetV1.MobilenetV1 if FLAGS.mobilenet_version == 1 else MobileNetV2.MobilenetV2
+    net = graph.nets['mobilenet'] = net_cls(graph, num_classes=FLAGS.nb_classes, depth_multiplier=FLAGS.mobilenet_depth_mult)
   if inputs.device.type == 'meta':
     return torch.empty((inputs.shape[0], FLAGS.nb_classes), device='meta')
   return net(inputs, is_train)
@@ -65,11 +68,19 @@ class ModelHelper(AbstractModelHelper):
     return loss, metrics
 
   def setup_lrn_rate(self, global_step):
-    nb_epochs = 100
-    idxs_epoch = [30, 60, 80, 90]
-    decay_rates = [1.0, 0.1, 0.01, 0.001, 0.0001]
     batch_size = FLAGS.batch_size * (1 if not FLAGS.enbl_multi_gpu else mgw.size())
-    lrn_rate = setup_lrn_rate_piecewise_constant(global_step, batch_size, idxs_epoch, decay_rates)
+    if FLAGS.mobilenet_version == 1:
+      nb_epochs = 100
+      idxs_epoch = [30, 60, 80, 90]
+      decay_rates = [1.0, 0.1, 0.01, 0.001, 0.0001]
+      lrn_rate = setup_lrn_rate_piecewise_constant(global_step, batch_size, idxs_epoch, decay_rates)
+    elif FLAGS.mobilenet_version == 2:
+      nb_epochs = 412
+      epoch_step = 2.5
+      decay_rate = 0.98 ** epoch_step
+      lrn_rate = setup_lrn_rate_exponential_decay(global_step, batch_size, epoch_step, decay_rate)
+    else:
+      raise ValueError('invalid MobileNet version: {}'.format(FLAGS.mobilenet_version))
     nb_iters = int(FLAGS.nb_smpls_train * nb_epochs * FLAGS.nb_epochs_rat / batch_size)
     return lrn_rate, nb_iters
 
