@@ -25,7 +25,7 @@
 // Otherwise (GEN = true; 24, 48, 96 ... channels) the 256 - SPB * (C / 8) left-over lanes have sl == SPB: they take no strip -- it
 // would be the first strip of the NEXT workgroup, computed and counted in the statistics twice --, write nothing to LDS, whose
 // reductions read sl < SPB only, and reach every barrier.  255 of 256 lanes work at C = 24, 252 at 96, 240 at 384, 192 at 768.
-#include "pf_common.h"
+#include "pf_buffer.h"
 
 #define DW_T 256
 #define DW_PW 4
@@ -35,31 +35,17 @@
 // `if (inside) load8(...) else zeros` per vector: hipcc turns that into a branch around every load with `s_waitcnt vmcnt(0)` behind
 // it (cdna_hip_programming.md, "per-element register-or-load select"), i.e. 18 DEPENDENT round trips to L2 / HBM per strip of four
 // output pixels -- the kernels ran at 2.5-2.9x their HBM floor (profiles/r05_depthwise_layers_before.txt), latency-bound at two
-// wavefronts per SIMD.  Now the 18 (+ 4) loads of a strip are issued back to back and waited for once.
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __amdgpu_buffer_rsrc_t dw_rsrc_t;
-#define DW_MAKE_RSRC(p, bytes) __builtin_amdgcn_make_buffer_rsrc((void*)(p), (short)0, (int)(bytes), 0x00020000)
-typedef uint32_t dw_u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint4 dw_load16(dw_rsrc_t rs, uint32_t off) {
-  const dw_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0);
-  return make_uint4(v[0], v[1], v[2], v[3]);
-}
-#else
-typedef int dw_rsrc_t;
-#define DW_MAKE_RSRC(p, bytes) 0
-__device__ __forceinline__ uint4 dw_load16(dw_rsrc_t, uint32_t) { return make_uint4(0, 0, 0, 0); }
-#endif
-#define DW_OOB 0x80000000u
+// wavefronts per SIMD.  Now the 18 (+ 4) loads of a strip are issued back to back and waited for once.  (pf_buffer.h)
 
 // eight consecutive channels of one pixel as they sit in memory: one 16-byte vector (bf16) or two (float32)
 template <typename T> struct DwRaw;
 template <> struct DwRaw<bf16_t> { uint4 a; };
 template <> struct DwRaw<float> { uint4 a, b; };
-template <typename T> __device__ __forceinline__ void dw_fetch(dw_rsrc_t rs, uint32_t off, DwRaw<T>& r);
-template <> __device__ __forceinline__ void dw_fetch<bf16_t>(dw_rsrc_t rs, uint32_t off, DwRaw<bf16_t>& r) { r.a = dw_load16(rs, off); }
-template <> __device__ __forceinline__ void dw_fetch<float>(dw_rsrc_t rs, uint32_t off, DwRaw<float>& r) {
-  r.a = dw_load16(rs, off);
-  r.b = dw_load16(rs, off == DW_OOB ? DW_OOB : off + 16u);
+template <typename T> __device__ __forceinline__ void dw_fetch(pf_rsrc_t rs, uint32_t off, DwRaw<T>& r);
+template <> __device__ __forceinline__ void dw_fetch<bf16_t>(pf_rsrc_t rs, uint32_t off, DwRaw<bf16_t>& r) { r.a = pf_buffer_load16(rs, off); }
+template <> __device__ __forceinline__ void dw_fetch<float>(pf_rsrc_t rs, uint32_t off, DwRaw<float>& r) {
+  r.a = pf_buffer_load16(rs, off);
+  r.b = pf_buffer_load16(rs, off == PF_BUFFER_OOB ? PF_BUFFER_OOB : off + 16u);
 }
 template <typename T> __device__ __forceinline__ void dw_unpack(const DwRaw<T>& r, float* o);
 template <> __device__ __forceinline__ void dw_unpack<bf16_t>(const DwRaw<bf16_t>& r, float* o) {
@@ -121,7 +107,7 @@ __global__ __launch_bounds__(DW_T) void k_dw_fwd(const DwArgs a) {
   const int C8 = a.C >> 3, SPB = DW_T / C8;
   const int cg = threadIdx.x % C8, sl = threadIdx.x / C8;
   const bool idle = GEN && sl >= SPB;
-  const dw_rsrc_t rsx = DW_MAKE_RSRC(a.x, a.x_bytes);
+  const pf_rsrc_t rsx = PF_MAKE_RSRC(a.x, a.x_bytes);
   const T* __restrict__ w = (const T*)a.w;
   T* __restrict__ y = (T*)a.y;
   float wr[9][8];
@@ -161,7 +147,7 @@ __global__ __launch_bounds__(DW_T) void k_dw_fwd(const DwArgs a) {
       for (int i = 0; i < NV; ++i) {
         const int wi = wo0 * ST - a.pw + i;
         const bool ok = rok && (unsigned)wi < (unsigned)a.W;
-        dw_fetch<T>(rsx, ok ? rbase + (uint32_t)(wi * a.C * (int)sizeof(T)) : DW_OOB, raw[r][i]);
+        dw_fetch<T>(rsx, ok ? rbase + (uint32_t)(wi * a.C * (int)sizeof(T)) : PF_BUFFER_OOB, raw[r][i]);
         if (PRO != DW_PRO_NONE) okm |= ok ? (1u << (r * NV + i)) : 0u;
       }
     }
@@ -226,7 +212,7 @@ __global__ __launch_bounds__(DW_T) void k_dw_bwd_data(const DwArgs a) {
   const int C8 = a.C >> 3, SPB = DW_T / C8;
   const int cg = threadIdx.x % C8, sl = threadIdx.x / C8;
   const bool idle = GEN && sl >= SPB;
-  const dw_rsrc_t rsy = DW_MAKE_RSRC(a.x, a.x_bytes);
+  const pf_rsrc_t rsy = PF_MAKE_RSRC(a.x, a.x_bytes);
   const T* __restrict__ w = (const T*)a.w;
   T* __restrict__ dx = (T*)a.y;
   float wr[9][8];
@@ -251,7 +237,7 @@ __global__ __launch_bounds__(DW_T) void k_dw_bwd_data(const DwArgs a) {
         const int tw = wi + a.pw - s;
         const int wo = tw / a.stride;
         const bool ok = rok && tw >= 0 && (tw - wo * a.stride) == 0 && wo < a.Wo;
-        dw_fetch<T>(rsy, ok ? (uint32_t)((((int64_t)(b * a.Ho + ho) * a.Wo + wo) * a.C + cg * 8) * (int)sizeof(T)) : DW_OOB, raw[r * 3 + s]);
+        dw_fetch<T>(rsy, ok ? (uint32_t)((((int64_t)(b * a.Ho + ho) * a.Wo + wo) * a.C + cg * 8) * (int)sizeof(T)) : PF_BUFFER_OOB, raw[r * 3 + s]);
       }
     }
     float acc[8];
@@ -275,8 +261,8 @@ __global__ __launch_bounds__(DW_T) void k_dw_wrw(const DwArgs a) {
   const int C8 = a.C >> 3, SPB = DW_T / C8;
   const int cg = threadIdx.x % C8, sl = threadIdx.x / C8;
   const bool idle = GEN && sl >= SPB;
-  const dw_rsrc_t rsx = DW_MAKE_RSRC(a.x, a.x_bytes);
-  const dw_rsrc_t rsy = DW_MAKE_RSRC(a.dy, a.dy_bytes);
+  const pf_rsrc_t rsx = PF_MAKE_RSRC(a.x, a.x_bytes);
+  const pf_rsrc_t rsy = PF_MAKE_RSRC(a.dy, a.dy_bytes);
   float acc[9][8];
 #pragma unroll
   for (int t = 0; t < 9; ++t)
@@ -299,7 +285,7 @@ __global__ __launch_bounds__(DW_T) void k_dw_wrw(const DwArgs a) {
     uint32_t okm = 0u;                             // as in k_dw_fwd
 #pragma unroll
     for (int p = 0; p < DW_PW; ++p)
-      dw_fetch<T>(rsy, (wo0 + p < a.Wo) ? (uint32_t)((((int64_t)(b * a.Ho + ho) * a.Wo + wo0 + p) * a.C + cg * 8) * (int)sizeof(T)) : DW_OOB, graw[p]);
+      dw_fetch<T>(rsy, (wo0 + p < a.Wo) ? (uint32_t)((((int64_t)(b * a.Ho + ho) * a.Wo + wo0 + p) * a.C + cg * 8) * (int)sizeof(T)) : PF_BUFFER_OOB, graw[p]);
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
       const int hi = ho * ST + r - a.ph;
@@ -309,7 +295,7 @@ __global__ __launch_bounds__(DW_T) void k_dw_wrw(const DwArgs a) {
       for (int i = 0; i < NV; ++i) {
         const int wi = wo0 * ST - a.pw + i;
         const bool ok = rok && (unsigned)wi < (unsigned)a.W;
-        dw_fetch<T>(rsx, ok ? rbase + (uint32_t)(wi * a.C * (int)sizeof(T)) : DW_OOB, raw[r][i]);
+        dw_fetch<T>(rsx, ok ? rbase + (uint32_t)(wi * a.C * (int)sizeof(T)) : PF_BUFFER_OOB, raw[r][i]);
         if (PRO != DW_PRO_NONE) okm |= ok ? (1u << (r * NV + i)) : 0u;
       }
     }
@@ -389,178 +375,128 @@ static int dw_fill(DwArgs& a, int B, int H, int W, int C, int Ho, int Wo, int st
   return 0;
 }
 
-extern "C" int pf_depthwise_fwd(const void* X, const void* W, void* Y, int dtype, float* partial, int B, int H, int Wd, int C,
-                                int k, int stride, int pad_h, int pad_w, int Ho, int Wo, void* stream) {
-  if (!pf_depthwise_supported(C, k, stride)) return (int)hipErrorInvalidValue;
-  if (!pf_aligned16(X) || !pf_aligned16(Y) || X == nullptr || W == nullptr || Y == nullptr) return (int)hipErrorInvalidValue;
-  DwArgs a;
-  const int r = dw_fill(a, B, H, Wd, C, Ho, Wo, stride, pad_h, pad_w);
+// the prologue operands of pf_depthwise_fwd_act / pf_depthwise_wrw_act (a null slot: no quantiser); the plain entries pass none
+struct DwPro { const float* scale_shift; int act; const uint32_t* slot; int bits; };
+static bool dw_act_ok(DwArgs& a, const DwPro& p) {
+  if (p.scale_shift == nullptr) return false;
+  if (p.act != PF_ACT_NONE && p.act != PF_ACT_RELU6) return false;   // the producers of a depthwise layer: ReLU6 (MobileNet) or none; no ReLU forms are built
+  if (p.slot != nullptr && (p.bits < 1 || p.bits > 32 || ((uintptr_t)p.slot & 7u) != 0)) return false;
+  a.ss = p.scale_shift; a.slot = p.slot; a.qk = uq_k_of_bits(p.slot != nullptr ? p.bits : 8);
+  return true;
+}
+
+enum DwDir { DW_FWD, DW_BWD_DATA, DW_WRW };
+struct DwDims { int B, H, Wd, C, k, stride, pad_h, pad_w, Ho, Wo; };   // the forward geometry, as every entry receives it
+
+// Everything an entry does in front of its launch.  `in` is the tensor behind a.x (forward and backward-filter: X, backward-data: dY),
+// `other` W (backward-filter: dY), `out` Y / dX / dW, `partial` the statistics (or null) / the slabs.
+static int dw_setup(DwArgs& a, int& grid, DwDir dir, const void* in, const void* other, void* out, float* partial, const DwPro* pro,
+                    int dtype, const DwDims& d) {
+  const bool wrw = dir == DW_WRW;
+  if (!pf_depthwise_supported(d.C, d.k, d.stride)) return (int)hipErrorInvalidValue;
+  if (!pf_aligned16(in) || !pf_aligned16(wrw ? other : out) || in == nullptr || other == nullptr || out == nullptr ||
+      (wrw && partial == nullptr))
+    return (int)hipErrorInvalidValue;
+  // stride-1 backward-data is the strip kernel of the forward pass on the flipped taps, over the swapped extents:
+  // dx[hi][wi] = sum_{r',s'} dy[hi + r' - (2-ph)][wi + s' - (2-pw)] * w[2-r'][2-s']
+  const bool flip = dir == DW_BWD_DATA && d.stride == 1;
+  const int r = flip ? dw_fill(a, d.B, d.Ho, d.Wo, d.C, d.H, d.Wd, 1, 2 - d.pad_h, 2 - d.pad_w)
+                     : dw_fill(a, d.B, d.H, d.Wd, d.C, d.Ho, d.Wo, d.stride, d.pad_h, d.pad_w);
   if (r) return r;
-  a.x = X; a.w = W; a.y = Y; a.dy = nullptr; a.partial = partial;
-  if (!dw_set_bytes(a, dtype, (int64_t)B * H * Wd * C, 0)) return (int)hipErrorInvalidValue;
-  const int grid = dw_groups(a.total, C);
-  hipStream_t st = (hipStream_t)stream;
-#define PF_DW(TT)                                                                     \
-  do {                                                                                \
-    if (dw_general(C)) {                                                              \
-      if (stride == 1) k_dw_fwd<TT, 1, true><<<grid, DW_T, 0, st>>>(a);               \
-      else k_dw_fwd<TT, 2, true><<<grid, DW_T, 0, st>>>(a);                           \
-    } else if (stride == 1) k_dw_fwd<TT, 1, false><<<grid, DW_T, 0, st>>>(a);         \
-    else k_dw_fwd<TT, 2, false><<<grid, DW_T, 0, st>>>(a);                            \
-  } while (0)
-  if (dtype == PF_F32) PF_DW(float);
-  else if (dtype == PF_BF16) PF_DW(bf16_t);
-  else return (int)hipErrorInvalidValue;
-#undef PF_DW
-  PF_LAUNCH_CHECK();
+  a.flip = flip ? 1 : 0;
+  if (pro != nullptr && !dw_act_ok(a, *pro)) return (int)hipErrorInvalidValue;
+  a.x = in; a.w = wrw ? nullptr : other; a.y = wrw ? nullptr : out; a.dy = wrw ? other : nullptr; a.partial = partial;
+  const int64_t x_elems = (int64_t)d.B * d.H * d.Wd * d.C, y_elems = (int64_t)d.B * d.Ho * d.Wo * d.C;
+  if (!dw_set_bytes(a, dtype, dir == DW_BWD_DATA ? y_elems : x_elems, wrw ? y_elems : 0)) return (int)hipErrorInvalidValue;
+  // k_dw_bwd_data (stride 2) gives a lane one input pixel, the strip kernels one strip
+  grid = dw_groups((dir == DW_BWD_DATA && !flip) ? (int64_t)d.B * d.H * d.Wd : a.total, d.C);
   return 0;
 }
 
-// dX [B][H][Wd][C] from dY [B][Ho][Wo][C]; W is the forward kernel [C][3][3] (not flipped), pad_h / pad_w the forward front pads
-extern "C" int pf_depthwise_bwd_data(const void* dY, const void* W, void* dX, int dtype, int B, int H, int Wd, int C, int k,
-                                     int stride, int pad_h, int pad_w, int Ho, int Wo, void* stream) {
-  if (!pf_depthwise_supported(C, k, stride)) return (int)hipErrorInvalidValue;
-  if (!pf_aligned16(dY) || !pf_aligned16(dX) || dY == nullptr || W == nullptr || dX == nullptr) return (int)hipErrorInvalidValue;
-  DwArgs a;
-  hipStream_t st = (hipStream_t)stream;
-  if (stride == 1) {
-    // the same strip kernel on the flipped taps: dx[hi][wi] = sum_{r',s'} dy[hi + r' - (2-ph)][wi + s' - (2-pw)] * w[2-r'][2-s']
-    const int r1 = dw_fill(a, B, Ho, Wo, C, H, Wd, 1, 2 - pad_h, 2 - pad_w);
-    if (r1) return r1;
-    a.x = dY; a.w = W; a.y = dX; a.dy = nullptr; a.partial = nullptr; a.flip = 1;
-    if (!dw_set_bytes(a, dtype, (int64_t)B * Ho * Wo * C, 0)) return (int)hipErrorInvalidValue;
-    const int grid1 = dw_groups(a.total, C);
-    const bool gen1 = dw_general(C);
-    if (dtype == PF_F32) { if (gen1) k_dw_fwd<float, 1, true><<<grid1, DW_T, 0, st>>>(a); else k_dw_fwd<float, 1, false><<<grid1, DW_T, 0, st>>>(a); }
-    else if (dtype == PF_BF16) { if (gen1) k_dw_fwd<bf16_t, 1, true><<<grid1, DW_T, 0, st>>>(a); else k_dw_fwd<bf16_t, 1, false><<<grid1, DW_T, 0, st>>>(a); }
-    else return (int)hipErrorInvalidValue;
-    PF_LAUNCH_CHECK();
-    return 0;
-  }
-  const int r = dw_fill(a, B, H, Wd, C, Ho, Wo, stride, pad_h, pad_w);
-  if (r) return r;
-  a.x = dY; a.w = W; a.y = dX; a.dy = nullptr; a.partial = nullptr;
-  if (!dw_set_bytes(a, dtype, (int64_t)B * Ho * Wo * C, 0)) return (int)hipErrorInvalidValue;
-  const int64_t npix = (int64_t)B * H * Wd;
-  const int grid = dw_groups(npix, C);
-  const bool gen = dw_general(C);
-  if (dtype == PF_F32) { if (gen) k_dw_bwd_data<float, true><<<grid, DW_T, 0, st>>>(a); else k_dw_bwd_data<float, false><<<grid, DW_T, 0, st>>>(a); }
-  else if (dtype == PF_BF16) { if (gen) k_dw_bwd_data<bf16_t, true><<<grid, DW_T, 0, st>>>(a); else k_dw_bwd_data<bf16_t, false><<<grid, DW_T, 0, st>>>(a); }
-  else return (int)hipErrorInvalidValue;
-  PF_LAUNCH_CHECK();
+// the three kernel templates under one parameter list (k_dw_bwd_data: any stride, no prologue)
+template <typename T, int ST, bool GEN, int PRO, int ACT> struct DwFwd { static constexpr auto kernel = k_dw_fwd<T, ST, GEN, PRO, ACT>; };
+template <typename T, int ST, bool GEN, int PRO, int ACT> struct DwWrw { static constexpr auto kernel = k_dw_wrw<T, ST, GEN, PRO, ACT>; };
+template <typename T, int ST, bool GEN, int PRO, int ACT> struct DwBwdData { static constexpr auto kernel = k_dw_bwd_data<T, GEN>; };
+
+// (dtype, a.stride, dw_general(a.C), prologue, activation) -> the instantiation of K that runs.  Without a prologue (a.ss == nullptr)
+// there is no activation either: no DW_PRO_NONE kernel with an ACT is built.
+template <template <typename, int, bool, int, int> class K>
+static int dw_launch(const DwArgs& a, int grid, int dtype, int act, hipStream_t st) {
+  if (dtype != PF_F32 && dtype != PF_BF16) return (int)hipErrorInvalidValue;
+  auto ladder = [&](auto PRO, auto ACT) {
+    pf_with_bool(dtype == PF_F32, [&](auto F32) {
+      pf_with_bool(a.stride == 1, [&](auto S1) {
+        pf_with_bool(dw_general(a.C), [&](auto GEN) {
+          using T = std::conditional_t<decltype(F32)::value, float, bf16_t>;
+          K<T, decltype(S1)::value ? 1 : 2, decltype(GEN)::value, decltype(PRO)::value, decltype(ACT)::value>::kernel<<<grid, DW_T, 0, st>>>(a);
+        });
+      });
+    });
+  };
+  if (a.ss == nullptr) ladder(std::integral_constant<int, DW_PRO_NONE>{}, std::integral_constant<int, PF_ACT_NONE>{});
+  else
+    pf_with_bool(act == PF_ACT_RELU6, [&](auto R6) {
+      pf_with_bool(a.slot != nullptr, [&](auto Q) {
+        ladder(std::integral_constant<int, decltype(Q)::value ? DW_PRO_QUANT : DW_PRO_AFFINE>{},
+               std::integral_constant<int, decltype(R6)::value ? PF_ACT_RELU6 : PF_ACT_NONE>{});
+      });
+    });
   return 0;
 }
 
 int pf_wrw_reduce(float* workspace, int S, int64_t n, void* dW, int dw_dtype, hipStream_t st);   // pf_conv.hip
 
-// dW [C][3][3] (dw_dtype) from dY and X; slabs: (pf_depthwise_groups(B, Ho, Wo, C) + 32) * C * 9 floats of workspace
-extern "C" int pf_depthwise_wrw(const void* dY, const void* X, void* dW, int dtype, int dw_dtype, float* slabs, int B, int H,
-                                int Wd, int C, int k, int stride, int pad_h, int pad_w, int Ho, int Wo, void* stream) {
-  if (!pf_depthwise_supported(C, k, stride)) return (int)hipErrorInvalidValue;
-  if (!pf_aligned16(dY) || !pf_aligned16(X) || dY == nullptr || X == nullptr || dW == nullptr || slabs == nullptr)
-    return (int)hipErrorInvalidValue;
+static int dw_run(DwDir dir, const void* in, const void* other, void* out, float* partial, const DwPro* pro, int dtype, int dw_dtype,
+                  const DwDims& d, void* stream) {
   DwArgs a;
-  const int r = dw_fill(a, B, H, Wd, C, Ho, Wo, stride, pad_h, pad_w);
+  int grid = 0;
+  const int r = dw_setup(a, grid, dir, in, other, out, partial, pro, dtype, d);
   if (r) return r;
-  a.x = X; a.w = nullptr; a.y = nullptr; a.dy = dY; a.partial = slabs;
-  if (!dw_set_bytes(a, dtype, (int64_t)B * H * Wd * C, (int64_t)B * Ho * Wo * C)) return (int)hipErrorInvalidValue;
-  const int grid = dw_groups(a.total, C);
   hipStream_t st = (hipStream_t)stream;
-#define PF_DWW(TT)                                                                    \
-  do {                                                                                \
-    if (dw_general(C)) {                                                              \
-      if (stride == 1) k_dw_wrw<TT, 1, true><<<grid, DW_T, 0, st>>>(a);               \
-      else k_dw_wrw<TT, 2, true><<<grid, DW_T, 0, st>>>(a);                           \
-    } else if (stride == 1) k_dw_wrw<TT, 1, false><<<grid, DW_T, 0, st>>>(a);         \
-    else k_dw_wrw<TT, 2, false><<<grid, DW_T, 0, st>>>(a);                            \
-  } while (0)
-  if (dtype == PF_F32) PF_DWW(float);
-  else if (dtype == PF_BF16) PF_DWW(bf16_t);
-  else return (int)hipErrorInvalidValue;
-#undef PF_DWW
-  const int n = C * 9;
+  const int act = pro != nullptr ? pro->act : PF_ACT_NONE;
+  const int l = dir == DW_WRW                 ? dw_launch<DwWrw>(a, grid, dtype, act, st)
+                : (dir == DW_FWD || a.flip) ? dw_launch<DwFwd>(a, grid, dtype, act, st)
+                                            : dw_launch<DwBwdData>(a, grid, dtype, act, st);
+  if (l) return l;
   // The slabs go through the staged reduction of the other backward-filter kernels (pf_wrw_reduce: 64 outputs x 4 interleaved slab
   // lanes per workgroup, split ranges on gridDim.y, a second launch folds the ranges; fixed order).  Round 4's own reduction ran ONE
   // thread per output over all G <= 1024 slabs (271 us per launch, 14.6 % of the C3 step); measured in round 5's first GPU call
   // (profiles/r05_first_call_ab.txt): C3 13 602 -> 16 140 images/s with this one, the old kernel is gone.
-  return pf_wrw_reduce(slabs, grid, (int64_t)n, dW, dw_dtype, st);
+  if (dir == DW_WRW) return pf_wrw_reduce(partial, grid, (int64_t)(d.C * 9), out, dw_dtype, st);
+  PF_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int pf_depthwise_fwd(const void* X, const void* W, void* Y, int dtype, float* partial, int B, int H, int Wd, int C,
+                                int k, int stride, int pad_h, int pad_w, int Ho, int Wo, void* stream) {
+  return dw_run(DW_FWD, X, W, Y, partial, nullptr, dtype, 0, {B, H, Wd, C, k, stride, pad_h, pad_w, Ho, Wo}, stream);
+}
+
+// dX [B][H][Wd][C] from dY [B][Ho][Wo][C]; W is the forward kernel [C][3][3] (not flipped), pad_h / pad_w the forward front pads
+extern "C" int pf_depthwise_bwd_data(const void* dY, const void* W, void* dX, int dtype, int B, int H, int Wd, int C, int k,
+                                     int stride, int pad_h, int pad_w, int Ho, int Wo, void* stream) {
+  return dw_run(DW_BWD_DATA, dY, W, dX, nullptr, nullptr, dtype, 0, {B, H, Wd, C, k, stride, pad_h, pad_w, Ho, Wo}, stream);
+}
+
+// dW [C][3][3] (dw_dtype) from dY and X; slabs: (pf_depthwise_groups(B, Ho, Wo, C) + 32) * C * 9 floats of workspace
+extern "C" int pf_depthwise_wrw(const void* dY, const void* X, void* dW, int dtype, int dw_dtype, float* slabs, int B, int H,
+                                int Wd, int C, int k, int stride, int pad_h, int pad_w, int Ho, int Wo, void* stream) {
+  return dw_run(DW_WRW, X, dY, dW, slabs, nullptr, dtype, dw_dtype, {B, H, Wd, C, k, stride, pad_h, pad_w, Ho, Wo}, stream);
 }
 
 // ---- the producer BatchNorm's normalise / activation / fake-quant in the prologue (MobileNet-v2: the 6x expansion) -------------
 // X is the RAW tensor in front of the BatchNorm; everything else as pf_depthwise_fwd / pf_depthwise_wrw (same grids, same statistics
 // and slab layouts, same reduction orders).  A null slot: no quantiser.
-template <typename T, int PRO, int ACT>
-static void dw_fwd_act_launch(const DwArgs& a, int grid, hipStream_t st) {
-  if (dw_general(a.C)) {
-    if (a.stride == 1) k_dw_fwd<T, 1, true, PRO, ACT><<<grid, DW_T, 0, st>>>(a);
-    else k_dw_fwd<T, 2, true, PRO, ACT><<<grid, DW_T, 0, st>>>(a);
-  } else if (a.stride == 1) k_dw_fwd<T, 1, false, PRO, ACT><<<grid, DW_T, 0, st>>>(a);
-  else k_dw_fwd<T, 2, false, PRO, ACT><<<grid, DW_T, 0, st>>>(a);
-}
-template <typename T, int PRO, int ACT>
-static void dw_wrw_act_launch(const DwArgs& a, int grid, hipStream_t st) {
-  if (dw_general(a.C)) {
-    if (a.stride == 1) k_dw_wrw<T, 1, true, PRO, ACT><<<grid, DW_T, 0, st>>>(a);
-    else k_dw_wrw<T, 2, true, PRO, ACT><<<grid, DW_T, 0, st>>>(a);
-  } else if (a.stride == 1) k_dw_wrw<T, 1, false, PRO, ACT><<<grid, DW_T, 0, st>>>(a);
-  else k_dw_wrw<T, 2, false, PRO, ACT><<<grid, DW_T, 0, st>>>(a);
-}
-
-// the prologue operands the two entries check alike
-static bool dw_act_ok(DwArgs& a, const float* scale_shift, int act, const uint32_t* slot, int bits, int dtype) {
-  if (scale_shift == nullptr || (dtype != PF_F32 && dtype != PF_BF16)) return false;
-  if (act != PF_ACT_NONE && act != PF_ACT_RELU6) return false;   // the producers of a depthwise layer: ReLU6 (MobileNet) or none; no ReLU forms are built
-  if (slot != nullptr && (bits < 1 || bits > 32 || ((uintptr_t)slot & 7u) != 0)) return false;
-  a.ss = scale_shift; a.slot = slot; a.qk = uq_k_of_bits(slot != nullptr ? bits : 8);
-  return true;
-}
-
 extern "C" int pf_depthwise_fwd_act(const void* X, const float* scale_shift, int act, const uint32_t* slot, int bits, const void* W,
                                     void* Y, int dtype, float* partial, int B, int H, int Wd, int C, int k, int stride, int pad_h,
                                     int pad_w, int Ho, int Wo, void* stream) {
-  if (!pf_depthwise_supported(C, k, stride)) return (int)hipErrorInvalidValue;
-  if (!pf_aligned16(X) || !pf_aligned16(Y) || X == nullptr || W == nullptr || Y == nullptr) return (int)hipErrorInvalidValue;
-  DwArgs a;
-  const int r = dw_fill(a, B, H, Wd, C, Ho, Wo, stride, pad_h, pad_w);
-  if (r) return r;
-  if (!dw_act_ok(a, scale_shift, act, slot, bits, dtype)) return (int)hipErrorInvalidValue;
-  a.x = X; a.w = W; a.y = Y; a.dy = nullptr; a.partial = partial;
-  if (!dw_set_bytes(a, dtype, (int64_t)B * H * Wd * C, 0)) return (int)hipErrorInvalidValue;
-  const int grid = dw_groups(a.total, C);
-  hipStream_t st = (hipStream_t)stream;
-  pf_with_bool(act == PF_ACT_RELU6, [&](auto R6) {
-    pf_with_bool(slot != nullptr, [&](auto Q) {
-      constexpr int PRO = decltype(Q)::value ? DW_PRO_QUANT : DW_PRO_AFFINE;
-      constexpr int ACT = decltype(R6)::value ? PF_ACT_RELU6 : PF_ACT_NONE;
-      if (dtype == PF_F32) dw_fwd_act_launch<float, PRO, ACT>(a, grid, st);
-      else dw_fwd_act_launch<bf16_t, PRO, ACT>(a, grid, st);
-    });
-  });
-  PF_LAUNCH_CHECK();
-  return 0;
+  const DwPro pro = {scale_shift, act, slot, bits};
+  return dw_run(DW_FWD, X, W, Y, partial, &pro, dtype, 0, {B, H, Wd, C, k, stride, pad_h, pad_w, Ho, Wo}, stream);
 }
 
 extern "C" int pf_depthwise_wrw_act(const void* dY, const void* X, const float* scale_shift, int act, const uint32_t* slot, int bits,
                                     void* dW, int dtype, int dw_dtype, float* slabs, int B, int H, int Wd, int C, int k, int stride,
                                     int pad_h, int pad_w, int Ho, int Wo, void* stream) {
-  if (!pf_depthwise_supported(C, k, stride)) return (int)hipErrorInvalidValue;
-  if (!pf_aligned16(dY) || !pf_aligned16(X) || dY == nullptr || X == nullptr || dW == nullptr || slabs == nullptr)
-    return (int)hipErrorInvalidValue;
-  DwArgs a;
-  const int r = dw_fill(a, B, H, Wd, C, Ho, Wo, stride, pad_h, pad_w);
-  if (r) return r;
-  if (!dw_act_ok(a, scale_shift, act, slot, bits, dtype)) return (int)hipErrorInvalidValue;
-  a.x = X; a.w = nullptr; a.y = nullptr; a.dy = dY; a.partial = slabs;
-  if (!dw_set_bytes(a, dtype, (int64_t)B * H * Wd * C, (int64_t)B * Ho * Wo * C)) return (int)hipErrorInvalidValue;
-  const int grid = dw_groups(a.total, C);
-  hipStream_t st = (hipStream_t)stream;
-  pf_with_bool(act == PF_ACT_RELU6, [&](auto R6) {
-    pf_with_bool(slot != nullptr, [&](auto Q) {
-      constexpr int PRO = decltype(Q)::value ? DW_PRO_QUANT : DW_PRO_AFFINE;
-      constexpr int ACT = decltype(R6)::value ? PF_ACT_RELU6 : PF_ACT_NONE;
-      if (dtype == PF_F32) dw_wrw_act_launch<float, PRO, ACT>(a, grid, st);
-      else dw_wrw_act_launch<bf16_t, PRO, ACT>(a, grid, st);
-    });
-  });
-  return pf_wrw_reduce(slabs, grid, (int64_t)(C * 9), dW, dw_dtype, st);
+  const DwPro pro = {scale_shift, act, slot, bits};
+  return dw_run(DW_WRW, X, dY, dW, slabs, &pro, dtype, dw_dtype, {B, H, Wd, C, k, stride, pad_h, pad_w, Ho, Wo}, stream);
 }

@@ -3,26 +3,20 @@
 // that value -- one rounding to the output type (k_dw_i8), or the consumer's BatchNorm + activation + static quantiser (k_dw_i8_q)
 // -- is the caller's `emit`.
 #pragma once
-#include "pf_common.h"
+#include "pf_buffer.h"
 
 #define DWI_T 256
 #define DWI_PW 4
-#define DWI_OOB 0x80000000u
 
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __amdgpu_buffer_rsrc_t dwi_rsrc_t;
-#define DWI_MAKE_RSRC(p, bytes) __builtin_amdgcn_make_buffer_rsrc((void*)(p), (short)0, (int)(bytes), 0x00020000)
-typedef uint32_t dwi_u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void dwi_load16(dwi_rsrc_t rs, uint32_t off, uint32_t* o) {
-  const dwi_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0);
-  o[0] = v[0]; o[1] = v[1]; o[2] = v[2]; o[3] = v[3];
+// the sixteen codes of one vector as the four dwords the strip loop indexes
+__device__ __forceinline__ void dwi_load16(pf_rsrc_t rs, uint32_t off, uint32_t* o) {
+  const uint4 v = pf_buffer_load16(rs, off);
+  o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
 }
 // sum of the four byte products of a and b, plus c
+#if defined(__HIP_DEVICE_COMPILE__)
 __device__ __forceinline__ uint32_t dwi_dot4(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_udot4(a, b, c, false); }
 #else
-typedef int dwi_rsrc_t;
-#define DWI_MAKE_RSRC(p, bytes) 0
-__device__ __forceinline__ void dwi_load16(dwi_rsrc_t, uint32_t, uint32_t* o) { o[0] = o[1] = o[2] = o[3] = 0u; }
 __device__ __forceinline__ uint32_t dwi_dot4(uint32_t, uint32_t, uint32_t c) { return c; }
 #endif
 
@@ -47,7 +41,7 @@ __device__ __forceinline__ void dw_i8_body(const DwiArgs& a, Emit&& emit) {
   const int cgl = threadIdx.x % a.cgb, sl = threadIdx.x / a.cgb;
   const int cg = blockIdx.y * a.cgb + cgl;
   if (cg >= a.C16 || sl >= a.spb) return;                  // lanes left over when cgb does not divide the workgroup
-  const dwi_rsrc_t rsx = DWI_MAKE_RSRC(a.x, a.x_bytes);
+  const pf_rsrc_t rsx = PF_MAKE_RSRC(a.x, a.x_bytes);
   uint32_t wc[3][16];
 #pragma unroll
   for (int j = 0; j < 16; ++j)
@@ -74,7 +68,7 @@ __device__ __forceinline__ void dw_i8_body(const DwiArgs& a, Emit&& emit) {
       for (int i = 0; i < NV; ++i) {
         const int wi = wo0 * ST - a.pw + i;
         const bool ok = rok && (unsigned)wi < (unsigned)a.W;
-        dwi_load16(rsx, ok ? rbase + (uint32_t)(wi * a.C) : DWI_OOB, raw[r][i]);
+        dwi_load16(rsx, ok ? rbase + (uint32_t)(wi * a.C) : PF_BUFFER_OOB, raw[r][i]);
       }
     }
     float out[DWI_PW][16];

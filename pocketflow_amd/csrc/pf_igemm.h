@@ -1,21 +1,8 @@
 // Shared by the implicit-GEMM kernels (pf_igemm.hip): argument block,
-// buffer-descriptor / LDS-DMA macros, counted waits, mode constants.
+// counted waits, mode constants (buffer-descriptor / LDS-DMA macros: pf_buffer.h).
 #pragma once
 #include "pf_conv_common.h"
-
-#define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
-
-// The buffer-descriptor type exists only in the device pass; the host pass (which merely emits the launch stub) still has
-// to parse the kernel body -- without this the host pass silently DROPS the stubs and the library fails to load.
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __amdgpu_buffer_rsrc_t pf_rsrc_t;
-#define PF_MAKE_RSRC(p, bytes) __builtin_amdgcn_make_buffer_rsrc((void*)(p), (short)0, (int)(bytes), 0x00020000)
-#define PF_BUFFER_LOAD_LDS16(rs, lds, voff, soff) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, LDS_PTR(lds), 16, voff, soff, 0, 0)
-#else
-typedef int pf_rsrc_t;
-#define PF_MAKE_RSRC(p, bytes) 0
-#define PF_BUFFER_LOAD_LDS16(rs, lds, voff, soff) ((void)(rs), (void)(lds), (void)(voff), (void)(soff))
-#endif
+#include "pf_buffer.h"
 
 struct IgArgs {
   const bf16_t* X;      // [rows_in][C]

@@ -14,20 +14,10 @@
 //     such that a lane ends up with 16 CONSECUTIVE channels of its pixel: two 16-byte stores, no LDS transposition;
 //   * persistent workgroups (2 per CU) loop over (image, strip) items, so the weight packing is paid once.
 #include "pf_conv_common.h"
+#include "pf_buffer.h"
 
-#define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 typedef short st_v4s __attribute__((ext_vector_type(4)));
 typedef short st_v8s __attribute__((ext_vector_type(8)));
-// device-only buffer-descriptor type: the host pass only has to parse the kernel bodies (see pf_igemm.hip)
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __amdgpu_buffer_rsrc_t st_rsrc_t;
-#define ST_MAKE_RSRC(p, bytes) __builtin_amdgcn_make_buffer_rsrc((void*)(p), (short)0, (int)(bytes), 0x00020000)
-#define ST_BUFFER_LOAD_LDS16(rs, lds, voff) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, LDS_PTR(lds), 16, voff, 0, 0, 0)
-#else
-typedef int st_rsrc_t;
-#define ST_MAKE_RSRC(p, bytes) 0
-#define ST_BUFFER_LOAD_LDS16(rs, lds, voff) ((void)(rs), (void)(lds), (void)(voff))
-#endif
 
 #define ST_THREADS 256
 #define ST_OROWS 8                      // output rows per item
@@ -198,7 +188,7 @@ __global__ __launch_bounds__(ST_THREADS) void k_stem7x7_wrw(StemWrwArgs a) {
   const int l15 = lane & 15, q = lane >> 4;
   const int nb0 = 2 * (wave & 1);                           // this wavefront's two 16-channel blocks
   const int r0 = (wave >> 1) ? 4 : 0, nr = (wave >> 1) ? 3 : 4;   // and its kernel rows
-  const st_rsrc_t rsY = ST_MAKE_RSRC(a.dY, a.dy_bytes);
+  const pf_rsrc_t rsY = PF_MAKE_RSRC(a.dY, a.dy_bytes);
   constexpr uint32_t OOB = 0x80000000u;
   const int sb = lane >> 4, srow = (lane & 15) >> 1, sch = lane & 1;        // role inside one LDS-DMA instruction
   const int tr_off = (q & 1) * 128 + (l15 >> 2) * 32 + (l15 & 3) * 8;       // piece of the transposed read (k_wrw2)
@@ -229,7 +219,7 @@ __global__ __launch_bounds__(ST_THREADS) void k_stem7x7_wrw(StemWrwArgs a) {
     for (int id = wave; id < steps * 4; id += ST_THREADS / 64) {
       const int lin = id * 8 + srow;                        // id = step*4 + pg
       const uint32_t voff = (lin < valid_px) ? (uint32_t)(((m_base + lin) * ST_N + 16 * sb + 8 * sch) * 2) : OOB;
-      ST_BUFFER_LOAD_LDS16(rsY, dys + id * 1024, voff);
+      PF_BUFFER_LOAD_LDS16(rsY, dys + id * 1024, voff, 0);
     }
     // ---- X: 9 input rows, 3 -> 4 channels ----
     for (int row = tid >> 7; row < SW_IROWS; row += 2) {

@@ -19,19 +19,10 @@
 //     read ds_read_b64_tr_b16 exactly as in k_stem7x7_wrw -- dY in [8 pixels][16 channels] blocks filled by LDS-DMA, X pieces = one
 //     padded pixel each; float32 slabs [N][27] per workgroup, summed in a fixed order by pf_wrw_reduce (deterministic).
 #include "pf_conv_common.h"
+#include "pf_buffer.h"
 
-#define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 typedef short s3_v4s __attribute__((ext_vector_type(4)));
 typedef short s3_v8s __attribute__((ext_vector_type(8)));
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __amdgpu_buffer_rsrc_t s3_rsrc_t;
-#define S3_MAKE_RSRC(p, bytes) __builtin_amdgcn_make_buffer_rsrc((void*)(p), (short)0, (int)(bytes), 0x00020000)
-#define S3_BUFFER_LOAD_LDS16(rs, lds, voff) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, LDS_PTR(lds), 16, voff, 0, 0, 0)
-#else
-typedef int s3_rsrc_t;
-#define S3_MAKE_RSRC(p, bytes) 0
-#define S3_BUFFER_LOAD_LDS16(rs, lds, voff) ((void)(rs), (void)(lds), (void)(voff))
-#endif
 
 #define S3_THREADS 256
 #define S3_OROWS 8                      // forward: output rows per item
@@ -202,7 +193,7 @@ __global__ __launch_bounds__(S3_THREADS) void k_stem3x3_wrw(Stem3WrwArgs a) {
   const int nb0 = (NB == 2) ? (wave & 1) : 0;               // this wavefront's 16-channel block
   const int r0 = (NB == 2) ? ((wave >> 1) ? 2 : 0) : wave;  // and its kernel rows r0 .. r0 + nr - 1
   const int nr = (NB == 2) ? ((wave >> 1) ? 1 : 2) : (wave < 3 ? 1 : 0);
-  const s3_rsrc_t rsY = S3_MAKE_RSRC(a.dY, a.dy_bytes);
+  const pf_rsrc_t rsY = PF_MAKE_RSRC(a.dY, a.dy_bytes);
   constexpr uint32_t OOB = 0x80000000u;
   // role inside one LDS-DMA instruction (1 KiB = PGI pixel groups x NB channel blocks x [8 pixels][16 channels])
   const int spg = lane / (16 * NB), sb = (lane >> 4) % NB, srow = (lane & 15) >> 1, sch = lane & 1;
@@ -231,7 +222,7 @@ __global__ __launch_bounds__(S3_THREADS) void k_stem3x3_wrw(Stem3WrwArgs a) {
     for (int id = wave; id < steps * NB; id += S3_THREADS / 64) {
       const int lin = (id * PGI + spg) * 8 + srow;
       const uint32_t voff = (lin < valid_px) ? (uint32_t)(((m_base + lin) * N + 16 * sb + 8 * sch) * 2) : OOB;
-      S3_BUFFER_LOAD_LDS16(rsY, dys + id * 1024, voff);
+      PF_BUFFER_LOAD_LDS16(rsY, dys + id * 1024, voff, 0);
     }
     // ---- X: 5 input rows, 3 -> 4 channels ----
     for (int row = tid >> 7; row < S3W_IROWS; row += 2) {

@@ -20,9 +20,9 @@
 // The (n, k) tiles of one pixel split occupy consecutive workgroups of one XCD, so the rows they all read are fetched
 // from HBM once and shared through that XCD's L2.
 #include "pf_conv_common.h"
+#include "pf_buffer.h"
 #include <stdlib.h>
 
-#define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 typedef short v4s __attribute__((ext_vector_type(4)));
 typedef short v8s __attribute__((ext_vector_type(8)));
 
@@ -293,16 +293,6 @@ int pf_wrw_tr_launch(const void* dY, const void* X, float* slabs, const float* s
 // staged itself (8 consecutive channels of one pixel: its scale / shift live in registers for the whole launch), right
 // behind the MFMAs of the previous step.
 // =====================================================================================================================
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __amdgpu_buffer_rsrc_t pf_wrsrc_t;
-#define PF_W_MAKE_RSRC(p, bytes) __builtin_amdgcn_make_buffer_rsrc((void*)(p), (short)0, (int)(bytes), 0x00020000)
-#define PF_W_BUFFER_LOAD_LDS16(rs, lds, voff) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, LDS_PTR(lds), 16, voff, 0, 0, 0)
-#else
-typedef int pf_wrsrc_t;                               // host pass: the kernel body only has to parse (see pf_igemm.hip)
-#define PF_W_MAKE_RSRC(p, bytes) 0
-#define PF_W_BUFFER_LOAD_LDS16(rs, lds, voff) ((void)(rs), (void)(lds), (void)(voff))
-#endif
-
 // Ablation builds for tools/gpu/wrw_ablate.py ONLY (never in libpocketflow_hip.so): PF_W2_ABLATE bit 0 drops the fragment reads
 // and MFMAs of k_wrw2, bit 1 the LDS-DMA, bit 2 the slab stores of the epilogue.  Results are garbage by design.
 #ifndef PF_W2_ABLATE
@@ -432,8 +422,8 @@ __global__ __launch_bounds__(64 * (TN / WTN) * (TK / WTK)) void k_wrw2(const Wrw
 
   // dY (and X under the identity map) are bounded at THIS workgroup's last pixel row: rows past it read zeros through the
   // descriptor's range check, the tail needs no per-lane compare
-  const pf_wrsrc_t rsY = PF_W_MAKE_RSRC(a.dY, (uint32_t)mend * (uint32_t)a.N * 2u);
-  const pf_wrsrc_t rsX = PF_W_MAKE_RSRC(a.X, (MAPM == 0) ? (uint32_t)mend * (uint32_t)a.C * 2u : a.x_bytes);
+  const pf_rsrc_t rsY = PF_MAKE_RSRC(a.dY, (uint32_t)mend * (uint32_t)a.N * 2u);
+  const pf_rsrc_t rsX = PF_MAKE_RSRC(a.X, (MAPM == 0) ? (uint32_t)mend * (uint32_t)a.C * 2u : a.x_bytes);
   constexpr uint32_t OOB = 0x80000000u;
   const int sb = lane >> 4, srow = (lane & 15) >> 1, sch = lane & 1;       // role inside one LDS-DMA instruction
   const int hw_o = a.Ho * a.Wo;
@@ -496,7 +486,7 @@ __global__ __launch_bounds__(64 * (TN / WTN) * (TK / WTK)) void k_wrw2(const Wrw
       const int id = (wave + k * NWAVE) % IDY;
       const int pg = id / (TN / 64), g4 = id % (TN / 64);
       unsigned char* ydst = owny ? dst + (pg * NBN + g4 * 4) * 256 : smem + 3 * STAGE;
-      if (!(PF_W2_ABLATE & 2)) PF_W_BUFFER_LOAD_LDS16(rsY, ydst, yoff[k]);
+      if (!(PF_W2_ABLATE & 2)) PF_BUFFER_LOAD_LDS16(rsY, ydst, yoff[k], 0);
       yoff[k] += ystep;
     }
 #pragma unroll
@@ -530,7 +520,7 @@ __global__ __launch_bounds__(64 * (TN / WTN) * (TK / WTK)) void k_wrw2(const Wrw
       }
       if (!own) voff = OOB;
       unsigned char* xdst = own ? dst + DY_BYTES + (pg * NBK + g4 * 4) * 256 : smem + 3 * STAGE;
-      if (!(PF_W2_ABLATE & 2)) PF_W_BUFFER_LOAD_LDS16(rsX, xdst, voff);
+      if (!(PF_W2_ABLATE & 2)) PF_BUFFER_LOAD_LDS16(rsX, xdst, voff, 0);
     }
   };
   auto transform = [&](int buf) {                                            // own X pieces, in place

@@ -2178,8 +2178,9 @@ def _pass_tag(x, y):
   return y
 
 
-def _run_depthwise(x, w, stride, ph, pw, Ho, Wo, want_stats):
-  """x: logical NCHW / physical NHWC, float32 or bf16; w: [C][1][k][k]; ph / pw: the FRONT pads."""
+def _run_depthwise(x, lazy, w, stride, ph, pw, Ho, Wo, want_stats):
+  """x: logical NCHW / physical NHWC, float32 or bf16; w: [C][1][k][k]; ph / pw: the FRONT pads.  `lazy` (a LazyAct, or None): x is the
+  RAW tensor in front of that BatchNormAct, whose un-materialised output the kernel applies on the fly."""
   B, C, H, W = x.shape
   k = w.shape[2]
   y = torch.empty((B, C, Ho, Wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
@@ -2187,76 +2188,37 @@ def _run_depthwise(x, w, stride, ph, pw, Ho, Wo, want_stats):
   if want_stats:
     G = hip.depthwise_groups(B, Ho, Wo, C)
     partial = torch.empty((G, 4, C), dtype=torch.float32, device=x.device)
-  with region('depthwise_fwd', float((x.numel() + y.numel()) * x.element_size())):
-    hip.depthwise_fwd(x, w.detach().reshape(C, k, k), y, B, H, W, C, k, stride, ph, pw, Ho, Wo, partial=partial)
+  dims = (B, H, W, C, k, stride, ph, pw, Ho, Wo)
+  with region('depthwise_fwd' if lazy is None else 'depthwise_fwd_act', float((x.numel() + y.numel()) * x.element_size())):
+    if lazy is None:
+      hip.depthwise_fwd(x, w.detach().reshape(C, k, k), y, *dims, partial=partial)
+    else:
+      hip.depthwise_fwd_act(x, *_dw_prologue(lazy), w.detach().reshape(C, k, k), y, *dims, partial=partial)
   if want_stats:
     y._pf_stats = (partial, G)
   return y
+
+
+def _dw_prologue(lazy):
+  """The prologue operands of hip.depthwise_fwd_act / hip.depthwise_wrw_act: scale_shift, act, slot, bits of a LazyAct."""
+  quant = lazy.bits is not None
+  return lazy.scale_shift, lazy.act, lazy.slot if quant else None, lazy.bits if quant else 8
 
 
 class _Depthwise(torch.autograd.Function):
   """y = depthwise_conv3x3(x, W) on pf_depthwise_* (float32 or bf16 NHWC), TF 'SAME' front pads; the forward kernel leaves
-  the statistics of y for the BatchNorm behind it (`want_stats`)."""
+  the statistics of y for the BatchNorm behind it (`want_stats`).
 
-  @staticmethod
-  def forward(ctx, x, w, stride, ph, pw, Ho, Wo, want_stats, graph, w_var, box):
-    x = _nhwc(x)
-    y = _run_depthwise(x, w, stride, ph, pw, Ho, Wo, want_stats)
-    ctx.save_for_backward(x, w)
-    ctx.meta = (stride, ph, pw, Ho, Wo, graph, w_var)
-    box.append(getattr(y, '_pf_stats', None))
-    return y
-
-  @staticmethod
-  def backward(ctx, dy):
-    x, w = ctx.saved_tensors
-    stride, ph, pw, Ho, Wo, graph, w_var = ctx.meta
-    dy = _nhwc(dy)
-    if dy.dtype != x.dtype:
-      dy = dy.to(x.dtype)
-    B, C, H, W = x.shape
-    k = w.shape[2]
-    dx = dw = None
-    if ctx.needs_input_grad[1]:
-      G = hip.depthwise_groups(B, Ho, Wo, C)
-
-      def wrw(dwk, scratch):                       # dwk: [C][k][k][1] memory = [C][k][k]
-        hip.depthwise_wrw(dy, x, dwk, scratch((G + 32) * C * k * k), B, H, W, C, k, stride, ph, pw, Ho, Wo)
-      dw = _filter_grad(graph, w, w_var, (dy, x), 'depthwise_wrw', float((x.numel() + dy.numel()) * x.element_size()), wrw)
-    if ctx.needs_input_grad[0]:
-      dx = torch.empty_like(x)
-      with region('depthwise_bwd_data', float((x.numel() + dy.numel()) * x.element_size())):
-        hip.depthwise_bwd_data(dy, w.detach().reshape(C, k, k), dx, B, H, W, C, k, stride, ph, pw, Ho, Wo)
-    return dx, dw, None, None, None, None, None, None, None, None, None
-
-
-def _run_depthwise_act(x, lazy, w, stride, ph, pw, Ho, Wo, want_stats):
-  """_run_depthwise on the un-materialised output of a BatchNormAct: x is the RAW tensor, the kernel applies `lazy` on the fly."""
-  B, C, H, W = x.shape
-  k = w.shape[2]
-  y = torch.empty((B, C, Ho, Wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-  partial = None
-  if want_stats:
-    G = hip.depthwise_groups(B, Ho, Wo, C)
-    partial = torch.empty((G, 4, C), dtype=torch.float32, device=x.device)
-  quant = lazy.bits is not None
-  with region('depthwise_fwd_act', float((x.numel() + y.numel()) * x.element_size())):
-    hip.depthwise_fwd_act(x, lazy.scale_shift, lazy.act, lazy.slot if quant else None, lazy.bits if quant else 8,
-                          w.detach().reshape(C, k, k), y, B, H, W, C, k, stride, ph, pw, Ho, Wo, partial=partial)
-  if want_stats:
-    y._pf_stats = (partial, G)
-  return y
-
-
-class _DepthwiseAct(torch.autograd.Function):
-  """_Depthwise reading a LazyAct: y = depthwise_conv3x3(Q(x), W), Q the producer BN's normalise / act / fake-quant, applied in the
-  prologue of pf_depthwise_fwd_act and again in pf_depthwise_wrw_act (the raw x and Q's operands are what is saved: the activated
-  tensor never exists).  Backward-data never reads x: it is pf_depthwise_bwd_data as it stands, and its result is the gradient with
+  With `lazy`, a LazyAct whose raw tensor x is: y = depthwise_conv3x3(Q(x), W), Q the producer BN's normalise / act / fake-quant, applied
+  in the prologue of pf_depthwise_fwd_act and again in pf_depthwise_wrw_act (the raw x and Q's operands are what is saved: the activated
+  tensor never exists).  Backward-data never reads x: it is pf_depthwise_bwd_data either way, and there its result is the gradient with
   respect to Q(x), which flows into x's node (_BnLazy) as it does from the fused 1x1 convolutions."""
 
   @staticmethod
   def forward(ctx, x, w, lazy, stride, ph, pw, Ho, Wo, want_stats, graph, w_var, box):
-    y = _run_depthwise_act(x, lazy, w, stride, ph, pw, Ho, Wo, want_stats)
+    if lazy is None:
+      x = _nhwc(x)
+    y = _run_depthwise(x, lazy, w, stride, ph, pw, Ho, Wo, want_stats)
     ctx.save_for_backward(x, w)
     ctx.meta = (lazy, stride, ph, pw, Ho, Wo, graph, w_var)
     box.append(getattr(y, '_pf_stats', None))
@@ -2271,21 +2233,26 @@ class _DepthwiseAct(torch.autograd.Function):
       dy = dy.to(x.dtype)
     B, C, H, W = x.shape
     k = w.shape[2]
+    dims = (B, H, W, C, k, stride, ph, pw, Ho, Wo)
+    nbytes = float((x.numel() + dy.numel()) * x.element_size())
     dx = dw = None
     if ctx.needs_input_grad[1]:
       G = hip.depthwise_groups(B, Ho, Wo, C)
-      quant = lazy.bits is not None
-      ss = lazy.scale_shift
+      pro = None if lazy is None else _dw_prologue(lazy)
 
       def wrw(dwk, scratch):                       # dwk: [C][k][k][1] memory = [C][k][k]
-        hip.depthwise_wrw_act(dy, x, ss, lazy.act, lazy.slot if quant else None, lazy.bits if quant else 8, dwk,
-                              scratch((G + 32) * C * k * k), B, H, W, C, k, stride, ph, pw, Ho, Wo)
+        slabs = scratch((G + 32) * C * k * k)
+        if lazy is None:
+          hip.depthwise_wrw(dy, x, dwk, slabs, *dims)
+        else:
+          hip.depthwise_wrw_act(dy, x, *pro, dwk, slabs, *dims)
       # (the producer BN's constants belong to ITS node, which runs right behind this one: kept referenced until the join)
-      dw = _filter_grad(graph, w, w_var, (dy, x, ss, lazy), 'depthwise_wrw_act', float((x.numel() + dy.numel()) * x.element_size()), wrw)
+      keep = (dy, x) if lazy is None else (dy, x, pro[0], lazy)
+      dw = _filter_grad(graph, w, w_var, keep, 'depthwise_wrw' if lazy is None else 'depthwise_wrw_act', nbytes, wrw)
     if ctx.needs_input_grad[0]:
       dx = torch.empty_like(x)
-      with region('depthwise_bwd_data', float((x.numel() + dy.numel()) * x.element_size())):
-        hip.depthwise_bwd_data(dy, w.detach().reshape(C, k, k), dx, B, H, W, C, k, stride, ph, pw, Ho, Wo)
+      with region('depthwise_bwd_data', nbytes):
+        hip.depthwise_bwd_data(dy, w.detach().reshape(C, k, k), dx, *dims)
     return (dx, dw) + (None,) * 10
 
 
@@ -2350,8 +2317,7 @@ class DepthwiseConv2D:
     if g.taps is not None:
       return 'tap', x, None, None, None, None
     ph, pw, out_hw = self._geometry(x.shape)
-    if (OWN_DEPTHWISE and (x.is_cuda or DEPTHWISE_ANY_DEVICE) and x.dim() == 4 and x.dtype in (torch.float32, torch.bfloat16)
-        and w.dtype == x.dtype and hip.depthwise_supported(self.channels, self.k, self.stride)):
+    if self._takes(x):
       return 'own', x, (ph[0], pw[0]), out_hw, None, None
     x, pad = _symmetric_pads(x, ph, pw)
     return 'library', x, pad, None, None, None
@@ -2359,29 +2325,30 @@ class DepthwiseConv2D:
   def _call_tap(self, r, want_stats):
     return _tapped(self, r[ROUTE_X])
 
-  def _call_own(self, r, want_stats):
-    _, x, (ph, pw), (Ho, Wo), _, _ = r
-    w = self.kernel.tensor
-    if _wants_grad(w, x):
-      return _apply_with_stats(_Depthwise, x, w, self.stride, ph, pw, Ho, Wo, want_stats, self.graph, self.kernel)
-    return _run_depthwise(_nhwc(x), w, self.stride, ph, pw, Ho, Wo, want_stats)
+  def _takes(self, t) -> bool:
+    """Our kernels (pf_depthwise.hip) take this tensor: what the `own` route asks, and the `lazy` route of the raw tensor it reads."""
+    return (OWN_DEPTHWISE and (t.is_cuda or DEPTHWISE_ANY_DEVICE) and t.dim() == 4 and t.dtype in (torch.float32, torch.bfloat16)
+            and self.kernel.tensor.dtype == t.dtype and hip.depthwise_supported(self.channels, self.k, self.stride))
 
   def takes_lazy(self, t, quantised: bool) -> bool:
     """This layer will read the RAW tensor `t` behind a LazyAct and apply the producer itself: everything the `own` route asks, no
     tap, no packed kernel, a library (or test double) with the entry points, and the switch (dw_lazy_on)."""
-    w = self.kernel.tensor
-    return (OWN_DEPTHWISE and self.graph.taps is None and self.int8 is None and isinstance(t, torch.Tensor)
-            and (t.is_cuda or DEPTHWISE_ANY_DEVICE) and t.dim() == 4 and t.dtype in (torch.float32, torch.bfloat16)
-            and w.dtype == t.dtype and t.shape[1] == self.channels and hasattr(hip, 'depthwise_fwd_act')
-            and hasattr(hip, 'depthwise_wrw_act') and hip.depthwise_supported(self.channels, self.k, self.stride)
+    return (self.graph.taps is None and self.int8 is None and isinstance(t, torch.Tensor) and self._takes(t)
+            and t.shape[1] == self.channels and hasattr(hip, 'depthwise_fwd_act') and hasattr(hip, 'depthwise_wrw_act')
             and dw_lazy_on(self.channels, self.stride, quantised, t.dtype))
 
-  def _call_lazy(self, r, want_stats):
-    _, lazy, (ph, pw), (Ho, Wo), _, _ = r
-    w, x = self.kernel.tensor, lazy.x
+  def _call_own(self, r, want_stats):
+    """`own` and `lazy`: the record's tensor, or the LazyAct whose raw tensor the kernels read."""
+    name, x, (ph, pw), (Ho, Wo), _, _ = r
+    lazy = x if name == 'lazy' else None
+    if lazy is not None:
+      x = lazy.x
+    w = self.kernel.tensor
     if _wants_grad(w, x):
-      return _apply_with_stats(_DepthwiseAct, x, w, lazy, self.stride, ph, pw, Ho, Wo, want_stats, self.graph, self.kernel)
-    return _run_depthwise_act(x, lazy, w, self.stride, ph, pw, Ho, Wo, want_stats)
+      return _apply_with_stats(_Depthwise, x, w, lazy, self.stride, ph, pw, Ho, Wo, want_stats, self.graph, self.kernel)
+    return _run_depthwise(x if lazy is not None else _nhwc(x), lazy, w, self.stride, ph, pw, Ho, Wo, want_stats)
+
+  _call_lazy = _call_own
 
   def _call_library(self, r, want_stats):
     _, x, pad, _, _, _ = r

@@ -712,12 +712,16 @@ def depthwise_bwd_data(dY, W, dX, B: int, H: int, Wd: int, C: int, k: int, strid
          'pf_depthwise_bwd_data')
 
 
+def _dw_wrw_check(name: str, X, slabs, B: int, Ho: int, Wo: int, C: int, k: int) -> None:
+  _dev(X)
+  if slabs.dtype != torch.float32 or slabs.numel() < (depthwise_groups(B, Ho, Wo, C) + 32) * C * k * k:
+    raise TypeError('%s: float32 workspace of (groups + 32) * C * k * k elements' % name)
+
+
 def depthwise_wrw(dY, X, dW, slabs, B: int, H: int, Wd: int, C: int, k: int, stride: int, pad_h: int, pad_w: int, Ho: int,
                   Wo: int) -> None:
   """dW: [C][k][k], float32 or bf16; slabs: (depthwise_groups(B, Ho, Wo, C) + 32) * C * k * k floats."""
-  _dev(X)
-  if slabs.dtype != torch.float32 or slabs.numel() < (depthwise_groups(B, Ho, Wo, C) + 32) * C * k * k:
-    raise TypeError('depthwise_wrw: float32 workspace of (groups + 32) * C * k * k elements')
+  _dw_wrw_check('depthwise_wrw', X, slabs, B, Ho, Wo, C, k)
   _check(_lib.pf_depthwise_wrw(_ptr(dY), _ptr(X), _ptr(dW), c_int(dtype_code(X)), c_int(dtype_code(dW)), _ptr(slabs), c_int(B),
                                c_int(H), c_int(Wd), c_int(C), c_int(k), c_int(stride), c_int(pad_h), c_int(pad_w), c_int(Ho),
                                c_int(Wo), _stream()), 'pf_depthwise_wrw')
@@ -736,9 +740,7 @@ def depthwise_fwd_act(X, scale_shift, act, slot, bits: int, W, Y, B: int, H: int
 def depthwise_wrw_act(dY, X, scale_shift, act, slot, bits: int, dW, slabs, B: int, H: int, Wd: int, C: int, k: int, stride: int,
                       pad_h: int, pad_w: int, Ho: int, Wo: int) -> None:
   """depthwise_wrw with the same prologue on X; dW and slabs as there."""
-  _dev(X)
-  if slabs.dtype != torch.float32 or slabs.numel() < (depthwise_groups(B, Ho, Wo, C) + 32) * C * k * k:
-    raise TypeError('depthwise_wrw_act: float32 workspace of (groups + 32) * C * k * k elements')
+  _dw_wrw_check('depthwise_wrw_act', X, slabs, B, Ho, Wo, C, k)
   _check(_lib.pf_depthwise_wrw_act(_ptr(dY), _ptr(X), _ptr(scale_shift), c_int(ACT_CODES[act]), _ptr(slot), c_int(bits), _ptr(dW),
                                    c_int(dtype_code(X)), c_int(dtype_code(dW)), _ptr(slabs), c_int(B), c_int(H), c_int(Wd), c_int(C),
                                    c_int(k), c_int(stride), c_int(pad_h), c_int(pad_w), c_int(Ho), c_int(Wo), _stream()),

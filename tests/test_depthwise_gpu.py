@@ -236,3 +236,47 @@ def test_entries_refuse_tensors_of_2_to_the_31_bytes(hip):
   assert bwd(hip.PF_F32, 1, S, 1) == 0
   torch.cuda.synchronize()
   assert bool((y == 0.0).all())
+
+
+def test_plain_entries_refuse_what_they_cannot_run(hip):
+  """The plain twin of test_fused_entries_refuse_what_they_cannot_run (tests/test_depthwise_act_gpu.py): a null pointer, a tensor
+  4 bytes off a 16-byte boundary, unsupported C / k / stride, a front pad of 3, an unknown dtype code -- every one of the three C
+  entries returns non-zero before any launch and writes nothing; the same call sites with nothing wrong return 0 and fill their
+  outputs."""
+  from ctypes import c_int as I
+  B, H, W, C = 2, 6, 6, 16                                  # stride 1: front pads 1, Ho = Wo = 6
+  nan = lambda *shape: torch.full(shape, float('nan'), device='cuda')
+  x = torch.randn(B, H, W, C, device='cuda')                # NHWC memory; stands in for dY too
+  w = torch.randn(C, 3, 3, device='cuda')
+  G = hip.depthwise_groups(B, H, W, C)
+  y, dx, dw, partial, slabs = nan(B, H, W, C), nan(B, H, W, C), nan(C, 3, 3), nan(G, 4, C), nan((G + 32) * C * 9)
+  flat = torch.zeros(x.numel() + 4, device='cuda')
+  off = flat[1:1 + x.numel()]                               # 4 bytes off a 16-byte boundary
+  assert off.data_ptr() % 16 != 0
+  P, F32 = hip._ptr, hip.PF_F32
+
+  def geom(C_, k, stride, pad):
+    return [I(v) for v in (B, H, W, C_, k, stride, pad, pad, H, W)] + [hip._stream()]
+
+  def fwd(X=x, Wt=w, Y=y, dt=F32, C_=C, k=3, stride=1, pad=1):
+    return hip._lib.pf_depthwise_fwd(P(X), P(Wt), P(Y), I(dt), P(partial), *geom(C_, k, stride, pad))
+
+  def bwd(DY=x, Wt=w, DX=dx, dt=F32, C_=C, k=3, stride=1, pad=1):
+    return hip._lib.pf_depthwise_bwd_data(P(DY), P(Wt), P(DX), I(dt), *geom(C_, k, stride, pad))
+
+  def wrw(DY=x, X=x, DW=dw, SL=slabs, dt=F32, C_=C, k=3, stride=1, pad=1):
+    return hip._lib.pf_depthwise_wrw(P(DY), P(X), P(DW), I(dt), I(F32), P(SL), *geom(C_, k, stride, pad))
+  shape = (dict(C_=12), dict(C_=4), dict(C_=2056), dict(k=5), dict(stride=3), dict(stride=0), dict(pad=3), dict(dt=7))
+  for kw in (dict(X=None), dict(Wt=None), dict(Y=None), dict(X=off), dict(Y=off)) + shape:
+    assert fwd(**kw) != 0, kw
+  for kw in (dict(DY=None), dict(Wt=None), dict(DX=None), dict(DY=off), dict(DX=off)) + shape:
+    assert bwd(**kw) != 0, kw
+  for kw in (dict(DY=None), dict(X=None), dict(DW=None), dict(SL=None), dict(DY=off), dict(X=off)) + shape:
+    assert wrw(**kw) != 0, kw
+  torch.cuda.synchronize()
+  for t in (y, dx, dw, partial, slabs):
+    assert bool(torch.isnan(t).all())
+  assert fwd() == 0 and bwd() == 0 and wrw() == 0           # the same call sites with nothing wrong
+  torch.cuda.synchronize()
+  for t in (y, dx, dw, partial):
+    assert not torch.isnan(t).any()
