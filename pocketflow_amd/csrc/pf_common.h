@@ -25,6 +25,11 @@ typedef uint16_t bf16_t;
 // drives a second GPU, or launches first from another thread, is configured too (the caches were process-wide statics).
 int pf_require_lds(const void* fn, size_t lds);
 
+// The fixed-order fold of the S slabs of `n` floats a backward-filter kernel left at the head of `workspace` into dW (pf_conv.hip):
+// the ONE declaration for every file whose kernels write slabs (1x1, RxS, depthwise, the stems).  The workspace holds (S + 32) * n
+// floats, the slabs and the 32 partial sums of the staged reduction behind them (hip.wrw_workspace_floats).
+int pf_wrw_reduce(float* workspace, int S, int64_t n, void* dW, int dw_dtype, hipStream_t st);
+
 // ---- tuning / A-B switches (host) --------------------------------------------------------------
 // Every PF_* environment switch of the launchers is read ONCE, on first use, into this struct (pf_api.hip): a launcher and the
 // workspace-size query that precedes it always see the same decision, and no launch pays for getenv / atoi / sscanf.  Tools and

@@ -444,7 +444,6 @@ static int dw_launch(const DwArgs& a, int grid, int dtype, int act, hipStream_t 
   return 0;
 }
 
-int pf_wrw_reduce(float* workspace, int S, int64_t n, void* dW, int dw_dtype, hipStream_t st);   // pf_conv.hip
 
 static int dw_run(DwDir dir, const void* in, const void* other, void* out, float* partial, const DwPro* pro, int dtype, int dw_dtype,
                   const DwDims& d, void* stream) {

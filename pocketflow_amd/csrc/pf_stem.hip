@@ -13,27 +13,13 @@
 //     REGISTERS for the whole launch (4 channel blocks x 7 k-steps x 4 VGPRs); the MFMA row -> channel map is chosen
 //     such that a lane ends up with 16 CONSECUTIVE channels of its pixel: two 16-byte stores, no LDS transposition;
 //   * persistent workgroups (2 per CU) loop over (image, strip) items, so the weight packing is paid once.
-#include "pf_conv_common.h"
-#include "pf_buffer.h"
+#include "pf_stem.h"
 
-typedef short st_v4s __attribute__((ext_vector_type(4)));
-typedef short st_v8s __attribute__((ext_vector_type(8)));
-
-#define ST_THREADS 256
 #define ST_OROWS 8                      // output rows per item
 #define ST_IROWS (2 * ST_OROWS + 5)     // input rows staged per item
 #define ST_N 64
 #define ST_R 7
 #define ST_WL_BYTES (ST_N * ST_R * 32 * 2)
-
-struct StemArgs {
-  const bf16_t* X;   // [imgs][H][Wd][3]
-  const bf16_t* W;   // [64][7][7][3]
-  bf16_t* Y;         // [imgs][Ho][Wo][64]
-  int imgs, H, Wd, Ho, Wo;
-  int strips, n_items;
-  int rsb;           // LDS bytes per staged input row = (Wd + 8) * 8
-};
 
 __global__ __launch_bounds__(ST_THREADS) void k_stem7x7_fwd(StemArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -82,18 +68,10 @@ __global__ __launch_bounds__(ST_THREADS) void k_stem7x7_fwd(StemArgs a) {
     const int oy0 = strip * ST_OROWS, iy0 = 2 * oy0 - 3;
     __syncthreads();                                      // the previous item's fragment reads are done
     // ---- stage 21 input rows, 3 -> 4 channels ----
-    for (int row = tid >> 7; row < ST_IROWS; row += 2) {
+    for (int row = tid >> 7; row < ST_IROWS; row += 2) {     // (the first real pixel sits 24 bytes into the row: 8-byte stores)
       const int iy = iy0 + row;
-      unsigned char* dst = xs + (int64_t)row * a.rsb + 3 * 8;
       const bool live = iy >= 0 && iy < a.H;
-      const uint32_t* src = reinterpret_cast<const uint32_t*>(a.X + ((int64_t)img * a.H + (live ? iy : 0)) * a.Wd * 3);
-      for (int j = tid & 127; j < pairs; j += 128) {
-        uint32_t d0 = 0u, d1 = 0u, d2 = 0u;
-        if (live) { d0 = src[3 * j]; d1 = src[3 * j + 1]; d2 = src[3 * j + 2]; }
-        // (the first real pixel sits 24 bytes into the row: 8-byte stores)
-        *reinterpret_cast<uint2*>(dst + j * 16) = make_uint2(d0, d1 & 0xFFFFu);
-        *reinterpret_cast<uint2*>(dst + j * 16 + 8) = make_uint2((d1 >> 16) | (d2 << 16), d2 >> 16);
-      }
+      stem_stage_row(xs + (int64_t)row * a.rsb + 3 * 8, a.X + ((int64_t)img * a.H + (live ? iy : 0)) * a.Wd * 3, live, pairs, tid & 127, 128);
     }
     __syncthreads();
     // ---- 16-pixel x 64-channel units ----
@@ -132,20 +110,14 @@ extern "C" int pf_conv_stem_supported(int H, int Wd, int C, int N, int k, int st
 }
 
 extern "C" int pf_conv_stem_fwd(const void* X, const void* W, void* Y, int imgs, int H, int Wd, void* stream) {
-  if (!pf_conv_stem_supported(H, Wd, 3, ST_N, 7, 2, 3) || imgs <= 0) return (int)hipErrorInvalidValue;
-  if (!pf_aligned16(Y) || (reinterpret_cast<uintptr_t>(X) & 3u) || (reinterpret_cast<uintptr_t>(W) & 1u))
-    return (int)hipErrorInvalidValue;
   StemArgs a;
-  a.X = (const bf16_t*)X; a.W = (const bf16_t*)W; a.Y = (bf16_t*)Y;
-  a.imgs = imgs; a.H = H; a.Wd = Wd; a.Ho = H / 2; a.Wo = Wd / 2;
-  a.strips = (a.Ho + ST_OROWS - 1) / ST_OROWS;
-  a.n_items = imgs * a.strips;
-  a.rsb = (Wd + 8) * 8;
+  if (!pf_conv_stem_supported(H, Wd, 3, ST_N, 7, 2, 3) || imgs <= 0 || !stem_fill(a, X, Y, W, imgs, H, Wd, H / 2, Wd / 2, ST_OROWS))
+    return (int)hipErrorInvalidValue;
+  a.W = (const bf16_t*)W; a.Y = (bf16_t*)Y;
   const size_t lds = (size_t)ST_WL_BYTES + (size_t)ST_IROWS * a.rsb;
   if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
   if (int e = pf_require_lds(reinterpret_cast<const void*>(&k_stem7x7_fwd), lds)) return e;
-  const int grid = a.n_items < 512 ? a.n_items : 512;
-  k_stem7x7_fwd<<<grid, ST_THREADS, lds, (hipStream_t)stream>>>(a);
+  k_stem7x7_fwd<<<stem_grid(a.n_items, 512), ST_THREADS, lds, (hipStream_t)stream>>>(a);
   PF_LAUNCH_CHECK();
   return 0;
 }
@@ -167,16 +139,6 @@ extern "C" int pf_conv_stem_fwd(const void* X, const void* W, void* Y, int imgs,
 // over all (image, strip) items of the persistent workgroup; one fp32 slab [64][147] per workgroup, summed in a fixed
 // order by pf_wrw_reduce (deterministic).
 // =================================================================================================================
-struct StemWrwArgs {
-  const bf16_t* dY;  // [imgs][Ho][Wo][64]
-  const bf16_t* X;   // [imgs][H][Wd][3]
-  float* slabs;      // [S][64][147]
-  int imgs, H, Wd, Ho, Wo;
-  int strips, n_items;
-  int rsb;           // LDS bytes per staged input row
-  int dy_bytes;
-};
-
 #define SW_OROWS 2
 #define SW_IROWS (2 * SW_OROWS + 5)
 
@@ -224,15 +186,8 @@ __global__ __launch_bounds__(ST_THREADS) void k_stem7x7_wrw(StemWrwArgs a) {
     // ---- X: 9 input rows, 3 -> 4 channels ----
     for (int row = tid >> 7; row < SW_IROWS; row += 2) {
       const int iy = iy0 + row;
-      unsigned char* dst = xs + (int64_t)row * a.rsb + 3 * 8;
       const bool live = iy >= 0 && iy < a.H;
-      const uint32_t* src = reinterpret_cast<const uint32_t*>(a.X + ((int64_t)img * a.H + (live ? iy : 0)) * a.Wd * 3);
-      for (int j = tid & 127; j < pairs; j += 128) {
-        uint32_t d0 = 0u, d1 = 0u, d2 = 0u;
-        if (live) { d0 = src[3 * j]; d1 = src[3 * j + 1]; d2 = src[3 * j + 2]; }
-        *reinterpret_cast<uint2*>(dst + j * 16) = make_uint2(d0, d1 & 0xFFFFu);
-        *reinterpret_cast<uint2*>(dst + j * 16 + 8) = make_uint2((d1 >> 16) | (d2 << 16), d2 >> 16);
-      }
+      stem_stage_row(xs + (int64_t)row * a.rsb + 3 * 8, a.X + ((int64_t)img * a.H + (live ? iy : 0)) * a.Wd * 3, live, pairs, tid & 127, 128);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -300,32 +255,19 @@ __global__ __launch_bounds__(ST_THREADS) void k_stem7x7_wrw(StemWrwArgs a) {
   }
 }
 
-int pf_wrw_reduce(float* workspace, int S, int64_t n, void* dW, int dw_dtype, hipStream_t st);   // pf_conv.hip
-
-static int stem_wrw_grid(int imgs, int H) {
-  const int items = imgs * ((H / 2 + SW_OROWS - 1) / SW_OROWS);
-  return items < 768 ? items : 768;
-}
-
-// number of fp32 slabs pf_conv_stem_wrw writes; the workspace must hold (slabs + 32) * 64 * 147 floats (0: unsupported)
+// number of fp32 slabs pf_conv_stem_wrw writes, one per workgroup, for pf_wrw_reduce and its workspace contract (0: unsupported)
 extern "C" int pf_conv_stem_wrw_slabs(int imgs, int H, int Wd) {
-  if (!pf_conv_stem_supported(H, Wd, 3, ST_N, 7, 2, 3) || imgs <= 0 || Wd > 256) return 0;
-  if ((int64_t)imgs * (H / 2) * (Wd / 2) * ST_N * 2 >= (int64_t)1 << 31) return 0;
-  return stem_wrw_grid(imgs, H);
+  if (!pf_conv_stem_supported(H, Wd, 3, ST_N, 7, 2, 3) || imgs <= 0 || Wd > 256 || !stem_dy_fits(imgs, H / 2, Wd / 2, ST_N)) return 0;
+  return stem_grid(imgs * stem_strips(H / 2, SW_OROWS), 768);
 }
 
 extern "C" int pf_conv_stem_wrw(const void* dY, const void* X, void* dW, int dw_dtype, float* workspace, int imgs, int H,
                                 int Wd, void* stream) {
   const int S = pf_conv_stem_wrw_slabs(imgs, H, Wd);
-  if (S <= 0 || workspace == nullptr) return (int)hipErrorInvalidValue;
-  if (!pf_aligned16(dY) || (reinterpret_cast<uintptr_t>(X) & 3u)) return (int)hipErrorInvalidValue;
   StemWrwArgs a;
-  a.dY = (const bf16_t*)dY; a.X = (const bf16_t*)X; a.slabs = workspace;
-  a.imgs = imgs; a.H = H; a.Wd = Wd; a.Ho = H / 2; a.Wo = Wd / 2;
-  a.strips = (a.Ho + SW_OROWS - 1) / SW_OROWS;
-  a.n_items = imgs * a.strips;
-  a.rsb = (Wd + 8) * 8;
-  a.dy_bytes = (int)((int64_t)imgs * a.Ho * a.Wo * ST_N * 2);
+  if (S <= 0 || workspace == nullptr || !stem_fill(a, X, dY, nullptr, imgs, H, Wd, H / 2, Wd / 2, SW_OROWS)) return (int)hipErrorInvalidValue;
+  a.dY = (const bf16_t*)dY; a.slabs = workspace;
+  a.dy_bytes = (int)stem_dy_bytes(imgs, a.Ho, a.Wo, ST_N);
   const size_t lds = (size_t)SW_IROWS * a.rsb + (size_t)SW_OROWS * a.Wo * ST_N * 2;
   if (int e = pf_require_lds(reinterpret_cast<const void*>(&k_stem7x7_wrw), lds)) return e;
   k_stem7x7_wrw<<<S, ST_THREADS, lds, (hipStream_t)stream>>>(a);

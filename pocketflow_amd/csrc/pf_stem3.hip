@@ -18,39 +18,14 @@
 //   * backward-filter: both operands are pixel-major and the contraction runs over pixels, so both are fetched with the transposing LDS
 //     read ds_read_b64_tr_b16 exactly as in k_stem7x7_wrw -- dY in [8 pixels][16 channels] blocks filled by LDS-DMA, X pieces = one
 //     padded pixel each; float32 slabs [N][27] per workgroup, summed in a fixed order by pf_wrw_reduce (deterministic).
-#include "pf_conv_common.h"
-#include "pf_buffer.h"
+#include "pf_stem.h"
 
-typedef short s3_v4s __attribute__((ext_vector_type(4)));
-typedef short s3_v8s __attribute__((ext_vector_type(8)));
-
-#define S3_THREADS 256
 #define S3_OROWS 8                      // forward: output rows per item
 #define S3_IROWS (2 * S3_OROWS + 1)     // input rows staged per item
 #define S3_R 3
 
-struct Stem3Args {
-  const bf16_t* X;   // [imgs][H][Wd][3]
-  const bf16_t* W;   // [N][3][3][3]
-  bf16_t* Y;         // [imgs][Ho][Wo][N]
-  int imgs, H, Wd, Ho, Wo, ph, pw;
-  int strips, n_items;
-  int rsb;           // LDS bytes per staged input row = (Wd + 8) * 8
-};
-
-// one staged input row: Wd pixels of 3 channels -> 4 channels at LDS pixel pw.. (the halo pixels are zeroed once per workgroup)
-__device__ __forceinline__ void s3_stage_row(unsigned char* dst, const bf16_t* X, int64_t row_elems_off, bool live, int pairs, int t0, int tstep) {
-  const uint32_t* src = reinterpret_cast<const uint32_t*>(X + (live ? row_elems_off : 0));
-  for (int j = t0; j < pairs; j += tstep) {         // two pixels (12 bytes) per task
-    uint32_t d0 = 0u, d1 = 0u, d2 = 0u;
-    if (live) { d0 = src[3 * j]; d1 = src[3 * j + 1]; d2 = src[3 * j + 2]; }
-    *reinterpret_cast<uint2*>(dst + j * 16) = make_uint2(d0, d1 & 0xFFFFu);
-    *reinterpret_cast<uint2*>(dst + j * 16 + 8) = make_uint2((d1 >> 16) | (d2 << 16), d2 >> 16);
-  }
-}
-
 template <int NB>
-__global__ __launch_bounds__(S3_THREADS) void k_stem3x3_fwd(Stem3Args a) {
+__global__ __launch_bounds__(ST_THREADS) void k_stem3x3_fwd(Stem3Args a) {
   constexpr int N = 16 * NB;
   constexpr int WL_BYTES = N * S3_R * 32 * 2;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -60,7 +35,7 @@ __global__ __launch_bounds__(S3_THREADS) void k_stem3x3_fwd(Stem3Args a) {
   const int l16 = lane & 15, g = lane >> 4;
 
   // ---- pack the weights: chunk (n, r, q) = taps (2q, 2q+1) x 4 channels of kernel row r of output channel n ----
-  for (int ch = tid; ch < N * S3_R * 4; ch += S3_THREADS) {
+  for (int ch = tid; ch < N * S3_R * 4; ch += ST_THREADS) {
     const int q = ch & 3, nr = ch >> 2;                   // nr = n*3 + r
     uint32_t v[4] = {0u, 0u, 0u, 0u};
     if (q < 2) {
@@ -75,7 +50,7 @@ __global__ __launch_bounds__(S3_THREADS) void k_stem3x3_fwd(Stem3Args a) {
     *reinterpret_cast<uint4*>(wl + ((int64_t)nr * 32 + q * 8) * 2) = make_uint4(v[0], v[1], v[2], v[3]);
   }
   // ---- zero the halo pixels of every staged row once: LDS pixels [0, pw) and [pw + Wd, Wd + 8) ----
-  for (int t = tid; t < S3_IROWS * 8; t += S3_THREADS) {
+  for (int t = tid; t < S3_IROWS * 8; t += ST_THREADS) {
     const int row = t >> 3, h = t & 7;
     const int pp = h < a.pw ? h : a.Wd + h;
     *reinterpret_cast<uint2*>(xs + (int64_t)row * a.rsb + pp * 8) = make_uint2(0u, 0u);
@@ -100,10 +75,10 @@ __global__ __launch_bounds__(S3_THREADS) void k_stem3x3_fwd(Stem3Args a) {
     __syncthreads();                                      // the previous item's fragment reads are done
     for (int row = tid >> 7; row < S3_IROWS; row += 2) {
       const int iy = iy0 + row;
-      s3_stage_row(xs + (int64_t)row * a.rsb + a.pw * 8, a.X, ((int64_t)img * a.H + iy) * a.Wd * 3, iy >= 0 && iy < a.H, pairs, tid & 127, 128);
+      stem_stage_row(xs + (int64_t)row * a.rsb + a.pw * 8, a.X, ((int64_t)img * a.H + iy) * a.Wd * 3, iy >= 0 && iy < a.H, pairs, tid & 127, 128);
     }
     __syncthreads();
-    for (int u = wave; u < units; u += S3_THREADS / 64) {
+    for (int u = wave; u < units; u += ST_THREADS / 64) {
       const int orow = u / pblocks, pb = u - orow * pblocks;
       const int oy = oy0 + orow;
       if (oy >= a.Ho) continue;
@@ -145,21 +120,17 @@ extern "C" int pf_conv_stem3_supported(int H, int Wd, int C, int N, int k, int s
 
 extern "C" int pf_conv_stem3_fwd(const void* X, const void* W, void* Y, int imgs, int H, int Wd, int N, int pad_h, int pad_w, int Ho,
                                  int Wo, void* stream) {
-  if (!s3_shape_ok(H, Wd, 3, N, 3, 2, pad_h, pad_w, Ho, Wo) || imgs <= 0) return (int)hipErrorInvalidValue;
-  if (!pf_aligned16(Y) || (reinterpret_cast<uintptr_t>(X) & 3u) || (reinterpret_cast<uintptr_t>(W) & 1u)) return (int)hipErrorInvalidValue;
   Stem3Args a;
-  a.X = (const bf16_t*)X; a.W = (const bf16_t*)W; a.Y = (bf16_t*)Y;
-  a.imgs = imgs; a.H = H; a.Wd = Wd; a.Ho = Ho; a.Wo = Wo; a.ph = pad_h; a.pw = pad_w;
-  a.strips = (Ho + S3_OROWS - 1) / S3_OROWS;
-  a.n_items = imgs * a.strips;
-  a.rsb = (Wd + 8) * 8;
+  if (!s3_shape_ok(H, Wd, 3, N, 3, 2, pad_h, pad_w, Ho, Wo) || imgs <= 0 || !stem_fill(a, X, Y, W, imgs, H, Wd, Ho, Wo, S3_OROWS))
+    return (int)hipErrorInvalidValue;
+  a.W = (const bf16_t*)W; a.Y = (bf16_t*)Y; a.ph = pad_h; a.pw = pad_w;
   const size_t lds = (size_t)N * S3_R * 64 + (size_t)S3_IROWS * a.rsb + 16;
   if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
   const void* fn = (N == 32) ? reinterpret_cast<const void*>(&k_stem3x3_fwd<2>) : reinterpret_cast<const void*>(&k_stem3x3_fwd<1>);
   if (int e = pf_require_lds(fn, lds)) return e;
-  const int grid = a.n_items < 1024 ? a.n_items : 1024;
-  if (N == 32) k_stem3x3_fwd<2><<<grid, S3_THREADS, lds, (hipStream_t)stream>>>(a);
-  else k_stem3x3_fwd<1><<<grid, S3_THREADS, lds, (hipStream_t)stream>>>(a);
+  const int grid = stem_grid(a.n_items, 1024);
+  if (N == 32) k_stem3x3_fwd<2><<<grid, ST_THREADS, lds, (hipStream_t)stream>>>(a);
+  else k_stem3x3_fwd<1><<<grid, ST_THREADS, lds, (hipStream_t)stream>>>(a);
   PF_LAUNCH_CHECK();
   return 0;
 }
@@ -168,21 +139,11 @@ extern "C" int pf_conv_stem3_fwd(const void* X, const void* W, void* Y, int imgs
 // Backward-filter:  dW[n][r][s][c] = sum over (img, oy, ox) of dY[img][oy][ox][n] * X[img][2oy + r - ph][2ox + s - pw][c]
 // Wavefront w: channel block w % NB, kernel rows {0, 1} / {2} (N = 32) or row w (N = 16; the fourth wavefront only stages).
 // =================================================================================================================
-struct Stem3WrwArgs {
-  const bf16_t* dY;  // [imgs][Ho][Wo][N]
-  const bf16_t* X;   // [imgs][H][Wd][3]
-  float* slabs;      // [S][N][27]
-  int imgs, H, Wd, Ho, Wo, ph, pw;
-  int strips, n_items;
-  int rsb;
-  int dy_bytes;
-};
-
 #define S3W_OROWS 2
 #define S3W_IROWS (2 * S3W_OROWS + 1)
 
 template <int NB>
-__global__ __launch_bounds__(S3_THREADS) void k_stem3x3_wrw(Stem3WrwArgs a) {
+__global__ __launch_bounds__(ST_THREADS) void k_stem3x3_wrw(Stem3WrwArgs a) {
   constexpr int N = 16 * NB;
   constexpr int PGI = 4 / NB;                               // pixel groups (of 8) per LDS-DMA instruction
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -206,7 +167,7 @@ __global__ __launch_bounds__(S3_THREADS) void k_stem3x3_wrw(Stem3WrwArgs a) {
   f32x4 acc[2];
   acc[0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[1] = acc[0];
 
-  for (int t = tid; t < S3W_IROWS * 8; t += S3_THREADS) {   // halo pixels, once
+  for (int t = tid; t < S3W_IROWS * 8; t += ST_THREADS) {   // halo pixels, once
     const int row = t >> 3, h = t & 7;
     const int pp = h < a.pw ? h : a.Wd + h;
     *reinterpret_cast<uint2*>(xs + (int64_t)row * a.rsb + pp * 8) = make_uint2(0u, 0u);
@@ -219,7 +180,7 @@ __global__ __launch_bounds__(S3_THREADS) void k_stem3x3_wrw(Stem3WrwArgs a) {
     const int64_t m_base = ((int64_t)img * a.Ho + oy0) * a.Wo;
     __syncthreads();                                        // the previous item's reads are done
     // ---- dY: steps x 4 pixel groups x NB channel blocks, one LDS-DMA instruction per KiB ----
-    for (int id = wave; id < steps * NB; id += S3_THREADS / 64) {
+    for (int id = wave; id < steps * NB; id += ST_THREADS / 64) {
       const int lin = (id * PGI + spg) * 8 + srow;
       const uint32_t voff = (lin < valid_px) ? (uint32_t)(((m_base + lin) * N + 16 * sb + 8 * sch) * 2) : OOB;
       PF_BUFFER_LOAD_LDS16(rsY, dys + id * 1024, voff, 0);
@@ -227,18 +188,18 @@ __global__ __launch_bounds__(S3_THREADS) void k_stem3x3_wrw(Stem3WrwArgs a) {
     // ---- X: 5 input rows, 3 -> 4 channels ----
     for (int row = tid >> 7; row < S3W_IROWS; row += 2) {
       const int iy = iy0 + row;
-      s3_stage_row(xs + (int64_t)row * a.rsb + a.pw * 8, a.X, ((int64_t)img * a.H + iy) * a.Wd * 3, iy >= 0 && iy < a.H, pairs, tid & 127, 128);
+      stem_stage_row(xs + (int64_t)row * a.rsb + a.pw * 8, a.X, ((int64_t)img * a.H + iy) * a.Wd * 3, iy >= 0 && iy < a.H, pairs, tid & 127, 128);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     // ---- 32 pixels per step ----
     for (int st = 0; st < steps; ++st) {
       const unsigned char* dbase = dys + st * (4 * NB * 256);
-      const s3_v4s dlo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-          (__attribute__((address_space(3))) s3_v4s*)(dbase + (pg_lo * NB + nb0) * 256 + tr_off));
-      const s3_v4s dhi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-          (__attribute__((address_space(3))) s3_v4s*)(dbase + ((pg_lo + 2) * NB + nb0) * 256 + tr_off));
-      s3_v8s d8;
+      const st_v4s dlo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+          (__attribute__((address_space(3))) st_v4s*)(dbase + (pg_lo * NB + nb0) * 256 + tr_off));
+      const st_v4s dhi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+          (__attribute__((address_space(3))) st_v4s*)(dbase + ((pg_lo + 2) * NB + nb0) * 256 + tr_off));
+      st_v8s d8;
       d8[0] = dlo[0]; d8[1] = dlo[1]; d8[2] = dlo[2]; d8[3] = dlo[3];
       d8[4] = dhi[0]; d8[5] = dhi[1]; d8[6] = dhi[2]; d8[7] = dhi[3];
       const bf16x8 df = *reinterpret_cast<const bf16x8*>(&d8);
@@ -252,9 +213,9 @@ __global__ __launch_bounds__(S3_THREADS) void k_stem3x3_wrw(Stem3WrwArgs a) {
 #pragma unroll
       for (int rr = 0; rr < 2; ++rr) {
         if (rr < nr) {
-          const s3_v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s3_v4s*)(xlo + (int64_t)rr * a.rsb));
-          const s3_v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s3_v4s*)(xhi + (int64_t)rr * a.rsb));
-          s3_v8s x8;
+          const st_v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) st_v4s*)(xlo + (int64_t)rr * a.rsb));
+          const st_v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) st_v4s*)(xhi + (int64_t)rr * a.rsb));
+          st_v8s x8;
           x8[0] = lo[0]; x8[1] = lo[1]; x8[2] = lo[2]; x8[3] = lo[3];
           x8[4] = hi[0]; x8[5] = hi[1]; x8[6] = hi[2]; x8[7] = hi[3];
           const bf16x8 xf = *reinterpret_cast<const bf16x8*>(&x8);
@@ -275,37 +236,24 @@ __global__ __launch_bounds__(S3_THREADS) void k_stem3x3_wrw(Stem3WrwArgs a) {
   }
 }
 
-int pf_wrw_reduce(float* workspace, int S, int64_t n, void* dW, int dw_dtype, hipStream_t st);   // pf_conv.hip
-
-static int s3_wrw_grid(int imgs, int Ho) {
-  const int items = imgs * ((Ho + S3W_OROWS - 1) / S3W_OROWS);
-  return items < 768 ? items : 768;
-}
-
-// number of fp32 slabs pf_conv_stem3_wrw writes; the workspace must hold (slabs + 32) * N * 27 floats (0: unsupported)
+// number of fp32 slabs pf_conv_stem3_wrw writes, one per workgroup, for pf_wrw_reduce and its workspace contract (0: unsupported)
 extern "C" int pf_conv_stem3_wrw_slabs(int imgs, int H, int Wd, int N, int pad_h, int pad_w, int Ho, int Wo) {
-  if (!s3_shape_ok(H, Wd, 3, N, 3, 2, pad_h, pad_w, Ho, Wo) || imgs <= 0 || Wd > 512) return 0;
-  if ((int64_t)imgs * Ho * Wo * N * 2 >= (int64_t)1 << 31) return 0;
-  return s3_wrw_grid(imgs, Ho);
+  if (!s3_shape_ok(H, Wd, 3, N, 3, 2, pad_h, pad_w, Ho, Wo) || imgs <= 0 || Wd > 512 || !stem_dy_fits(imgs, Ho, Wo, N)) return 0;
+  return stem_grid(imgs * stem_strips(Ho, S3W_OROWS), 768);
 }
 
 extern "C" int pf_conv_stem3_wrw(const void* dY, const void* X, void* dW, int dw_dtype, float* workspace, int imgs, int H, int Wd, int N,
                                  int pad_h, int pad_w, int Ho, int Wo, void* stream) {
   const int S = pf_conv_stem3_wrw_slabs(imgs, H, Wd, N, pad_h, pad_w, Ho, Wo);
-  if (S <= 0 || workspace == nullptr) return (int)hipErrorInvalidValue;
-  if (!pf_aligned16(dY) || (reinterpret_cast<uintptr_t>(X) & 3u)) return (int)hipErrorInvalidValue;
   Stem3WrwArgs a;
-  a.dY = (const bf16_t*)dY; a.X = (const bf16_t*)X; a.slabs = workspace;
-  a.imgs = imgs; a.H = H; a.Wd = Wd; a.Ho = Ho; a.Wo = Wo; a.ph = pad_h; a.pw = pad_w;
-  a.strips = (Ho + S3W_OROWS - 1) / S3W_OROWS;
-  a.n_items = imgs * a.strips;
-  a.rsb = (Wd + 8) * 8;
-  a.dy_bytes = (int)((int64_t)imgs * Ho * Wo * N * 2);
+  if (S <= 0 || workspace == nullptr || !stem_fill(a, X, dY, nullptr, imgs, H, Wd, Ho, Wo, S3W_OROWS)) return (int)hipErrorInvalidValue;
+  a.dY = (const bf16_t*)dY; a.slabs = workspace; a.ph = pad_h; a.pw = pad_w;
+  a.dy_bytes = (int)stem_dy_bytes(imgs, Ho, Wo, N);
   const size_t lds = (size_t)S3W_IROWS * a.rsb + (size_t)S3W_OROWS * Wo * N * 2 + 16;
   const void* fn = (N == 32) ? reinterpret_cast<const void*>(&k_stem3x3_wrw<2>) : reinterpret_cast<const void*>(&k_stem3x3_wrw<1>);
   if (int e = pf_require_lds(fn, lds)) return e;
-  if (N == 32) k_stem3x3_wrw<2><<<S, S3_THREADS, lds, (hipStream_t)stream>>>(a);
-  else k_stem3x3_wrw<1><<<S, S3_THREADS, lds, (hipStream_t)stream>>>(a);
+  if (N == 32) k_stem3x3_wrw<2><<<S, ST_THREADS, lds, (hipStream_t)stream>>>(a);
+  else k_stem3x3_wrw<1><<<S, ST_THREADS, lds, (hipStream_t)stream>>>(a);
   PF_LAUNCH_CHECK();
   return pf_wrw_reduce(workspace, S, (int64_t)N * 27, dW, dw_dtype, (hipStream_t)stream);
 }

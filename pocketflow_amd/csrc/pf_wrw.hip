@@ -710,7 +710,6 @@ int pf_wrw2_launch(const void* dY, const void* X, float* slabs, const float* sca
 }
 
 // ---- RxS backward-filter behind the C ABI ------------------------------------------------------------------------
-int pf_wrw_reduce(float* workspace, int S, int64_t n, void* dW, int dw_dtype, hipStream_t st);   // pf_conv.hip
 
 // pf_wrw3x3_c64.hip: the window-staged kernel for 3x3 / stride 1, 64 -> 64 channels on 56 x 56 maps
 bool pf_wrw3x3_c64_geom(int H, int Wd, int C, int N, int th, int tw, int stride, int pad_h, int pad_w, int Ho, int Wo);

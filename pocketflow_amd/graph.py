@@ -27,6 +27,7 @@ kernels, [in, out] dense) so that checkpoints and the oracle see TF-shaped tenso
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 import math
 import os
@@ -41,6 +42,7 @@ import torch.nn.functional as F
 from pocketflow_amd import hip
 from pocketflow_amd.hip import check_gather
 from pocketflow_amd.hip import bn_vector_ok as _bn_vector_ok   # bound here: the tests' stand-ins for `hip` emulate launches only
+from pocketflow_amd.hip import wrw_workspace_floats as _wrw_floats
 from pocketflow_amd.plan import WeightDesc
 from pocketflow_amd.profiling import region
 
@@ -1178,8 +1180,7 @@ def _out_size(size: int, k: int, stride: int, pad_total: int) -> int:
 
 
 def _wants_grad(w, x=None) -> bool:
-  """A layer call takes part in the backward pass: gradients are enabled and the kernel `w` or the input `x` asks for one.  (Without
-  `x`: the MobileNet stem, whose image never does.)"""
+  """A layer call takes part in the backward pass: gradients are enabled and the kernel `w` or the input `x` asks for one."""
   return torch.is_grad_enabled() and (w.requires_grad or (x is not None and x.requires_grad))
 
 
@@ -1315,7 +1316,7 @@ class _FusedConv1x1(torch.autograd.Function):
       S = hip.conv1x1_wrw_splits(M, N, K)
 
       def wrw(dwk, scratch):                     # dwk: [N][1][1][K] memory = [N][K]
-        hip.conv1x1_wrw(dy, x, dwk.view(N, K), scratch((S + 32) * N * K), M, N, K, scale_shift=ss, act=act,
+        hip.conv1x1_wrw(dy, x, dwk.view(N, K), scratch(_wrw_floats(S, N * K)), M, N, K, scale_shift=ss, act=act,
                         slot=lazy.slot if quant else None, bits=lazy.bits if quant else 8, geom=geom)
       # (everything the launch reads stays referenced until the join: the producer BN's constants belong to ITS autograd node, which
       # runs -- and frees them -- on the main stream right after this function returns)
@@ -1449,7 +1450,7 @@ class _Conv2dIgemm(torch.autograd.Function):
       nbytes = float((x.numel() + dy.numel()) * 2)
       if splits > 0:
         def wrw(dwk, scratch):
-          hip.conv2d_wrw(dy, x, dwk, scratch((splits + 32) * N * R * S * C), B, H, W, C, N, R, S, stride, pad[0], pad[1], Ho, Wo)
+          hip.conv2d_wrw(dy, x, dwk, scratch(_wrw_floats(splits, N * R * S * C)), B, H, W, C, N, R, S, stride, pad[0], pad[1], Ho, Wo)
         dw = _filter_grad(graph, w, ctx.w_var, (dy, x), 'conv2d_wrw', nbytes, wrw)
       elif OWN_CONV2D_WRW and OWN_CONV_GENERIC and x.is_cuda and dy.dtype == x.dtype and w.dtype == x.dtype:
         # fewer than 2 048 output pixels (the 64 x 64 test networks): too few steps for the pixel-split MFMA kernels -- the general
@@ -1615,7 +1616,7 @@ class _ConvIm2col(torch.autograd.Function):
       splits = hip.conv1x1_wrw_splits(M, N, K)
 
       def wrw(dwk, scratch):                     # dwk: [N][R][S][C] memory = [N][K]
-        hip.conv1x1_wrw(dy, xcol, dwk.view(N, K), scratch((splits + 32) * N * K), M, N, K)
+        hip.conv1x1_wrw(dy, xcol, dwk.view(N, K), scratch(_wrw_floats(splits, N * K)), M, N, K)
       dw = _filter_grad(graph, w, w_var, (dy, xcol), 'conv_im2col_wrw', float((M * K + M * N) * 2), wrw)
     if ctx.needs_input_grad[0]:
       dxcol = torch.empty((M, K), dtype=x.dtype, device=x.device)
@@ -1634,88 +1635,76 @@ def im2col_conv_ok(x, conv, pad) -> bool:
           and x.shape[0] * x.shape[2] * x.shape[3] * kh * kw * cin < (1 << 31))
 
 
-def _run_stem(x, w):
-  """x: the image batch, logical NCHW / physical NHWC bf16; w: logical [64][3][7][7] over KRSC memory."""
+# One stem route (Conv2D._route builds it once per call): `k` names the kernel family -- 7: the ResNet stem, 7x7 / stride 2 / pad 3,
+# 3 -> 64 channels on pf_stem.hip; 3: the MobileNet stem, 3x3 / stride 2 / 'SAME', 3 -> 16 | 32 on pf_stem3.hip --, `pads` are the FRONT
+# pads (pad_h, pad_w) and `out_hw` the output size.  Neither family reads a padded copy of the image.
+StemGeom = collections.namedtuple('StemGeom', 'k pads out_hw')
+
+
+def _run_stem(x, w, geom):
+  """x: the image batch, logical NCHW / physical NHWC bf16; w: logical [N][3][k][k] over KRSC memory; geom: the StemGeom."""
   B, _, H, Wd = x.shape
-  y = torch.empty((B, w.shape[0], H // 2, Wd // 2), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+  N = w.shape[0]
+  Ho, Wo = geom.out_hw
+  y = torch.empty((B, N, Ho, Wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
   with region('conv_stem_fwd', float((x.numel() + y.numel()) * 2)):
-    hip.conv_stem_fwd(x, w.detach().permute(0, 2, 3, 1), y, B, H, Wd)
+    if geom.k == 7:
+      hip.conv_stem_fwd(x, w.detach().permute(0, 2, 3, 1), y, B, H, Wd)
+    else:
+      hip.conv_stem3_fwd(x, w.detach().permute(0, 2, 3, 1), y, B, H, Wd, N, geom.pads[0], geom.pads[1], Ho, Wo)
   return y
 
 
 class _StemConv(torch.autograd.Function):
-  """The ResNet stem (7x7 / stride 2 / pad 3, 3 -> 64 channels) on pf_conv_stem_fwd / pf_conv_stem_wrw (the image needs
-  no gradient; if it does, backward-data goes through MIOpen)."""
+  """The first-layer convolution of an image on pf_conv_stem[3]_fwd / pf_conv_stem[3]_wrw.  The two kernel families were written
+  apart, and backward differs between them in three ways that are kept as they are (tests/test_conv_routes_cpu.py pins each):
+
+    family   PF_OWN_CONV2D_WRW=0            the backward-filter kernel refuses        the image asks for a gradient
+    7x7      honoured: the library's dW     the library's dW                          the library's backward-data
+    3x3      ignored: the kernel's dW       RuntimeError                              RuntimeError (Conv2D._route gives such an
+                                                                                      image to another route in the first place)
+
+  (round 4 ran the 3x3 layer on the general kernel over F.pad(image): 361 + 878 us per step against 148 / 119 us for MIOpen.)"""
 
   @staticmethod
-  def forward(ctx, x, w, graph, w_var):
+  def forward(ctx, x, w, graph, w_var, geom):
     ctx.save_for_backward(x, w)
-    ctx.meta = (graph, w_var)
-    return _run_stem(x, w)
+    ctx.meta = (graph, w_var, geom)
+    return _run_stem(x, w, geom)
 
   @staticmethod
   def backward(ctx, dy):
     x, w = ctx.saved_tensors
-    graph, w_var = ctx.meta
+    graph, w_var, geom = ctx.meta
     dy = _nhwc(dy)
     dx = dw = None
     if ctx.needs_input_grad[1]:
       B, _, H, Wd = x.shape
-      S = hip.conv_stem_wrw_slabs(B, H, Wd) if OWN_CONV2D_WRW else 0
+      N = w.shape[0]
       nbytes = float((x.numel() + dy.numel()) * 2)
+      if geom.k == 7:
+        S = hip.conv_stem_wrw_slabs(B, H, Wd) if OWN_CONV2D_WRW else 0
+      else:
+        dims = (B, H, Wd, N, geom.pads[0], geom.pads[1]) + tuple(geom.out_hw)
+        S = hip.conv_stem3_wrw_slabs(*dims)
+        if S <= 0:
+          raise RuntimeError('pf_conv_stem3_wrw does not take the shape its forward kernel took')
       if S > 0:
         def wrw(dwk, scratch):
-          hip.conv_stem_wrw(dy, x, dwk, scratch((S + 32) * 64 * 147), B, H, Wd)
+          ws = scratch(_wrw_floats(S, w.numel()))    # slabs of [N][k][k][3]
+          if geom.k == 7:
+            hip.conv_stem_wrw(dy, x, dwk, ws, B, H, Wd)
+          else:
+            hip.conv_stem3_wrw(dy, x, dwk, ws, *dims)
         dw = _filter_grad(graph, w, w_var, (dy, x), 'conv_stem_wrw', nbytes, wrw)
       else:
         with region('conv_stem_wrw', nbytes):
-          dw = _library_conv_backward(dy, x, w, 2, (3, 3), 1)
+          dw = _library_conv_backward(dy, x, w, 2, geom.pads, 1)
     if ctx.needs_input_grad[0]:
-      dx = _library_conv_backward(dy, x, w, 2, (3, 3), 0)
-    return dx, dw, None, None
-
-
-def _run_stem3(x, w, pads, out_hw):
-  """x: the image batch, logical NCHW / physical NHWC bf16; w: logical [N][3][3][3] over KRSC memory; pads: the FRONT pads."""
-  B, _, H, Wd = x.shape
-  N = w.shape[0]
-  Ho, Wo = out_hw
-  y = torch.empty((B, N, Ho, Wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-  with region('conv_stem_fwd', float((x.numel() + y.numel()) * 2)):
-    hip.conv_stem3_fwd(x, w.detach().permute(0, 2, 3, 1), y, B, H, Wd, N, pads[0], pads[1], Ho, Wo)
-  return y
-
-
-class _Stem3Conv(torch.autograd.Function):
-  """The MobileNet-v1 stem (3x3 / stride 2, 3 -> 16 | 32 channels, TensorFlow 'SAME' padding given by its FRONT pads) on
-  pf_conv_stem3_fwd / pf_conv_stem3_wrw: no padded copy of the image (round 4 ran this layer on the general kernel over
-  F.pad(image): 361 + 878 us per step against 148 / 119 us for MIOpen).  The image needs no gradient."""
-
-  @staticmethod
-  def forward(ctx, x, w, graph, w_var, pads, out_hw):
-    ctx.save_for_backward(x, w)
-    ctx.meta = (graph, w_var, pads, out_hw)
-    return _run_stem3(x, w, pads, out_hw)
-
-  @staticmethod
-  def backward(ctx, dy):
-    x, w = ctx.saved_tensors
-    graph, w_var, pads, (Ho, Wo) = ctx.meta
-    dy = _nhwc(dy)
-    dw = None
-    if ctx.needs_input_grad[1]:
-      B, _, H, Wd = x.shape
-      N = w.shape[0]
-      S = hip.conv_stem3_wrw_slabs(B, H, Wd, N, pads[0], pads[1], Ho, Wo)
-      if S <= 0:
-        raise RuntimeError('pf_conv_stem3_wrw does not take the shape its forward kernel took')
-
-      def wrw(dwk, scratch):
-        hip.conv_stem3_wrw(dy, x, dwk, scratch((S + 32) * N * 27), B, H, Wd, N, pads[0], pads[1], Ho, Wo)
-      dw = _filter_grad(graph, w, w_var, (dy, x), 'conv_stem_wrw', float((x.numel() + dy.numel()) * 2), wrw)
-    if ctx.needs_input_grad[0]:
-      raise RuntimeError('the MobileNet stem kernels compute no image gradient')
-    return None, dw, None, None, None, None
+      if geom.k != 7:
+        raise RuntimeError('the MobileNet stem kernels compute no image gradient')
+      dx = _library_conv_backward(dy, x, w, 2, geom.pads, 0)
+    return dx, dw, None, None, None
 
 
 def igemm_limits_ok(n_in_elems: int, n_kernel_elems: int, taps: int) -> bool:
@@ -1889,8 +1878,9 @@ def dw_lazy_on(C: int, stride: int, quantised: bool, dtype) -> bool:
 # `name`: the route; the layer launches it in `_call_<name>`.  `x`: the prepared input -- materialised where the route reads a tensor,
 # padded where its kernel pads both ends alike, never converted, so that it still carries the producer's tags.  `pad`: (pad_h, pad_w);
 # for the routes that take 'SAME' padding by its FRONT pads, those.  `out_bn`: the BatchNormAct the launch applies in its epilogue
-# (folded; on the int8 routes the requantising one).  `geom`: the int8 geometry.  What a route does not need is None.  The record
-# lives for the call and references inputs, never an output.
+# (folded; on the int8 routes the requantising one).  `geom`: the int8 geometry; on the stem route the StemGeom, whose front pads and
+# output size also stand in `pad` / `out_hw`.  What a route does not need is None.  The record lives for the call and references
+# inputs, never an output.
 ROUTE_NAME, ROUTE_X = 0, 1
 
 # the Conv2D routes that count themselves on the producer's BnSums (the table stands at BnSums.add_consumer)
@@ -1950,9 +1940,9 @@ class Conv2D:
                    fake-quantised tensor of the apply pass, as without int8 -- and goes on down the list.
       conv1x1      1x1 on pf_conv.hip, the producer BN's normalise / act / fake-quant in the prologue: the only route that reads a
                    LazyAct, so it is asked before the input is materialised for all the others.
-      stem3        the MobileNet stem, asked BEFORE _symmetric_pads: its kernel takes the asymmetric 'SAME' pads by their front pads
-                   and must not see (or pay for) a padded copy of the image.  Asks about the image's gradient: it computes none.
-      stem         the ResNet stem, asked AFTER it: its kernel pads both ends alike.
+      stem         either stem kernel (_stem_geom), asked BEFORE _symmetric_pads: the 3x3 kernel takes the asymmetric 'SAME' pads by
+                   their front pads and must not see (or pay for) a padded copy of the image; the 7x7 kernel pads both ends by 3,
+                   which is what its layer hands over, so no copy is ever in question for it.
       igemm        RxS on the implicit-GEMM kernel (cin % 64 == 0).
       im2col       few-channel RxS as im2col + the 1x1 kernels (im2col_conv_ok).
       general      everything else our kernels take (convg_ok): pf_convg.hip.
@@ -1984,15 +1974,10 @@ class Conv2D:
     ph, pw, out_hw = self._geometry(x.shape)
     # what the stem and implicit-GEMM kernels ask alike: no bias, a 4-D bf16 device tensor, fusion on (a padded copy keeps all three)
     mfma = self.bias is None and isinstance(x, torch.Tensor) and fusable_tensor(x) and x.dim() == 4 and g.fuse_conv1x1
-    if (mfma and OWN_STEM and self.padding == 'SAME' and residual is None and x.shape[1] == 3 and self.k == 3 and self.stride == 2
-        and not x.requires_grad and x.is_contiguous(memory_format=torch.channels_last)
-        and hip.conv_stem3_supported(x.shape[2], x.shape[3], 3, cout, 3, 2, ph[0], pw[0], out_hw[0], out_hw[1])
-        and hip.conv_stem3_wrw_slabs(x.shape[0], x.shape[2], x.shape[3], cout, ph[0], pw[0], out_hw[0], out_hw[1]) > 0):
-      return 'stem3', x, (ph[0], pw[0]), out_hw, None, None
+    stem = self._stem_geom(x, ph, pw, out_hw) if mfma and OWN_STEM and residual is None else None
+    if stem is not None:
+      return 'stem', x, stem.pads, stem.out_hw, None, stem
     x, pad = _symmetric_pads(x, ph, pw)
-    if (mfma and OWN_STEM and residual is None and pad[0] == pad[1] and x.is_contiguous(memory_format=torch.channels_last)
-        and hip.conv_stem_supported(x.shape[2], x.shape[3], x.shape[1], cout, self.k, self.stride, pad[0])):
-      return 'stem', x, pad, out_hw, None, None
     if (mfma and OWN_CONV2D and self.k > 1 and cin % 64 == 0 and cout % 8 == 0
         and igemm_limits_ok(x.numel(), kh * kw * cin * cout, kh * kw)):
       return 'igemm', x, pad, out_hw, out_bn, None
@@ -2017,16 +2002,26 @@ class Conv2D:
     w2d = w.detach().permute(0, 2, 3, 1).reshape(w.shape[0], w.shape[1])
     return _run_conv1x1(xin, w2d, lazy, _nhwc(residual) if residual is not None else None, want_stats, self.stride, out_bn=out_bn)
 
-  def _call_stem3(self, r, residual, want_stats):
-    _, x, front_pads, out_hw, _, _ = r
-    w = self.kernel.tensor
-    if _wants_grad(w):                           # (the route was refused to an image that asks for a gradient)
-      return _Stem3Conv.apply(x, w, self.graph, self.kernel, front_pads, out_hw)
-    return _run_stem3(x, w, front_pads, out_hw)
+  def _stem_geom(self, x, ph, pw, out_hw):
+    """The StemGeom where one of the stem kernels takes this layer on the image `x` as it stands (no padded copy), else None.  7x7: the
+    explicit pad of 3 on every side.  3x3: TF 'SAME' by its front pads, a backward-filter kernel that takes the shape too, and an image
+    that asks for no gradient (the kernels compute none)."""
+    if self.k not in (3, 7) or not x.is_contiguous(memory_format=torch.channels_last):
+      return None
+    B, C, H, Wd = x.shape
+    cout = self.kernel.ref_shape[3]
+    if self.k == 7:
+      ok = ph[0] == ph[1] == pw[0] == pw[1] and hip.conv_stem_supported(H, Wd, C, cout, 7, self.stride, ph[0])
+    else:
+      ok = (self.padding == 'SAME' and C == 3 and self.stride == 2 and not x.requires_grad
+            and hip.conv_stem3_supported(H, Wd, 3, cout, 3, 2, ph[0], pw[0], out_hw[0], out_hw[1])
+            and hip.conv_stem3_wrw_slabs(B, H, Wd, cout, ph[0], pw[0], out_hw[0], out_hw[1]) > 0)
+    return StemGeom(self.k, (ph[0], pw[0]), out_hw) if ok else None
 
   def _call_stem(self, r, residual, want_stats):
-    x, w = r[ROUTE_X], self.kernel.tensor
-    return _StemConv.apply(x, w, self.graph, self.kernel) if _wants_grad(w, x) else _run_stem(x, w)
+    x, w, geom = r[ROUTE_X], self.kernel.tensor, r[5]
+    # (`x` of the 3x3 family never asks for a gradient: the route was refused to such an image)
+    return _StemConv.apply(x, w, self.graph, self.kernel, geom) if _wants_grad(w, x) else _run_stem(x, w, geom)
 
   def _call_igemm(self, r, residual, want_stats):
     _, x, pad, _, out_bn, _ = r
@@ -2241,7 +2236,7 @@ class _Depthwise(torch.autograd.Function):
       pro = None if lazy is None else _dw_prologue(lazy)
 
       def wrw(dwk, scratch):                       # dwk: [C][k][k][1] memory = [C][k][k]
-        slabs = scratch((G + 32) * C * k * k)
+        slabs = scratch(_wrw_floats(G, C * k * k))
         if lazy is None:
           hip.depthwise_wrw(dy, x, dwk, slabs, *dims)
         else:

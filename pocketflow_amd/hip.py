@@ -712,15 +712,23 @@ def depthwise_bwd_data(dY, W, dX, B: int, H: int, Wd: int, C: int, k: int, strid
          'pf_depthwise_bwd_data')
 
 
+def wrw_workspace_floats(slabs: int, n: int) -> int:
+  """Float32 elements of the workspace of a backward-filter launch that writes `slabs` slabs of `n` gradient elements each: the slabs
+  and, behind them, the 32 partial sums of the staged reduction (pf_wrw_reduce).  The contract of conv1x1_wrw, conv2d_wrw,
+  depthwise_wrw[_act], conv_stem_wrw and conv_stem3_wrw, with `slabs` from the entry's own *_splits / *_groups / *_slabs query.  (The
+  general kernel, convg_wrw, has another: splits * n.)"""
+  return (slabs + 32) * n
+
+
 def _dw_wrw_check(name: str, X, slabs, B: int, Ho: int, Wo: int, C: int, k: int) -> None:
   _dev(X)
-  if slabs.dtype != torch.float32 or slabs.numel() < (depthwise_groups(B, Ho, Wo, C) + 32) * C * k * k:
+  if slabs.dtype != torch.float32 or slabs.numel() < wrw_workspace_floats(depthwise_groups(B, Ho, Wo, C), C * k * k):
     raise TypeError('%s: float32 workspace of (groups + 32) * C * k * k elements' % name)
 
 
 def depthwise_wrw(dY, X, dW, slabs, B: int, H: int, Wd: int, C: int, k: int, stride: int, pad_h: int, pad_w: int, Ho: int,
                   Wo: int) -> None:
-  """dW: [C][k][k], float32 or bf16; slabs: (depthwise_groups(B, Ho, Wo, C) + 32) * C * k * k floats."""
+  """dW: [C][k][k], float32 or bf16; slabs: wrw_workspace_floats(depthwise_groups(B, Ho, Wo, C), C * k * k)."""
   _dw_wrw_check('depthwise_wrw', X, slabs, B, Ho, Wo, C, k)
   _check(_lib.pf_depthwise_wrw(_ptr(dY), _ptr(X), _ptr(dW), c_int(dtype_code(X)), c_int(dtype_code(dW)), _ptr(slabs), c_int(B),
                                c_int(H), c_int(Wd), c_int(C), c_int(k), c_int(stride), c_int(pad_h), c_int(pad_w), c_int(Ho),
@@ -1041,7 +1049,7 @@ def conv_stem_wrw_slabs(imgs: int, H: int, Wd: int) -> int:
 
 def conv_stem_wrw(dY, X, dW, workspace, imgs: int, H: int, Wd: int) -> None:
   """dY: [imgs][H/2][Wd/2][64] bf16, X: [imgs][H][Wd][3] bf16, dW: KRSC memory [64][7][7][3] float32 / bf16;
-  workspace: float32, (conv_stem_wrw_slabs(...) + 32) * 64 * 147 elements."""
+  workspace: float32, wrw_workspace_floats(conv_stem_wrw_slabs(...), 64 * 147)."""
   _dev(dY)
   _check(_lib.pf_conv_stem_wrw(_ptr(dY), _ptr(X), _ptr(dW), c_int(dtype_code(dW)), _ptr(workspace), c_int(imgs), c_int(H),
                                c_int(Wd), _stream()), 'pf_conv_stem_wrw')
@@ -1065,7 +1073,7 @@ def conv_stem3_wrw_slabs(imgs: int, H: int, Wd: int, N: int, pad_h: int, pad_w: 
 
 
 def conv_stem3_wrw(dY, X, dW, workspace, imgs: int, H: int, Wd: int, N: int, pad_h: int, pad_w: int, Ho: int, Wo: int) -> None:
-  """dW: KRSC memory [N][3][3][3] float32 / bf16; workspace: float32, (conv_stem3_wrw_slabs(...) + 32) * N * 27 elements."""
+  """dW: KRSC memory [N][3][3][3] float32 / bf16; workspace: float32, wrw_workspace_floats(conv_stem3_wrw_slabs(...), N * 27)."""
   _dev(dY)
   _check(_lib.pf_conv_stem3_wrw(_ptr(dY), _ptr(X), _ptr(dW), c_int(dtype_code(dW)), _ptr(workspace), c_int(imgs), c_int(H), c_int(Wd),
                                 c_int(N), c_int(pad_h), c_int(pad_w), c_int(Ho), c_int(Wo), _stream()), 'pf_conv_stem3_wrw')

@@ -17,9 +17,14 @@ from test_proj_join_cpu import _Counting, _JoinHip
 class _Spy(object):
   """Tells the backward-data launches of the 1x1 route apart: `conv1x1_res` = a plain launch with a residual operand (the second of
   two joined consumers), `conv1x1_ymap` (test_proj_join_cpu._Counting) = the row scatter of a strided layer, whose target must
-  arrive zero-filled; and keeps the tensor the MobileNet stem kernel was handed."""
+  arrive zero-filled; keeps the tensor each stem kernel was handed, and the size of the workspace each backward-filter entry got."""
+  stem_input = None
   stem3_input = None
   ymap_into_zeros = None
+
+  def __init__(self):
+    super(_Spy, self).__init__()
+    self.workspaces = {}
 
   def conv1x1_fwd(self, X, W, Y, M, N, K, R=None, scale_shift=None, **kw):
     if scale_shift is None and R is not None:
@@ -28,9 +33,32 @@ class _Spy(object):
       self.ymap_into_zeros = not bool(Y.any())
     return super(_Spy, self).conv1x1_fwd(X, W, Y, M, N, K, R=R, scale_shift=scale_shift, **kw)
 
+  def conv_stem_fwd(self, X, *args):
+    self.stem_input = X
+    return super(_Spy, self).conv_stem_fwd(X, *args)
+
   def conv_stem3_fwd(self, X, *args):
     self.stem3_input = X
     return super(_Spy, self).conv_stem3_fwd(X, *args)
+
+  def _wrw(self, name, dY, X, dW, workspace, *args, **kw):
+    self.workspaces[name] = workspace.numel()
+    return getattr(super(_Spy, self), name)(dY, X, dW, workspace, *args, **kw)
+
+  def conv1x1_wrw(self, *args, **kw):
+    return self._wrw('conv1x1_wrw', *args, **kw)
+
+  def conv2d_wrw(self, *args, **kw):
+    return self._wrw('conv2d_wrw', *args, **kw)
+
+  def depthwise_wrw(self, *args, **kw):
+    return self._wrw('depthwise_wrw', *args, **kw)
+
+  def conv_stem_wrw(self, *args, **kw):
+    return self._wrw('conv_stem_wrw', *args, **kw)
+
+  def conv_stem3_wrw(self, *args, **kw):
+    return self._wrw('conv_stem3_wrw', *args, **kw)
 
 
 class _Hip(_Spy, _Counting):
@@ -242,10 +270,93 @@ def test_resnet_stem(monkeypatch):
   G, g, fake = _graph(monkeypatch)
   conv = G.Conv2D(g, 'conv', 3, 64, 7, stride=2, padding=3)
   _ready(g, fake)
-  y = conv(_image(3, 4, 32, grad=False))
+  x = _image(3, 4, 32, grad=False)
+  y = conv(x)
+  assert fake.stem_input is x                  # no padded copy: the kernel pads by 3 itself
   assert tuple(y.shape) == (2, 64, 2, 16) and type(y.grad_fn).__name__ == '_StemConvBackward'
   y.sum().backward()
   assert fake.calls == dict(conv_stem_fwd=1, conv_stem_wrw=1)
+
+
+def _library_grads(x, w, stride, padding, dy):
+  """(dx, dw) of the library convolution on the same operands."""
+  xr, wr = x.detach().clone().requires_grad_(), w.detach().clone().requires_grad_()
+  F.conv2d(xr, wr, stride=stride, padding=padding).backward(dy)
+  return xr.grad, wr.grad
+
+
+def test_resnet_stem_with_the_filter_switch_off_takes_the_librarys_filter_gradient(monkeypatch):
+  """PF_OWN_CONV2D_WRW=0 is honoured by the 7x7 family: the forward kernel, no backward-filter kernel, the library's dW."""
+  G, g, fake = _graph(monkeypatch, OWN_CONV2D_WRW=False)
+  conv = G.Conv2D(g, 'conv', 3, 64, 7, stride=2, padding=3)
+  _ready(g, fake)
+  x, w = _image(3, 4, 32, grad=False), conv.kernel.tensor
+  w.grad = None
+  y = conv(x)
+  torch.manual_seed(5)
+  dy = torch.randn_like(y)
+  y.backward(dy)
+  assert fake.calls == dict(conv_stem_fwd=1)
+  assert torch.equal(w.grad, _library_grads(x, w, 2, 3, dy)[1])
+
+
+def test_mobilenet_stem_ignores_the_filter_switch(monkeypatch):
+  """... and not by the 3x3 family, whose node has no library side: pinned as it is."""
+  G, g, fake = _graph(monkeypatch, OWN_CONV2D_WRW=False)
+  conv = G.Conv2D(g, 'conv', 3, 16, 3, stride=2)
+  _ready(g, fake)
+  conv(_image(3, 4, 32, grad=False)).sum().backward()
+  assert fake.calls == dict(conv_stem3_fwd=1, conv_stem3_wrw=1)
+
+
+def test_resnet_stem_with_an_image_that_asks_for_its_gradient(monkeypatch):
+  """The 7x7 route is not refused to such an image: the stem kernels for y and dW, the library's backward-data for dx."""
+  G, g, fake = _graph(monkeypatch)
+  conv = G.Conv2D(g, 'conv', 3, 64, 7, stride=2, padding=3)
+  _ready(g, fake)
+  x = _image(3, 4, 32)
+  y = conv(x)
+  assert fake.stem_input is x and type(y.grad_fn).__name__ == '_StemConvBackward'
+  torch.manual_seed(5)
+  dy = torch.randn_like(y)
+  y.backward(dy)
+  assert fake.calls == dict(conv_stem_fwd=1, conv_stem_wrw=1)
+  assert torch.equal(x.grad, _library_grads(x, conv.kernel.tensor, 2, 3, dy)[0])
+
+
+# (slabs: every *_splits / *_groups / *_slabs query of fake_hip answers 2)
+@pytest.mark.parametrize('layer,image,entry,n', [
+    (lambda G, g: G.Conv2D(g, 'conv', 3, 64, 7, stride=2, padding=3), (3, 4, 32), 'conv_stem_wrw', 64 * 147),
+    (lambda G, g: G.Conv2D(g, 'conv', 3, 16, 3, stride=2), (3, 4, 32), 'conv_stem3_wrw', 16 * 27),
+    (lambda G, g: G.Conv2D(g, 'conv', 3, 32, 3, stride=2), (3, 4, 32), 'conv_stem3_wrw', 32 * 27),
+    (lambda G, g: G.Conv2D(g, 'conv', 8, 16, 1), (8, 8, 8), 'conv1x1_wrw', 16 * 8),                     # N * K
+    (lambda G, g: G.Conv2D(g, 'conv', 8, 16, 3, stride=2), (8, 7, 7), 'conv1x1_wrw', 16 * 3 * 3 * 8),    # im2col: N * K, K = R * S * C
+    (lambda G, g: G.Conv2D(g, 'conv', 64, 64, 3), (64, 8, 8), 'conv2d_wrw', 64 * 3 * 3 * 64),            # N * R * S * C
+    (lambda G, g: G.DepthwiseConv2D(g, 'dw', 8, 3, 2), (8, 8, 8), 'depthwise_wrw', 8 * 3 * 3),           # C * k * k
+])
+def test_backward_filter_workspace_is_slabs_plus_32_times_the_gradient(monkeypatch, layer, image, entry, n):
+  """Every backward-filter site whose slabs pf_wrw_reduce folds asks for hip.wrw_workspace_floats(slabs, n): (slabs + 32) * n floats,
+  `n` the elements of the layer's gradient."""
+  G, g, fake = _graph(monkeypatch)
+  conv = layer(G, g)
+  _ready(g, fake)
+  g.scratch = lambda n_floats: torch.empty(n_floats)     # (the graph's own hands out one pooled buffer: its size says nothing)
+  conv(_image(*image, grad=False)).sum().backward()
+  assert fake.workspaces == {entry: (2 + 32) * n}
+
+
+def test_workspace_helper_and_the_check_that_uses_it(monkeypatch):
+  from pocketflow_amd import hip
+  assert hip.wrw_workspace_floats(2, 64 * 147) == 34 * 64 * 147 and hip.wrw_workspace_floats(0, 5) == 160
+  monkeypatch.setattr(hip, '_dev', lambda t: None)
+  monkeypatch.setattr(hip, 'depthwise_groups', lambda B, Ho, Wo, C: 2)
+  x, need = torch.zeros(2, 8, 8, 8), (2 + 32) * 8 * 3 * 3
+  hip._dw_wrw_check('depthwise_wrw', x, torch.empty(need), 2, 8, 8, 8, 3)
+  for name in ('depthwise_wrw', 'depthwise_wrw_act'):
+    with pytest.raises(TypeError, match=name + ': float32 workspace'):
+      hip._dw_wrw_check(name, x, torch.empty(need - 1), 2, 8, 8, 8, 3)
+  with pytest.raises(TypeError, match='float32 workspace'):                 # through the entry itself: refused before any launch
+    hip.depthwise_wrw(x, x, torch.empty(8, 3, 3), torch.empty(need - 1), 2, 8, 8, 8, 3, 1, 1, 1, 8, 8)
 
 
 def test_resnet_stem_as_the_network_calls_it(monkeypatch):
@@ -277,7 +388,7 @@ def test_mobilenet_stem_reads_the_image_itself(monkeypatch):
   assert conv._geometry(x.shape)[:2] == ((0, 1), (0, 1))
   y = conv(x)
   assert fake.stem3_input is x
-  assert tuple(y.shape) == (2, 16, 2, 16) and type(y.grad_fn).__name__ == '_Stem3ConvBackward'
+  assert tuple(y.shape) == (2, 16, 2, 16) and type(y.grad_fn).__name__ == '_StemConvBackward'
   y.sum().backward()
   assert fake.calls == dict(conv_stem3_fwd=1, conv_stem3_wrw=1)
   # an image that asks for its gradient is not the stem's: the padded copy and the library

@@ -326,6 +326,59 @@ def test_conv_stem3_wrw_matches_autograd(hip, imgs, H, Wd, N, dw_dtype):
   assert torch.equal(outs[0], outs[1])
 
 
+# ---- both stems through the layer (graph.Conv2D -> _StemConv) ----------------------------------------------------------------------
+# The smallest shapes the two `supported` predicates take (Wd % 32 == 0, Wo % 16 == 0): 7x7 needs an even H; 3x3 'SAME' has front pads
+# (0, 0) on even sizes and front pad 1 on an odd H.  One or two (image, strip) items per image: the persistent loops are host-independent
+# and covered by the tests above.
+@pytest.mark.parametrize('k,N,H,Wd', [(7, 64, 4, 32), (3, 16, 4, 32), (3, 32, 4, 32), (3, 16, 5, 32)])
+def test_stem_layer_reaches_the_launches_of_the_direct_calls(hip, k, N, H, Wd):
+  """graph.Conv2D forward + backward on a finalised bf16 graph against hip.conv_stem*_fwd / _wrw on the same tensors: the same kernel,
+  grid and reduction order, so the output and the filter gradient are the same BITS -- any difference is a host bug (a wrong pad,
+  size, layout or workspace handed down by the one route / node)."""
+  from pocketflow_amd import graph as G
+  imgs = 2
+  (ph, _, Ho), (pw, _, Wo) = (3, 3, H // 2), (3, 3, Wd // 2)
+  if k == 3:
+    (ph, _, Ho), (pw, _, Wo) = _same(H), _same(Wd)
+    assert (ph, pw) == (H % 2, 0)
+    assert hip.conv_stem3_supported(H, Wd, 3, N, 3, 2, ph, pw, Ho, Wo) and hip.conv_stem3_wrw_slabs(imgs, H, Wd, N, ph, pw, Ho, Wo) > 0
+  else:
+    assert hip.conv_stem_supported(H, Wd, 3, N, 7, 2, 3) and hip.conv_stem_wrw_slabs(imgs, H, Wd) > 0
+  g = G.Graph('model', 'cuda', torch.bfloat16)
+  with g.as_default():
+    conv = G.Conv2D(g, 'conv', 3, N, k, stride=2, padding=3 if k == 7 else 'SAME')
+  g.finalize(seed=11)
+  gen = torch.Generator(device='cuda').manual_seed(H + Wd + N + k)
+  x = _bf(torch.randn(imgs, H, Wd, 3, device='cuda', generator=gen))
+  dy = _bf(torch.randn(imgs, Ho, Wo, N, device='cuda', generator=gen) * 0.1)
+  w = conv.kernel.tensor
+  assert w.dtype == torch.bfloat16 and w.requires_grad
+  with torch.no_grad():                                    # an asymmetric random kernel, whatever the initialiser left
+    w.copy_(torch.randn(N, 3, k, k, device='cuda', generator=gen) * 0.1)
+  with g.as_default():
+    y = conv(x.permute(0, 3, 1, 2))
+  assert type(y.grad_fn).__name__ == '_StemConvBackward' and tuple(y.shape) == (imgs, N, Ho, Wo)
+  y.backward(dy.permute(0, 3, 1, 2))
+  torch.cuda.synchronize()
+  got_dw = w.grad.permute(0, 2, 3, 1)
+  # the direct calls
+  wk = w.detach().permute(0, 2, 3, 1)
+  assert wk.is_contiguous()
+  y2 = torch.full((imgs, Ho, Wo, N), float('nan'), device='cuda', dtype=torch.bfloat16)
+  dw2 = torch.full((N, k, k, 3), float('nan'), device='cuda', dtype=got_dw.dtype)
+  if k == 7:
+    ws = torch.full((hip.wrw_workspace_floats(hip.conv_stem_wrw_slabs(imgs, H, Wd), N * 147),), float('nan'), device='cuda')
+    hip.conv_stem_fwd(x, wk, y2, imgs, H, Wd)
+    hip.conv_stem_wrw(dy, x, dw2, ws, imgs, H, Wd)
+  else:
+    dims = (imgs, H, Wd, N, ph, pw, Ho, Wo)
+    ws = torch.full((hip.wrw_workspace_floats(hip.conv_stem3_wrw_slabs(*dims), N * 27),), float('nan'), device='cuda')
+    hip.conv_stem3_fwd(x, wk, y2, *dims)
+    hip.conv_stem3_wrw(dy, x, dw2, ws, *dims)
+  assert torch.equal(y.detach().permute(0, 2, 3, 1), y2)
+  assert torch.isfinite(dw2.float()).all() and torch.equal(got_dw, dw2)
+
+
 @pytest.mark.parametrize('tile', ['', '256x128'])
 @pytest.mark.parametrize('imgs,H,C,N,stride', [(24, 28, 128, 128, 1), (16, 56, 64, 64, 1), (12, 28, 128, 128, 2), (37, 7, 512, 512, 1),
                                                (5, 9, 64, 72, 1)])
