@@ -442,6 +442,21 @@ int pf_conv_stem3_wrw_slabs(int imgs, int H, int Wd, int N, int pad_h, int pad_w
 int pf_conv_stem3_wrw(const void* dY, const void* X, void* dW, int dw_dtype, float* workspace, int imgs, int H, int Wd, int N,
                       int pad_h, int pad_w, int Ho, int Wo, void* stream);
 
+/* ---- narrow 3x3 convolutions (pf_conv3x3_narrow.hip): 3x3 / stride 1 / pad 1, C and N in {16, 32}, the body of ResNet-20/32/56 @
+ * CIFAR-10 (utils/external/resnet_model.py:92-103 with 16 / 32 filters) ----------------------------------------------------------
+ * X [imgs][H][Wd][C] bf16 (NHWC), W [N][3][3][C] bf16 (KRSC), Y / R / dY [imgs][H][Wd][N] bf16.  Wd % 16 == 0, 16 <= Wd <= 64, any
+ * H >= 1 (pf_conv3x3n_supported: pure host); imgs >= 1 and imgs * H * Wd * max(C, N) * 2 < 2^31; every pointer 16-byte aligned.  The
+ * launchers return hipErrorInvalidValue for anything else; they neither allocate nor synchronise.
+ * pf_conv3x3n_fwd: Y = conv(X, W) (+ R in float32 before the one rounding; R may be NULL).  Backward-data is the same entry with
+ * (C, N) swapped on the flipped / transposed kernel W'[c][2 - r][2 - s][n].
+ * pf_conv3x3n_wrw: dW [N][3][3][C] in dw_dtype (PF_F32 / PF_BF16), deterministic (one slab per workgroup, fixed-order fold);
+ * workspace (pf_conv3x3n_wrw_slabs(...) + 32) * N * 9 * C floats (0 slabs: shape not taken).  Activations must be finite.        */
+int pf_conv3x3n_supported(int H, int Wd, int C, int N, int stride, int pad_h, int pad_w);
+int pf_conv3x3n_fwd(const void* X, const void* W, void* Y, const void* R, int imgs, int H, int Wd, int C, int N, void* stream);
+int pf_conv3x3n_wrw_slabs(int imgs, int H, int Wd, int C, int N);
+int pf_conv3x3n_wrw(const void* dY, const void* X, void* dW, int dw_dtype, float* workspace, int imgs, int H, int Wd, int C, int N,
+                    void* stream);
+
 /* ---- K12 (MobileNet): depthwise 3x3 convolutions, NHWC float32 / bf16, kernel [C][3][3] in the activation dtype ----------
  * replaces DepthwiseConv2dNative / ...BackpropInput / ...BackpropFilter behind slim.separable_conv2d(num_outputs=None)
  * (utils/external/mobilenet_v1.py:264-292).  stride 1 | 2; pad_h / pad_w are TensorFlow's FRONT pads of 'SAME'

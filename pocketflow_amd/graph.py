@@ -646,7 +646,7 @@ class BnSums(object):
       Conv2D   fused 1x1 reading a LazyAct            1        DepthwiseConv2D   own kernel           2
                fused 1x1 reading a materialised tensor 2       LazyAct.materialize                    2
                implicit GEMM                          1
-               im2col, general kernel, library        2
+               im2col, narrow 3x3, general, library   2
     These count NOTHING, and that is kept as it was found: the tap (the plain call behind it counts as the route IT takes), gather,
     int8 / codes and the two stem routes of Conv2D, and the tap, codes and library routes of DepthwiseConv2D.  (The gather and codes
     routes run in inference only, where no record exists; the stems read images.)"""
@@ -1382,6 +1382,8 @@ OWN_CONV2D = os.environ.get('PF_OWN_CONV2D', '1') != '0'     # RxS convolutions 
 OWN_STEM = os.environ.get('PF_OWN_STEM', '1') != '0'         # the 7x7/2 stem on pf_stem.hip (0: MIOpen, for A/B runs)
 OWN_DEPTHWISE = os.environ.get('PF_OWN_DEPTHWISE', '1') != '0'   # depthwise 3x3 on pf_depthwise.hip (0: MIOpen, for A/B runs)
 OWN_CONV_IM2COL = os.environ.get('PF_OWN_CONV_IM2COL', '1') != '0'   # few-channel RxS convolutions as im2col + own 1x1 kernels (0: MIOpen)
+# 3x3 / stride 1 / pad 1 with 16 | 32 channels on pf_conv3x3_narrow.hip, one launch per pass (0: im2col, for A/B runs)
+OWN_CONV3X3_NARROW = os.environ.get('PF_OWN_CONV3X3_NARROW', '1') != '0'
 CONVG_BF16_NARROW = os.environ.get('PF_CONVG_BF16_NARROW', '0') != '0'
 # inference-mode BN + activation applied in the epilogue of the producing convolution (teacher / evaluation of unquantised networks)
 FOLD_EVAL_BN = os.environ.get('PF_FOLD_EVAL_BN', '1') != '0'
@@ -1565,8 +1567,9 @@ def _convg_slab(graph, dtype, M: int, Nc: int, K: int):
 def convg_ok(x: torch.Tensor, w: torch.Tensor, dense: bool = False) -> bool:
   """float32: every convolution and dense layer.  bf16: the dense layer and convolutions over images (C % 8 != 0); a bf16
   convolution with 16 / 32 / 48 ... input channels (ResNet-20 @ CIFAR-10) is MFMA-shaped work that the vector-ALU kernel runs 2x
-  slower per step than MIOpen (measured, configuration C1: 33 665 vs 66 174 images/s) -- it stays with the library until the
-  implicit-GEMM kernel takes 16-channel k-steps (PF_CONVG_BF16_NARROW=1 forces ours)."""
+  slower per step than MIOpen (measured, configuration C1: 33 665 vs 66 174 images/s) -- it is not offered to this kernel
+  (PF_CONVG_BF16_NARROW=1 forces it): Conv2D._route gives the 3x3 / stride 1 layers with 16 | 32 channels to pf_conv3x3_narrow.hip
+  and the other bias-free ones with C % 8 == 0 to im2col + the 1x1 kernels before this is asked; what is left goes to the library."""
   if not (OWN_CONV_GENERIC and isinstance(x, torch.Tensor) and x.is_cuda and x.dtype in (torch.float32, torch.bfloat16)
           and w.dtype in (torch.float32, torch.bfloat16) and x.numel() > 0):
     return False
@@ -1633,6 +1636,50 @@ def im2col_conv_ok(x, conv, pad) -> bool:
   return (OWN_CONV_IM2COL and conv.k > 1 and conv.bias is None and isinstance(x, torch.Tensor) and fusable_tensor(x) and x.dim() == 4
           and cin % 8 == 0 and cin % 64 != 0 and cout % 8 == 0 and conv.graph.fuse_conv1x1
           and x.shape[0] * x.shape[2] * x.shape[3] * kh * kw * cin < (1 << 31))
+
+
+def _run_conv3x3n(x, w_krsc, residual):
+  """x: logical NCHW / physical NHWC bf16; w_krsc: KRSC memory [N][3][3][C]; residual: NHWC memory of the output's shape, or None --
+  added inside the launch, in float32, before the one rounding."""
+  B, C, H, Wd = x.shape
+  N = w_krsc.shape[0]
+  y = torch.empty((B, N, H, Wd), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+  with region('conv3x3n_fwd', float((x.numel() + y.numel() * (1 if residual is None else 2)) * 2)):
+    hip.conv3x3n_fwd(x, w_krsc, y, B, H, Wd, C, N, residual=residual)
+  return y
+
+
+class _Conv3x3Narrow(torch.autograd.Function):
+  """y = conv2d(x, W) (+ residual) for 3x3 / stride 1 / pad 1 with 16 | 32 input and output channels (ResNet-20/32/56 @ CIFAR-10) on
+  pf_conv3x3_narrow.hip: one launch per pass.  Backward-data is the forward kernel with (C, N) swapped on the flipped / transposed
+  kernel; the filter gradient is written straight into the flat gradient buffer; the residual's gradient is dy itself."""
+
+  @staticmethod
+  def forward(ctx, x, w, residual, graph, w_var):
+    ctx.save_for_backward(x, w)
+    ctx.meta = (graph, w_var)
+    return _run_conv3x3n(x, _krsc(w, x.dtype), None if residual is None else _nhwc(residual).to(x.dtype))
+
+  @staticmethod
+  def backward(ctx, dy):
+    x, w = ctx.saved_tensors
+    graph, w_var = ctx.meta
+    B, C, H, Wd = x.shape
+    N = w.shape[0]
+    dy = _nhwc(dy)
+    dx = dw = None
+    if ctx.needs_input_grad[1]:
+      S = hip.conv3x3n_wrw_slabs(B, H, Wd, C, N)
+
+      def wrw(dwk, scratch):                     # dwk: [N][3][3][C] memory
+        hip.conv3x3n_wrw(dy, x, dwk, scratch(_wrw_floats(S, w.numel())), B, H, Wd, C, N)
+      dw = _filter_grad(graph, w, w_var, (dy, x), 'conv3x3n_wrw', float((x.numel() + dy.numel()) * 2), wrw)
+    if ctx.needs_input_grad[0]:
+      wb = _bwd_data_weight(graph, w_var, w)                                              # [C][3][3][N], flipped
+      dx = torch.empty_like(x)
+      with region('conv3x3n_bwd_data', float((dy.numel() + dx.numel()) * 2)):
+        hip.conv3x3n_fwd(dy, wb, dx, B, H, Wd, N, C)
+    return dx, dw, (dy if ctx.needs_input_grad[2] else None), None, None
 
 
 # One stem route (Conv2D._route builds it once per call): `k` names the kernel family -- 7: the ResNet stem, 7x7 / stride 2 / pad 3,
@@ -1884,7 +1931,7 @@ def dw_lazy_on(C: int, stride: int, quantised: bool, dtype) -> bool:
 ROUTE_NAME, ROUTE_X = 0, 1
 
 # the Conv2D routes that count themselves on the producer's BnSums (the table stands at BnSums.add_consumer)
-_CONV2D_COUNTED = frozenset(['conv1x1', 'igemm', 'im2col', 'general', 'library'])
+_CONV2D_COUNTED = frozenset(['conv1x1', 'igemm', 'conv3x3n', 'im2col', 'general', 'library'])
 
 
 @contextlib.contextmanager
@@ -1943,8 +1990,11 @@ class Conv2D:
       stem         either stem kernel (_stem_geom), asked BEFORE _symmetric_pads: the 3x3 kernel takes the asymmetric 'SAME' pads by
                    their front pads and must not see (or pay for) a padded copy of the image; the 7x7 kernel pads both ends by 3,
                    which is what its layer hands over, so no copy is ever in question for it.
+      conv3x3n     3x3 / stride 1 / pad 1 with 16 | 32 input and output channels on pf_conv3x3_narrow.hip (PF_OWN_CONV3X3_NARROW=0:
+                   im2col); it asks `x.is_cuda` itself, whatever stands in for fusable_tensor.
       igemm        RxS on the implicit-GEMM kernel (cin % 64 == 0).
-      im2col       few-channel RxS as im2col + the 1x1 kernels (im2col_conv_ok).
+      im2col       few-channel RxS as im2col + the 1x1 kernels (im2col_conv_ok): among them what conv3x3n leaves -- the strided
+                   few-channel layers (16 -> 32 and 32 -> 64 at stride 2: 2 of ResNet-20's 13) and C = 8 / 24 / 48.
       general      everything else our kernels take (convg_ok): pf_convg.hip.
       library      the rest.
     `out_bn` is honoured by the conv1x1 and igemm routes where they run without gradients and by the gathered route; every other
@@ -1978,6 +2028,10 @@ class Conv2D:
     if stem is not None:
       return 'stem', x, stem.pads, stem.out_hw, None, stem
     x, pad = _symmetric_pads(x, ph, pw)
+    if (mfma and OWN_CONV3X3_NARROW and x.is_cuda and self.k == 3 and self.stride == 1 and ph == (1, 1) and pw == (1, 1)
+        and hip.conv3x3n_supported(x.shape[2], x.shape[3], cin, cout, 1, 1, 1)
+        and hip.conv3x3n_wrw_slabs(x.shape[0], x.shape[2], x.shape[3], cin, cout) > 0):     # (the slabs query: the byte limit)
+      return 'conv3x3n', x, pad, out_hw, None, None
     if (mfma and OWN_CONV2D and self.k > 1 and cin % 64 == 0 and cout % 8 == 0
         and igemm_limits_ok(x.numel(), kh * kw * cin * cout, kh * kw)):
       return 'igemm', x, pad, out_hw, out_bn, None
@@ -2031,6 +2085,12 @@ class Conv2D:
     else:
       y = _run_conv2d(xin, w.detach().permute(0, 2, 3, 1), self.stride, pad, want_stats, out_bn=out_bn)
     return y if residual is None else y + residual
+
+  def _call_conv3x3n(self, r, residual, want_stats):
+    x, w = _nhwc(r[ROUTE_X]), self.kernel.tensor
+    if _wants_grad(w, x) or (residual is not None and torch.is_grad_enabled() and residual.requires_grad):
+      return _Conv3x3Narrow.apply(x, w, residual, self.graph, self.kernel)
+    return _run_conv3x3n(x, _krsc(w, x.dtype), None if residual is None else _nhwc(residual).to(x.dtype))
 
   def _call_im2col(self, r, residual, want_stats):
     _, x, pad, out_hw, _, _ = r

@@ -63,6 +63,7 @@ SYMBOLS = [
     'pf_bn_vector_ok',
     'pf_conv1x1_bwd_apply_plan', 'pf_conv1x1_bwd_data_bnsums', 'pf_conv1x1_bwd_data_bnapply',
     'pf_depthwise_fwd_act', 'pf_depthwise_wrw_act',
+    'pf_conv3x3n_supported', 'pf_conv3x3n_fwd', 'pf_conv3x3n_wrw_slabs', 'pf_conv3x3n_wrw',
 ]
 
 
@@ -715,7 +716,7 @@ def depthwise_bwd_data(dY, W, dX, B: int, H: int, Wd: int, C: int, k: int, strid
 def wrw_workspace_floats(slabs: int, n: int) -> int:
   """Float32 elements of the workspace of a backward-filter launch that writes `slabs` slabs of `n` gradient elements each: the slabs
   and, behind them, the 32 partial sums of the staged reduction (pf_wrw_reduce).  The contract of conv1x1_wrw, conv2d_wrw,
-  depthwise_wrw[_act], conv_stem_wrw and conv_stem3_wrw, with `slabs` from the entry's own *_splits / *_groups / *_slabs query.  (The
+  depthwise_wrw[_act], conv_stem_wrw, conv_stem3_wrw and conv3x3n_wrw, with `slabs` from the entry's own *_splits / *_groups / *_slabs query.  (The
   general kernel, convg_wrw, has another: splits * n.)"""
   return (slabs + 32) * n
 
@@ -1077,6 +1078,30 @@ def conv_stem3_wrw(dY, X, dW, workspace, imgs: int, H: int, Wd: int, N: int, pad
   _dev(dY)
   _check(_lib.pf_conv_stem3_wrw(_ptr(dY), _ptr(X), _ptr(dW), c_int(dtype_code(dW)), _ptr(workspace), c_int(imgs), c_int(H), c_int(Wd),
                                 c_int(N), c_int(pad_h), c_int(pad_w), c_int(Ho), c_int(Wo), _stream()), 'pf_conv_stem3_wrw')
+
+
+def conv3x3n_supported(H: int, Wd: int, C: int, N: int, stride: int, pad_h: int, pad_w: int) -> bool:
+  return bool(_lib.pf_conv3x3n_supported(c_int(H), c_int(Wd), c_int(C), c_int(N), c_int(stride), c_int(pad_h), c_int(pad_w)))
+
+
+def conv3x3n_fwd(X, W, Y, imgs: int, H: int, Wd: int, C: int, N: int, residual=None) -> None:
+  """The narrow 3x3 convolutions (stride 1, pad 1; C, N in {16, 32}).  X: NHWC memory [imgs][H][Wd][C] bf16, W: KRSC memory
+  [N][3][3][C] bf16, Y and `residual` (added in float32 before the one rounding): [imgs][H][Wd][N] bf16.  Backward-data: the same
+  call with (C, N) swapped on the flipped / transposed kernel."""
+  _dev(X)
+  _check(_lib.pf_conv3x3n_fwd(_ptr(X), _ptr(W), _ptr(Y), _ptr(residual), c_int(imgs), c_int(H), c_int(Wd), c_int(C), c_int(N),
+                              _stream()), 'pf_conv3x3n_fwd')
+
+
+def conv3x3n_wrw_slabs(imgs: int, H: int, Wd: int, C: int, N: int) -> int:
+  return int(_lib.pf_conv3x3n_wrw_slabs(c_int(imgs), c_int(H), c_int(Wd), c_int(C), c_int(N)))
+
+
+def conv3x3n_wrw(dY, X, dW, workspace, imgs: int, H: int, Wd: int, C: int, N: int) -> None:
+  """dW: KRSC memory [N][3][3][C] float32 / bf16; workspace: float32, wrw_workspace_floats(conv3x3n_wrw_slabs(...), N * 9 * C)."""
+  _dev(dY)
+  _check(_lib.pf_conv3x3n_wrw(_ptr(dY), _ptr(X), _ptr(dW), c_int(dtype_code(dW)), _ptr(workspace), c_int(imgs), c_int(H), c_int(Wd),
+                              c_int(C), c_int(N), _stream()), 'pf_conv3x3n_wrw')
 
 
 # ------------------------------------------------------------------------------------------------
