@@ -457,6 +457,25 @@ int pf_conv3x3n_wrw_slabs(int imgs, int H, int Wd, int C, int N);
 int pf_conv3x3n_wrw(const void* dY, const void* X, void* dW, int dw_dtype, float* workspace, int imgs, int H, int Wd, int C, int N,
                     void* stream);
 
+/* ---- dense layers on the matrix cores (pf_dense.hip): tf.layers.dense and MobileNet's logits, any N (1001, 10, ...) ------------------
+ * X / dX [B][K] bf16, W / dW [N][K] (the store's [out][in]; dW in dw_dtype, PF_F32 / PF_BF16), Y / dY [B][N] bf16, bias / db [N]
+ * float32.  K % 32 == 0, K >= 32, any N >= 1, any B >= 1, B * K * 2, N * K * 4 and B * N * 2 below 2^31 (pf_dense_supported: pure
+ * host).  X, W, dX, dW and the workspace 16-byte aligned; Y / dY need their natural 2 bytes only (their row pitch is N * 2).  The
+ * launchers return hipErrorInvalidValue for anything else; they neither allocate nor synchronise.
+ * pf_dense_splits: the float32 slabs the forward (bwd_data = 0) / backward-data (1) launch sums its contraction in, a function of the
+ * shape alone (0: shape not taken); forward: divides K / 32, backward-data: <= ceil(N / 32).
+ * pf_dense_fwd: Y = X W^T (+ bias; may be NULL), one rounding.  workspace: splits * B * N floats, folded in ascending order by a second
+ * launch; splits == 1: not read, may be NULL.
+ * pf_dense_bwd_data: dX = dY W.  workspace: splits * B * K floats, as above.
+ * pf_dense_wrw: dW = dY^T X, summed in ascending b in one launch, and db[n] = sum over b of dY[b][n] (ascending; db may be NULL).
+ * Deterministic: no atomics.  Rows b >= B and columns n >= N of a tile are zeros in both operands, never memory.                   */
+int pf_dense_supported(int B, int K, int N);
+int pf_dense_splits(int B, int K, int N, int bwd_data);
+int pf_dense_fwd(const void* X, const void* W, const float* bias, void* Y, int B, int K, int N, float* workspace, int64_t ws_elems,
+                 void* stream);
+int pf_dense_bwd_data(const void* dY, const void* W, void* dX, int B, int K, int N, float* workspace, int64_t ws_elems, void* stream);
+int pf_dense_wrw(const void* dY, const void* X, void* dW, int dw_dtype, float* db, int B, int K, int N, void* stream);
+
 /* ---- K12 (MobileNet): depthwise 3x3 convolutions, NHWC float32 / bf16, kernel [C][3][3] in the activation dtype ----------
  * replaces DepthwiseConv2dNative / ...BackpropInput / ...BackpropFilter behind slim.separable_conv2d(num_outputs=None)
  * (utils/external/mobilenet_v1.py:264-292).  stride 1 | 2; pad_h / pad_w are TensorFlow's FRONT pads of 'SAME'

@@ -32,6 +32,7 @@ import contextlib
 import math
 import os
 import threading
+import types
 from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
@@ -1387,6 +1388,7 @@ OWN_CONV3X3_NARROW = os.environ.get('PF_OWN_CONV3X3_NARROW', '1') != '0'
 CONVG_BF16_NARROW = os.environ.get('PF_CONVG_BF16_NARROW', '0') != '0'
 # inference-mode BN + activation applied in the epilogue of the producing convolution (teacher / evaluation of unquantised networks)
 FOLD_EVAL_BN = os.environ.get('PF_FOLD_EVAL_BN', '1') != '0'
+OWN_DENSE_MFMA = os.environ.get('PF_OWN_DENSE_MFMA', '1') != '0'   # bf16 dense layers on pf_dense.hip (0: pf_convg.hip, for A/B runs)
 OWN_CONV_GENERIC = os.environ.get('PF_OWN_CONV_GENERIC', '1') != '0'   # every other convolution / dense layer on pf_convg.hip (0: MIOpen / rocBLAS)
 DEPTHWISE_ANY_DEVICE = False     # tests: run the depthwise plumbing on CPU tensors (the HIP entry points are emulated there)
 # a depthwise layer applies its producer's BN + activation (+ fake-quant) in its own prologue instead of reading a materialised tensor
@@ -1580,6 +1582,88 @@ def convg_ok(x: torch.Tensor, w: torch.Tensor, dense: bool = False) -> bool:
 def conv_generic(x, w, bias, stride, pad_begin, out_hw, graph):
   """Dispatch helper: 4-D x (logical NCHW) through _ConvGeneric; works with or without autograd."""
   return _ConvGeneric.apply(_nhwc(x), w, bias, stride, pad_begin, out_hw, graph)
+
+
+def dense_mfma_ok(x2d, w) -> bool:
+  """The bf16 dense layer on the matrix cores (pf_dense.hip): x2d [B][K] on the device, `w` the compute copy of the kernel, [N][K]
+  (or its [N][K][1][1] convolution form), K % 32 == 0, any N.  The float32 parity mode keeps pf_convg.hip (one ascending sum per
+  output, see _ConvGeneric.forward); a CPU tensor is never taken, whatever HEAD_FUSE_ANY_DEVICE says."""
+  return (OWN_DENSE_MFMA and isinstance(x2d, torch.Tensor) and x2d.is_cuda and x2d.dim() == 2 and x2d.dtype == torch.bfloat16
+          and w.dtype == torch.bfloat16 and hip.dense_supported(x2d.shape[0], x2d.shape[1], w.shape[0]))
+
+
+def _dense_kernel_2d(w):
+  """[N][K] memory of a dense kernel: itself, or the [N][1][1][K] storage of its [N][K][1][1] convolution form."""
+  w = w.detach()
+  return w if w.dim() == 2 else w.permute(0, 2, 3, 1).reshape(w.shape[0], w.shape[1])
+
+
+def _run_dense(x2d, w, bias, graph):
+  """y [B][N] = x2d W^T (+ bias); the split workspace is what hip.dense_splits asks for this shape, no more."""
+  B, K = x2d.shape
+  N = w.shape[0]
+  y = torch.empty((B, N), dtype=x2d.dtype, device=x2d.device)
+  S = hip.dense_splits(B, K, N)
+  bf = None if bias is None else bias.detach().float().contiguous()
+  with region('dense_fwd', float((x2d.numel() + w.numel() + y.numel()) * 2)):
+    hip.dense_fwd(x2d, _dense_kernel_2d(w), bf, y, B, K, N, graph.scratch(S * B * N) if S > 1 else None)
+  return y
+
+
+def dense_mfma(x2d, w, bias, graph, w_var=None):
+  """Dispatch helper: the autograd node where a gradient is wanted, the bare launch where not."""
+  x2d = x2d.contiguous()
+  if _wants_grad(w, x2d) or (bias is not None and torch.is_grad_enabled() and bias.requires_grad):
+    return _DenseMfma.apply(x2d, w, bias, graph, w_var)
+  return _run_dense(x2d, w, bias, graph)
+
+
+class _DenseMfma(torch.autograd.Function):
+  """y = x W^T (+ bias) for a bf16 dense layer on pf_dense.hip: tf.layers.dense and MobileNet's logits (a 1x1 convolution over 1x1
+  pixels, `w` then [N][K][1][1]).  Backward: dX = dY W; dW = dY^T X goes straight into the flat gradient buffer (on the side queue
+  where one is armed), and the same launch leaves db, the column sums of dY, in float32."""
+
+  @staticmethod
+  def forward(ctx, x, w, bias, graph, w_var):
+    ctx.save_for_backward(x, w)
+    ctx.meta = (graph, w_var, bias is not None)
+    return _run_dense(x, w, bias, graph)
+
+  @staticmethod
+  def backward(ctx, dy):
+    x, w = ctx.saved_tensors
+    graph, w_var, has_bias = ctx.meta
+    B, K = x.shape
+    N = w.shape[0]
+    dy = dy.contiguous()
+    if dy.dtype != x.dtype:
+      dy = dy.to(x.dtype)
+    dx = dw = db = None
+    want_db = has_bias and ctx.needs_input_grad[2]
+    if ctx.needs_input_grad[1]:
+      db = torch.empty(N, dtype=torch.float32, device=x.device) if want_db else None
+
+      def wrw(dwk, scratch):                     # dwk: [N][1][1][K] memory = [N][K]
+        hip.dense_wrw(dy, x, dwk, db, B, K, N)
+      # _filter_grad speaks of [N][C][R][S] kernels: a 2-D kernel is shown to it as its [N][K][1][1] view, whose storage order is [N][1][1][K]
+      w4 = w if w.dim() == 4 else types.SimpleNamespace(
+          grad=None if w.grad is None else w.grad.view(N, K, 1, 1), shape=torch.Size((N, K, 1, 1)), dtype=w.dtype, device=w.device)
+      dw = _filter_grad(graph, w4, w_var, (dy, x, db), 'dense_wrw', float((x.numel() + dy.numel() + w.numel()) * 2), wrw)
+      if dw is not None:
+        dw = dw.reshape(w.shape)
+    elif want_db:
+      db = dy.float().sum(dim=0)
+    if ctx.needs_input_grad[0]:
+      S = hip.dense_splits(B, K, N, True)
+      dx = torch.empty_like(x)
+      with region('dense_bwd_data', float((dy.numel() + w.numel() + dx.numel()) * 2)):
+        hip.dense_bwd_data(dy, _dense_kernel_2d(w), dx, B, K, N, graph.scratch(S * B * K) if S > 1 else None)
+    if db is not None:
+      # db goes to autograd, which reads it on this queue: wait for the side queue where the filter launch ran there
+      side = getattr(getattr(graph, 'store', None), 'wrw_side', None)
+      if side is not None and side.forks:
+        torch.cuda.current_stream(side.device).wait_stream(side.stream)
+    return dx, dw, db, None, None
 
 
 class _ConvIm2col(torch.autograd.Function):
@@ -2099,7 +2183,15 @@ class Conv2D:
 
   def _call_general(self, r, residual, want_stats):
     _, x, pad, out_hw, _, _ = r
-    y = conv_generic(x, self.kernel.tensor, self.bias.tensor if self.bias is not None else None, self.stride, pad, out_hw, self.graph)
+    w = self.kernel.tensor
+    bias = self.bias.tensor if self.bias is not None else None
+    if self.k == 1 and x.shape[2] * x.shape[3] == 1 and tuple(out_hw) == (1, 1) and not any(pad):
+      # a 1x1 kernel over 1x1 pixels IS a dense layer (MobileNet's logits): the [B][C] view on the matrix cores
+      x2d = x.reshape(x.shape[0], x.shape[1])
+      if dense_mfma_ok(x2d, w):
+        y = dense_mfma(x2d, w, bias, self.graph, self.kernel).view(x.shape[0], w.shape[0], 1, 1)
+        return y if residual is None else y + residual
+    y = conv_generic(x, w, bias, self.stride, pad, out_hw, self.graph)
     return y if residual is None else y + residual
 
   def _call_library(self, r, residual, want_stats):
@@ -2454,6 +2546,8 @@ class Dense:
     """x W^T [+ bias]: tf.layers.dense = the 1x1 convolution of a [B][1][1][in] tensor (+ BiasAdd in the epilogue) on pf_convg.hip,
     the library for what that kernel does not take."""
     w = self.kernel.tensor
+    if self.graph.taps is None and dense_mfma_ok(x, w):                      # bf16: the matrix cores (pf_dense.hip)
+      return dense_mfma(x, w, bias, self.graph, self.kernel)
     if x.dim() == 2 and convg_ok(x, w, dense=True):
       y = _ConvGeneric.apply(x.contiguous().view(x.shape[0], x.shape[1], 1, 1), w.view(w.shape[0], w.shape[1], 1, 1), bias, 1,
                              (0, 0), (1, 1), self.graph)

@@ -64,6 +64,7 @@ SYMBOLS = [
     'pf_conv1x1_bwd_apply_plan', 'pf_conv1x1_bwd_data_bnsums', 'pf_conv1x1_bwd_data_bnapply',
     'pf_depthwise_fwd_act', 'pf_depthwise_wrw_act',
     'pf_conv3x3n_supported', 'pf_conv3x3n_fwd', 'pf_conv3x3n_wrw_slabs', 'pf_conv3x3n_wrw',
+    'pf_dense_supported', 'pf_dense_splits', 'pf_dense_fwd', 'pf_dense_bwd_data', 'pf_dense_wrw',
 ]
 
 
@@ -1102,6 +1103,43 @@ def conv3x3n_wrw(dY, X, dW, workspace, imgs: int, H: int, Wd: int, C: int, N: in
   _dev(dY)
   _check(_lib.pf_conv3x3n_wrw(_ptr(dY), _ptr(X), _ptr(dW), c_int(dtype_code(dW)), _ptr(workspace), c_int(imgs), c_int(H), c_int(Wd),
                               c_int(C), c_int(N), _stream()), 'pf_conv3x3n_wrw')
+
+
+# dense layers on the matrix cores (pf_dense.hip): X / dX [B][K], W / dW [N][K], Y / dY [B][N] bf16 (dW: float32 or bf16), bias / db
+# [N] float32; K % 32 == 0, any N and B
+
+def dense_supported(B: int, K: int, N: int) -> bool:
+  return bool(_lib.pf_dense_supported(c_int(B), c_int(K), c_int(N)))
+
+
+def dense_splits(B: int, K: int, N: int, bwd_data: bool = False) -> int:
+  """Float32 slabs of the forward / backward-data launch (a function of the shape alone); 0: shape not taken."""
+  return int(_lib.pf_dense_splits(c_int(B), c_int(K), c_int(N), c_int(1 if bwd_data else 0)))
+
+
+def _dense_ws(workspace):
+  return _ptr(workspace), c_int64(workspace.numel() if workspace is not None else 0)
+
+
+def dense_fwd(X, W, bias, Y, B: int, K: int, N: int, workspace=None) -> None:
+  """Y = X W^T (+ bias, float32 or None); workspace: float32, dense_splits(B, K, N) * B * N elements (one split: not read)."""
+  _dev(X)
+  _check(_lib.pf_dense_fwd(_ptr(X), _ptr(W), _ptr(bias), _ptr(Y), c_int(B), c_int(K), c_int(N), *_dense_ws(workspace), _stream()),
+         'pf_dense_fwd')
+
+
+def dense_bwd_data(dY, W, dX, B: int, K: int, N: int, workspace=None) -> None:
+  """dX = dY W; workspace: float32, dense_splits(B, K, N, True) * B * K elements (one split: not read)."""
+  _dev(dY)
+  _check(_lib.pf_dense_bwd_data(_ptr(dY), _ptr(W), _ptr(dX), c_int(B), c_int(K), c_int(N), *_dense_ws(workspace), _stream()),
+         'pf_dense_bwd_data')
+
+
+def dense_wrw(dY, X, dW, db, B: int, K: int, N: int) -> None:
+  """dW = dY^T X (float32 or bf16) and, where `db` is not None, db[n] = sum over b of dY[b][n] (float32)."""
+  _dev(dY)
+  _check(_lib.pf_dense_wrw(_ptr(dY), _ptr(X), _ptr(dW), c_int(dtype_code(dW)), _ptr(db), c_int(B), c_int(K), c_int(N), _stream()),
+         'pf_dense_wrw')
 
 
 # ------------------------------------------------------------------------------------------------
