@@ -442,6 +442,20 @@ int pf_conv_stem3_wrw_slabs(int imgs, int H, int Wd, int N, int pad_h, int pad_w
 int pf_conv_stem3_wrw(const void* dY, const void* X, void* dW, int dw_dtype, float* workspace, int imgs, int H, int Wd, int N,
                       int pad_h, int pad_w, int Ho, int Wo, void* stream);
 
+/* ---- three-channel 3x3 stems at stride 1 | 2 and any N % 8 == 0, 8 <= N <= 64 (pf_stem3x.hip): the CIFAR ResNet stem (3 -> 16, stride
+ * 1, pad 1; utils/external/resnet_model.py of resnet_at_cifar10) and the MobileNet stems of width 8 / 24 / 48 (depth multipliers 0.25 /
+ * 0.75 / 1.4), which the entries above refuse.  Tensors, FRONT pads (0 | 1), finiteness of the pixels and the deterministic
+ * backward-filter as for pf_conv_stem3_*; the last window may reach one row / column behind the image (symmetric pad 1, 'SAME').
+ * Any H >= 1, Wd % 8 == 0 in 16 .. 256, X and Y / dY below 2^31 bytes (pf_conv_stem3x_supported sees the image only; the byte limits
+ * are in pf_conv_stem3x_wrw_slabs: 0 slabs = unsupported).  No byte behind channel N - 1 of a pixel is written and no kernel row
+ * behind W[N - 1] is read.  workspace: (pf_conv_stem3x_wrw_slabs(...) + 32) * N * 27 floats.                                        */
+int pf_conv_stem3x_supported(int H, int Wd, int C, int N, int k, int stride, int pad_h, int pad_w, int Ho, int Wo);
+int pf_conv_stem3x_fwd(const void* X, const void* W, void* Y, int imgs, int H, int Wd, int N, int stride, int pad_h, int pad_w, int Ho,
+                       int Wo, void* stream);
+int pf_conv_stem3x_wrw_slabs(int imgs, int H, int Wd, int N, int stride, int pad_h, int pad_w, int Ho, int Wo);
+int pf_conv_stem3x_wrw(const void* dY, const void* X, void* dW, int dw_dtype, float* workspace, int imgs, int H, int Wd, int N,
+                       int stride, int pad_h, int pad_w, int Ho, int Wo, void* stream);
+
 /* ---- narrow 3x3 convolutions (pf_conv3x3_narrow.hip): 3x3 / stride 1 / pad 1, C and N in {16, 32}, the body of ResNet-20/32/56 @
  * CIFAR-10 (utils/external/resnet_model.py:92-103 with 16 / 32 filters) ----------------------------------------------------------
  * X [imgs][H][Wd][C] bf16 (NHWC), W [N][3][3][C] bf16 (KRSC), Y / R / dY [imgs][H][Wd][N] bf16.  Wd % 16 == 0, 16 <= Wd <= 64, any

@@ -1381,6 +1381,8 @@ OWN_CONV2D_WRW_MIN_C = int(os.environ.get('PF_OWN_CONV2D_WRW_MIN_C', '64'))    #
 OWN_CONV2D_BWD_STRIDED = os.environ.get('PF_OWN_CONV2D_BWD_STRIDED', '1') != '0'   # strided backward-data by parity classes (0: MIOpen)
 OWN_CONV2D = os.environ.get('PF_OWN_CONV2D', '1') != '0'     # RxS convolutions on pf_igemm.hip (0: MIOpen, for A/B runs)
 OWN_STEM = os.environ.get('PF_OWN_STEM', '1') != '0'         # the 7x7/2 stem on pf_stem.hip (0: MIOpen, for A/B runs)
+# 3x3 stems at stride 1 | 2 to any N % 8 == 0 up to 64 on pf_stem3x.hip (0: pf_convg.hip as before, for A/B runs)
+OWN_STEM3X = os.environ.get('PF_OWN_STEM3X', '1') != '0'
 OWN_DEPTHWISE = os.environ.get('PF_OWN_DEPTHWISE', '1') != '0'   # depthwise 3x3 on pf_depthwise.hip (0: MIOpen, for A/B runs)
 OWN_CONV_IM2COL = os.environ.get('PF_OWN_CONV_IM2COL', '1') != '0'   # few-channel RxS convolutions as im2col + own 1x1 kernels (0: MIOpen)
 # 3x3 / stride 1 / pad 1 with 16 | 32 channels on pf_conv3x3_narrow.hip, one launch per pass (0: im2col, for A/B runs)
@@ -1767,9 +1769,11 @@ class _Conv3x3Narrow(torch.autograd.Function):
 
 
 # One stem route (Conv2D._route builds it once per call): `k` names the kernel family -- 7: the ResNet stem, 7x7 / stride 2 / pad 3,
-# 3 -> 64 channels on pf_stem.hip; 3: the MobileNet stem, 3x3 / stride 2 / 'SAME', 3 -> 16 | 32 on pf_stem3.hip --, `pads` are the FRONT
-# pads (pad_h, pad_w) and `out_hw` the output size.  Neither family reads a padded copy of the image.
-StemGeom = collections.namedtuple('StemGeom', 'k pads out_hw')
+# 3 -> 64 channels on pf_stem.hip; 3: the MobileNet stem, 3x3 / stride 2 / 'SAME', 3 -> 16 | 32 on pf_stem3.hip, and with `wide` set the
+# 3x3 stems those two refuse, stride 1 | 2 to any N % 8 == 0 up to 64 on pf_stem3x.hip (the CIFAR ResNet stem, MobileNet 0.25 / 0.75 /
+# 1.4) --, `pads` are the FRONT pads (pad_h, pad_w), `out_hw` the output size and `stride` the layer's.  No family reads a padded copy of
+# the image.
+StemGeom = collections.namedtuple('StemGeom', 'k pads out_hw stride wide')
 
 
 def _run_stem(x, w, geom):
@@ -1781,14 +1785,17 @@ def _run_stem(x, w, geom):
   with region('conv_stem_fwd', float((x.numel() + y.numel()) * 2)):
     if geom.k == 7:
       hip.conv_stem_fwd(x, w.detach().permute(0, 2, 3, 1), y, B, H, Wd)
+    elif geom.wide:
+      hip.conv_stem3x_fwd(x, w.detach().permute(0, 2, 3, 1), y, B, H, Wd, N, geom.stride, geom.pads[0], geom.pads[1], Ho, Wo)
     else:
       hip.conv_stem3_fwd(x, w.detach().permute(0, 2, 3, 1), y, B, H, Wd, N, geom.pads[0], geom.pads[1], Ho, Wo)
   return y
 
 
 class _StemConv(torch.autograd.Function):
-  """The first-layer convolution of an image on pf_conv_stem[3]_fwd / pf_conv_stem[3]_wrw.  The two kernel families were written
-  apart, and backward differs between them in three ways that are kept as they are (tests/test_conv_routes_cpu.py pins each):
+  """The first-layer convolution of an image on pf_conv_stem[3[x]]_fwd / pf_conv_stem[3[x]]_wrw.  The 7x7 and 3x3 kernel families were
+  written apart, and backward differs between them in three ways that are kept as they are (tests/test_conv_routes_cpu.py pins each;
+  the wide 3x3 family of pf_stem3x.hip behaves as the 3x3 row):
 
     family   PF_OWN_CONV2D_WRW=0            the backward-filter kernel refuses        the image asks for a gradient
     7x7      honoured: the library's dW     the library's dW                          the library's backward-data
@@ -1816,25 +1823,25 @@ class _StemConv(torch.autograd.Function):
       if geom.k == 7:
         S = hip.conv_stem_wrw_slabs(B, H, Wd) if OWN_CONV2D_WRW else 0
       else:
-        dims = (B, H, Wd, N, geom.pads[0], geom.pads[1]) + tuple(geom.out_hw)
-        S = hip.conv_stem3_wrw_slabs(*dims)
+        dims = (B, H, Wd, N) + ((geom.stride,) if geom.wide else ()) + (geom.pads[0], geom.pads[1]) + tuple(geom.out_hw)
+        S = (hip.conv_stem3x_wrw_slabs if geom.wide else hip.conv_stem3_wrw_slabs)(*dims)
         if S <= 0:
-          raise RuntimeError('pf_conv_stem3_wrw does not take the shape its forward kernel took')
+          raise RuntimeError('pf_conv_stem3%s_wrw does not take the shape its forward kernel took' % ('x' if geom.wide else ''))
       if S > 0:
         def wrw(dwk, scratch):
           ws = scratch(_wrw_floats(S, w.numel()))    # slabs of [N][k][k][3]
           if geom.k == 7:
             hip.conv_stem_wrw(dy, x, dwk, ws, B, H, Wd)
           else:
-            hip.conv_stem3_wrw(dy, x, dwk, ws, *dims)
+            (hip.conv_stem3x_wrw if geom.wide else hip.conv_stem3_wrw)(dy, x, dwk, ws, *dims)
         dw = _filter_grad(graph, w, w_var, (dy, x), 'conv_stem_wrw', nbytes, wrw)
       else:
         with region('conv_stem_wrw', nbytes):
-          dw = _library_conv_backward(dy, x, w, 2, geom.pads, 1)
+          dw = _library_conv_backward(dy, x, w, geom.stride, geom.pads, 1)
     if ctx.needs_input_grad[0]:
       if geom.k != 7:
-        raise RuntimeError('the MobileNet stem kernels compute no image gradient')
-      dx = _library_conv_backward(dy, x, w, 2, geom.pads, 0)
+        raise RuntimeError('the 3x3 stem kernels compute no image gradient')
+      dx = _library_conv_backward(dy, x, w, geom.stride, geom.pads, 0)
     return dx, dw, None, None, None
 
 
@@ -2071,7 +2078,7 @@ class Conv2D:
                    fake-quantised tensor of the apply pass, as without int8 -- and goes on down the list.
       conv1x1      1x1 on pf_conv.hip, the producer BN's normalise / act / fake-quant in the prologue: the only route that reads a
                    LazyAct, so it is asked before the input is materialised for all the others.
-      stem         either stem kernel (_stem_geom), asked BEFORE _symmetric_pads: the 3x3 kernel takes the asymmetric 'SAME' pads by
+      stem         any stem kernel (_stem_geom), asked BEFORE _symmetric_pads: the 3x3 kernels take the asymmetric 'SAME' pads by
                    their front pads and must not see (or pay for) a padded copy of the image; the 7x7 kernel pads both ends by 3,
                    which is what its layer hands over, so no copy is ever in question for it.
       conv3x3n     3x3 / stride 1 / pad 1 with 16 | 32 input and output channels on pf_conv3x3_narrow.hip (PF_OWN_CONV3X3_NARROW=0:
@@ -2143,7 +2150,8 @@ class Conv2D:
   def _stem_geom(self, x, ph, pw, out_hw):
     """The StemGeom where one of the stem kernels takes this layer on the image `x` as it stands (no padded copy), else None.  7x7: the
     explicit pad of 3 on every side.  3x3: TF 'SAME' by its front pads, a backward-filter kernel that takes the shape too, and an image
-    that asks for no gradient (the kernels compute none)."""
+    that asks for no gradient (the kernels compute none).  What both refuse is offered to pf_stem3x.hip (PF_OWN_STEM3X): 3x3 at either
+    stride under 'SAME' or the symmetric pad 1, on the device only."""
     if self.k not in (3, 7) or not x.is_contiguous(memory_format=torch.channels_last):
       return None
     B, C, H, Wd = x.shape
@@ -2154,7 +2162,10 @@ class Conv2D:
       ok = (self.padding == 'SAME' and C == 3 and self.stride == 2 and not x.requires_grad
             and hip.conv_stem3_supported(H, Wd, 3, cout, 3, 2, ph[0], pw[0], out_hw[0], out_hw[1])
             and hip.conv_stem3_wrw_slabs(B, H, Wd, cout, ph[0], pw[0], out_hw[0], out_hw[1]) > 0)
-    return StemGeom(self.k, (ph[0], pw[0]), out_hw) if ok else None
+    wide = (not ok and OWN_STEM3X and x.is_cuda and self.k == 3 and self.padding in ('SAME', 1) and C == 3 and not x.requires_grad
+            and hip.conv_stem3x_supported(H, Wd, 3, cout, 3, self.stride, ph[0], pw[0], out_hw[0], out_hw[1])
+            and hip.conv_stem3x_wrw_slabs(B, H, Wd, cout, self.stride, ph[0], pw[0], out_hw[0], out_hw[1]) > 0)
+    return StemGeom(self.k, (ph[0], pw[0]), out_hw, self.stride, wide) if ok or wide else None
 
   def _call_stem(self, r, residual, want_stats):
     x, w, geom = r[ROUTE_X], self.kernel.tensor, r[5]

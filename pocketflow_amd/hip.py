@@ -65,6 +65,7 @@ SYMBOLS = [
     'pf_depthwise_fwd_act', 'pf_depthwise_wrw_act',
     'pf_conv3x3n_supported', 'pf_conv3x3n_fwd', 'pf_conv3x3n_wrw_slabs', 'pf_conv3x3n_wrw',
     'pf_dense_supported', 'pf_dense_splits', 'pf_dense_fwd', 'pf_dense_bwd_data', 'pf_dense_wrw',
+    'pf_conv_stem3x_supported', 'pf_conv_stem3x_fwd', 'pf_conv_stem3x_wrw_slabs', 'pf_conv_stem3x_wrw',
 ]
 
 
@@ -1079,6 +1080,31 @@ def conv_stem3_wrw(dY, X, dW, workspace, imgs: int, H: int, Wd: int, N: int, pad
   _dev(dY)
   _check(_lib.pf_conv_stem3_wrw(_ptr(dY), _ptr(X), _ptr(dW), c_int(dtype_code(dW)), _ptr(workspace), c_int(imgs), c_int(H), c_int(Wd),
                                 c_int(N), c_int(pad_h), c_int(pad_w), c_int(Ho), c_int(Wo), _stream()), 'pf_conv_stem3_wrw')
+
+
+# three-channel 3x3 stems at stride 1 | 2 and any N % 8 == 0 up to 64 (pf_stem3x.hip): what the two families above refuse
+def conv_stem3x_supported(H: int, Wd: int, C: int, N: int, k: int, stride: int, pad_h: int, pad_w: int, Ho: int, Wo: int) -> bool:
+  return bool(_lib.pf_conv_stem3x_supported(c_int(H), c_int(Wd), c_int(C), c_int(N), c_int(k), c_int(stride), c_int(pad_h), c_int(pad_w),
+                                            c_int(Ho), c_int(Wo)))
+
+
+def conv_stem3x_fwd(X, W, Y, imgs: int, H: int, Wd: int, N: int, stride: int, pad_h: int, pad_w: int, Ho: int, Wo: int) -> None:
+  """X: NHWC memory [imgs][H][Wd][3] bf16, W: KRSC memory [N][3][3][3] bf16, Y: [imgs][Ho][Wo][N] bf16; pad_h / pad_w: FRONT pads."""
+  _dev(X)
+  _check(_lib.pf_conv_stem3x_fwd(_ptr(X), _ptr(W), _ptr(Y), c_int(imgs), c_int(H), c_int(Wd), c_int(N), c_int(stride), c_int(pad_h),
+                                 c_int(pad_w), c_int(Ho), c_int(Wo), _stream()), 'pf_conv_stem3x_fwd')
+
+
+def conv_stem3x_wrw_slabs(imgs: int, H: int, Wd: int, N: int, stride: int, pad_h: int, pad_w: int, Ho: int, Wo: int) -> int:
+  return int(_lib.pf_conv_stem3x_wrw_slabs(c_int(imgs), c_int(H), c_int(Wd), c_int(N), c_int(stride), c_int(pad_h), c_int(pad_w),
+                                           c_int(Ho), c_int(Wo)))
+
+
+def conv_stem3x_wrw(dY, X, dW, workspace, imgs: int, H: int, Wd: int, N: int, stride: int, pad_h: int, pad_w: int, Ho: int, Wo: int) -> None:
+  """dW: KRSC memory [N][3][3][3] float32 / bf16; workspace: float32, wrw_workspace_floats(conv_stem3x_wrw_slabs(...), N * 27)."""
+  _dev(dY)
+  _check(_lib.pf_conv_stem3x_wrw(_ptr(dY), _ptr(X), _ptr(dW), c_int(dtype_code(dW)), _ptr(workspace), c_int(imgs), c_int(H), c_int(Wd),
+                                 c_int(N), c_int(stride), c_int(pad_h), c_int(pad_w), c_int(Ho), c_int(Wo), _stream()), 'pf_conv_stem3x_wrw')
 
 
 def conv3x3n_supported(H: int, Wd: int, C: int, N: int, stride: int, pad_h: int, pad_w: int) -> bool:
