@@ -24,6 +24,15 @@ typedef uint16_t bf16_t;
 // device; launches that need more than 64 KiB of LDS fail without it).  Cached per (device, function) behind a mutex: a process that
 // drives a second GPU, or launches first from another thread, is configured too (the caches were process-wide statics).
 int pf_require_lds(const void* fn, size_t lds);
+// ... and the launch that needs it: `lds` bytes allowed, `kernel` launched with them, 0 or the first error (the attribute's, then the
+// launch's)
+template <typename K, typename... A>
+static inline int pf_launch_lds(K* kernel, dim3 grid, dim3 threads, size_t lds, hipStream_t st, const A&... args) {
+  if (int e = pf_require_lds(reinterpret_cast<const void*>(kernel), lds)) return e;
+  kernel<<<grid, threads, lds, st>>>(args...);
+  PF_LAUNCH_CHECK();
+  return 0;
+}
 
 // The fixed-order fold of the S slabs of `n` floats a backward-filter kernel left at the head of `workspace` into dW (pf_conv.hip):
 // the ONE declaration for every file whose kernels write slabs (1x1, RxS, depthwise, the stems).  The workspace holds (S + 32) * n

@@ -318,10 +318,7 @@ int pf_conv3x3_c64_stats_groups(int M) { return h3_grid(M); }
 template <int MODE, bool STATS, bool AFF>
 static int h3_launch_t(const IgArgs& a, hipStream_t st) {
   const size_t lds = 2 * (size_t)H3_WBYTES + (MODE == IG_BWD ? 4 * H3_C * 4 : 0);
-  if (int e = pf_require_lds(reinterpret_cast<const void*>(&k_conv3x3_c64<MODE, STATS, AFF>), lds)) return e;
-  k_conv3x3_c64<MODE, STATS, AFF><<<h3_grid(a.M), H3_THREADS, lds, st>>>(a);
-  PF_LAUNCH_CHECK();
-  return 0;
+  return pf_launch_lds(&k_conv3x3_c64<MODE, STATS, AFF>, h3_grid(a.M), H3_THREADS, lds, st, a);
 }
 
 int pf_conv3x3_c64_launch(const IgArgs& a, hipStream_t st) {

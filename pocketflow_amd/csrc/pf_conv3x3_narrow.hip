@@ -46,15 +46,12 @@
 // One float32 slab [N][9][C] per workgroup (min(tiles, 256) of them: a slab is 9 .. 36 KiB, more would cost more traffic than the
 // operands), folded by pf_wrw_reduce in a fixed order: deterministic, no atomics.  Rows of a tile past the image are zero rows of dY;
 // like the other backward-filter kernels this one assumes FINITE activations (0 * Inf).
-#include "pf_conv_common.h"
+#include "pf_mfma.h"
 #include "pf_buffer.h"
 
 #define CN_THREADS 256
 #define CN_FWD_GRID 1024
 #define CN_WRW_GRID 256
-
-typedef short cn_v4s __attribute__((ext_vector_type(4)));
-typedef short cn_v8s __attribute__((ext_vector_type(8)));
 
 struct Cn3Args {
   const bf16_t* X;      // [imgs][H][Wd][C]
@@ -68,13 +65,8 @@ struct Cn3Args {
   int wpix, nx, ny;     // window pixels; 1 KiB LDS-DMA instructions of the window and (backward-filter) of the dY tile
 };
 
-// LDS reads beside a pending LDS-DMA come from inline asm (pf_conv_common.h).  The reads carry no wait; cn_wait() is the wait, and a
-// register is valid behind CN_TIE(reg) placed after it (volatile asm statements keep their order, and the tie is a definition no use
-// can be scheduled in front of).
+// LDS reads beside a pending LDS-DMA come from inline asm and carry no wait: pf_lds_wait() and PF_TIE(reg) behind them (pf_mfma.h)
 __device__ __forceinline__ void cn_read(uint32_t p, u32x4_t& v) { asm volatile("ds_read_b128 %0, %1" : "=&v"(v) : "v"(p) : "memory"); }
-__device__ __forceinline__ void cn_read_tr(uint32_t p, cn_v4s& v) { asm volatile("ds_read_b64_tr_b16 %0, %1" : "=&v"(v) : "v"(p) : "memory"); }
-__device__ __forceinline__ void cn_wait() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-#define CN_TIE(x) asm volatile("" : "+v"(x) : : "memory")
 
 // one 1 KiB LDS-DMA instruction I of a [rows of `pitch` bytes] region: lane L fills bytes [I * 1024 + 16 L, + 16) = 16-byte group ck of
 // row `row`; the caller turns (row, ck) into a byte offset of the tensor or PF_BUFFER_OOB (zeros)
@@ -150,9 +142,9 @@ __global__ __launch_bounds__(CN_THREADS, 2) void k_conv3x3n(const Cn3Args a) {
       u32x4_t x[KS];
 #pragma unroll
       for (int j = 0; j < KS; ++j) cn_read(xb + toff[j], x[j]);
-      cn_wait();
+      pf_lds_wait();
 #pragma unroll
-      for (int j = 0; j < KS; ++j) CN_TIE(x[j]);
+      for (int j = 0; j < KS; ++j) PF_TIE(x[j]);
       if (C == 16 && q >= 2) x[KS - 1] = zero4;                              // (2)
 #pragma unroll
       for (int j = 0; j < KS; ++j) {
@@ -178,13 +170,6 @@ __global__ __launch_bounds__(CN_THREADS, 2) void k_conv3x3n(const Cn3Args a) {
 }
 
 // ---- backward-filter -----------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bf16x8 cn_join(const cn_v4s& lo, const cn_v4s& hi) {
-  cn_v8s x;
-  x[0] = lo[0]; x[1] = lo[1]; x[2] = lo[2]; x[3] = lo[3];
-  x[4] = hi[0]; x[5] = hi[1]; x[6] = hi[2]; x[7] = hi[3];
-  return *reinterpret_cast<const bf16x8*>(&x);
-}
-
 template <int C, int N>
 __global__ __launch_bounds__(CN_THREADS, 2) void k_wrw3x3n(const Cn3Args a) {
   constexpr int XP = (C == 16) ? 32 : 96, YP = (N == 16) ? 32 : 96;         // pixel pitches (header)
@@ -247,22 +232,22 @@ __global__ __launch_bounds__(CN_THREADS, 2) void k_wrw3x3n(const Cn3Args a) {
 #pragma unroll
     for (int kb = 0; kb < 4; ++kb) {
       if (kb < nkb) {
-        cn_v4s d[2], v[MAXT][2];
-        cn_read_tr(dyb + (uint32_t)(kb * 32 * YP), d[0]);
-        cn_read_tr(dyb + (uint32_t)((kb * 32 + 16) * YP), d[1]);
+        pf_v4s d[2], v[MAXT][2];
+        pf_tr_issue(dyb + (uint32_t)(kb * 32 * YP), d[0]);
+        pf_tr_issue(dyb + (uint32_t)((kb * 32 + 16) * YP), d[1]);
 #pragma unroll
         for (int e = 0; e < MAXT; ++e) {
-          cn_read_tr(xb[kb][0] + toff[e], v[e][0]);
-          cn_read_tr(xb[kb][1] + toff[e], v[e][1]);
+          pf_tr_issue(xb[kb][0] + toff[e], v[e][0]);
+          pf_tr_issue(xb[kb][1] + toff[e], v[e][1]);
         }
-        cn_wait();
-        CN_TIE(d[0]); CN_TIE(d[1]);
+        pf_lds_wait();
+        PF_TIE(d[0]); PF_TIE(d[1]);
 #pragma unroll
-        for (int e = 0; e < MAXT; ++e) { CN_TIE(v[e][0]); CN_TIE(v[e][1]); }
-        const bf16x8 df = cn_join(d[0], d[1]);
+        for (int e = 0; e < MAXT; ++e) { PF_TIE(v[e][0]); PF_TIE(v[e][1]); }
+        const bf16x8 df = pf_join(d[0], d[1]);
 #pragma unroll
         for (int e = 0; e < MAXT; ++e)
-          if (e < ntap) acc[e] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(df, cn_join(v[e][0], v[e][1]), acc[e], 0, 0, 0);
+          if (e < ntap) acc[e] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(df, pf_join(v[e][0], v[e][1]), acc[e], 0, 0, 0);
       }
     }
     __builtin_amdgcn_s_barrier();                                            // every wavefront is done with the tile

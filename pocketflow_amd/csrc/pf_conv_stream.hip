@@ -486,10 +486,7 @@ static int stream_launch_t(const typename StreamArgs<BV>::type& a, int nsplit, h
   const int JM = (NW == 256) ? 1 : 2, RS = 16 * JM;
   const size_t aux_fl = PRO ? 2 * (size_t)a.K : (BWD ? (BV == BV_APPLY ? 6 : 4) * (size_t)NW : 0);
   const size_t lds = (size_t)NW * a.K * 2 + aux_fl * 4 + (size_t)ST_WAVES * RS * (NW + 8) * 2;
-  if (int e = pf_require_lds(reinterpret_cast<const void*>(&k_conv1x1_stream<NW, PRO, BWD, MAP, AFF, RMAP, BR, BV, ACT>), lds)) return e;
-  k_conv1x1_stream<NW, PRO, BWD, MAP, AFF, RMAP, BR, BV, ACT><<<ST_GRID, ST_THREADS, lds, st>>>(a, nsplit);
-  PF_LAUNCH_CHECK();
-  return 0;
+  return pf_launch_lds(&k_conv1x1_stream<NW, PRO, BWD, MAP, AFF, RMAP, BR, BV, ACT>, ST_GRID, ST_THREADS, lds, st, a, nsplit);
 }
 
 // The pair without dq: is the plan `p` of a backward-data launch with BN-backward sums (q.bwd) one whose kernel variants are compiled?

@@ -32,14 +32,11 @@
 // X [32 b][64 k] are staged (pitch 160, as above) and both read transposed; the chunks are summed in ascending b inside the kernel, no
 // split, no slab: ceil(N / 64) * ceil(K / 64) tiles (512 for the ResNet-50 head).  Wavefront w owns the 16 n of fragment w and all 64
 // k.  The workgroups of the first K tile also sum their 64 dY columns from the staged chunk, ascending b, into db (float32).
-#include "pf_conv_common.h"
+#include "pf_mfma.h"
 
 #define DN_THREADS 256
 #define DN_WP 160             // pitch of a [32 rows][64 columns] bf16 chunk read transposed
 #define DN_YP 80              // pitch of the [256 rows][32 columns] dY chunk of backward-data
-
-typedef short dn_v4s __attribute__((ext_vector_type(4)));
-typedef short dn_v8s __attribute__((ext_vector_type(8)));
 
 struct DenseArgs {
   const bf16_t* A;      // forward: X [B][K]; backward: dY [B][N]
@@ -50,17 +47,6 @@ struct DenseArgs {
   int B, K, N;
   int per;              // 32-wide steps of the contraction per slice
 };
-
-__device__ __forceinline__ void dn_read_tr(uint32_t p, dn_v4s& v) { asm volatile("ds_read_b64_tr_b16 %0, %1" : "=&v"(v) : "v"(p) : "memory"); }
-__device__ __forceinline__ void dn_wait() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-#define DN_TIE(x) asm volatile("" : "+v"(x) : : "memory")
-
-__device__ __forceinline__ bf16x8 dn_join(const dn_v4s& lo, const dn_v4s& hi) {
-  dn_v8s x;
-  x[0] = lo[0]; x[1] = lo[1]; x[2] = lo[2]; x[3] = lo[3];
-  x[4] = hi[0]; x[5] = hi[1]; x[6] = hi[2]; x[7] = hi[3];
-  return *reinterpret_cast<const bf16x8*>(&x);
-}
 
 // two neighbouring bf16 of a row whose pitch is odd: one 4-byte load where the address allows, 2-byte loads where not; an element
 // at or behind `n_end` is zero and is not loaded
@@ -236,15 +222,15 @@ __global__ __launch_bounds__(DN_THREADS) void k_dense_bwd_data(const DenseArgs a
     for (int i = 0; i < 16; ++i) *reinterpret_cast<uint32_t*>(ys + (yr + 16 * i) * DN_YP + yp * 4) = yreg[i];
     __syncthreads();
     if (step + 1 < step1) load(step + 1);
-    dn_v4s wl[4], wh[4];
+    pf_v4s wl[4], wh[4];
 #pragma unroll
     for (int kf = 0; kf < 4; ++kf) {
-      dn_read_tr(wb + (uint32_t)(kf * 32), wl[kf]);
-      dn_read_tr(wb + (uint32_t)(16 * DN_WP + kf * 32), wh[kf]);
+      pf_tr_issue(wb + (uint32_t)(kf * 32), wl[kf]);
+      pf_tr_issue(wb + (uint32_t)(16 * DN_WP + kf * 32), wh[kf]);
     }
-    dn_wait();
+    pf_lds_wait();
 #pragma unroll
-    for (int kf = 0; kf < 4; ++kf) { DN_TIE(wl[kf]); DN_TIE(wh[kf]); }
+    for (int kf = 0; kf < 4; ++kf) { PF_TIE(wl[kf]); PF_TIE(wh[kf]); }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int fr = (wave + 4 * i) * 16;
@@ -255,7 +241,7 @@ __global__ __launch_bounds__(DN_THREADS) void k_dense_bwd_data(const DenseArgs a
         const bf16x8 yf = *reinterpret_cast<const bf16x8*>(&yv);
 #pragma unroll
         for (int kf = 0; kf < 4; ++kf)
-          if (kf < nkf) acc[i][kf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dn_join(wl[kf], wh[kf]), yf, acc[i][kf], 0, 0, 0);
+          if (kf < nkf) acc[i][kf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf_join(wl[kf], wh[kf]), yf, acc[i][kf], 0, 0, 0);
       }
     }
   }
@@ -328,22 +314,22 @@ __global__ __launch_bounds__(DN_THREADS) void k_dense_wrw(const DenseArgs a) {
     __syncthreads();
     if (c + 1 < chunks) load(c + 1);
     if (w_ok) {
-      dn_v4s dl, dh, xl[4], xh[4];
-      dn_read_tr(yb, dl);
-      dn_read_tr(yb + (uint32_t)(16 * DN_WP), dh);
+      pf_v4s dl, dh, xl[4], xh[4];
+      pf_tr_issue(yb, dl);
+      pf_tr_issue(yb + (uint32_t)(16 * DN_WP), dh);
 #pragma unroll
       for (int kf = 0; kf < 4; ++kf) {
-        dn_read_tr(xb + (uint32_t)(kf * 32), xl[kf]);
-        dn_read_tr(xb + (uint32_t)(16 * DN_WP + kf * 32), xh[kf]);
+        pf_tr_issue(xb + (uint32_t)(kf * 32), xl[kf]);
+        pf_tr_issue(xb + (uint32_t)(16 * DN_WP + kf * 32), xh[kf]);
       }
-      dn_wait();
-      DN_TIE(dl); DN_TIE(dh);
+      pf_lds_wait();
+      PF_TIE(dl); PF_TIE(dh);
 #pragma unroll
-      for (int kf = 0; kf < 4; ++kf) { DN_TIE(xl[kf]); DN_TIE(xh[kf]); }
-      const bf16x8 df = dn_join(dl, dh);
+      for (int kf = 0; kf < 4; ++kf) { PF_TIE(xl[kf]); PF_TIE(xh[kf]); }
+      const bf16x8 df = pf_join(dl, dh);
 #pragma unroll
       for (int kf = 0; kf < 4; ++kf)
-        if (kf < nkf) acc[kf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dn_join(xl[kf], xh[kf]), df, acc[kf], 0, 0, 0);
+        if (kf < nkf) acc[kf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf_join(xl[kf], xh[kf]), df, acc[kf], 0, 0, 0);
     }
     if (sums) {
 #pragma unroll 8

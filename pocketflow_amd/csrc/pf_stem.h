@@ -2,11 +2,8 @@
 // pf_stem3.hip (MobileNet: 3x3 / stride 2 / 'SAME' by its front pads, 3 -> 16 | 32).  The MFMA bodies differ and stay in their files;
 // here is what both families do alike: the argument blocks, the staging of one input row, and the host code of every launcher.
 #pragma once
-#include "pf_conv_common.h"
+#include "pf_mfma.h"
 #include "pf_buffer.h"
-
-typedef short st_v4s __attribute__((ext_vector_type(4)));
-typedef short st_v8s __attribute__((ext_vector_type(8)));
 
 #define ST_THREADS 256
 

@@ -116,10 +116,7 @@ extern "C" int pf_conv_stem_fwd(const void* X, const void* W, void* Y, int imgs,
   a.W = (const bf16_t*)W; a.Y = (bf16_t*)Y;
   const size_t lds = (size_t)ST_WL_BYTES + (size_t)ST_IROWS * a.rsb;
   if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
-  if (int e = pf_require_lds(reinterpret_cast<const void*>(&k_stem7x7_fwd), lds)) return e;
-  k_stem7x7_fwd<<<stem_grid(a.n_items, 512), ST_THREADS, lds, (hipStream_t)stream>>>(a);
-  PF_LAUNCH_CHECK();
-  return 0;
+  return pf_launch_lds(&k_stem7x7_fwd, stem_grid(a.n_items, 512), ST_THREADS, lds, (hipStream_t)stream, a);
 }
 
 
@@ -197,14 +194,9 @@ __global__ __launch_bounds__(ST_THREADS) void k_stem7x7_wrw(StemWrwArgs a) {
       bf16x8 df[2];
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        const st_v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (__attribute__((address_space(3))) st_v4s*)(dbase + (pg_lo * 4 + nb0 + i) * 256 + tr_off));
-        const st_v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (__attribute__((address_space(3))) st_v4s*)(dbase + ((pg_lo + 2) * 4 + nb0 + i) * 256 + tr_off));
-        st_v8s d8;
-        d8[0] = lo[0]; d8[1] = lo[1]; d8[2] = lo[2]; d8[3] = lo[3];
-        d8[4] = hi[0]; d8[5] = hi[1]; d8[6] = hi[2]; d8[7] = hi[3];
-        df[i] = *reinterpret_cast<const bf16x8*>(&d8);
+        const pf_v4s lo = pf_tr_read(dbase + (pg_lo * 4 + nb0 + i) * 256 + tr_off);
+        const pf_v4s hi = pf_tr_read(dbase + ((pg_lo + 2) * 4 + nb0 + i) * 256 + tr_off);
+        df[i] = pf_join(lo, hi);
       }
       // this lane's two X pixels of the step: lin -> (output row of the strip, ox)
       int lin = st * 32 + p_lo;
@@ -218,14 +210,9 @@ __global__ __launch_bounds__(ST_THREADS) void k_stem7x7_wrw(StemWrwArgs a) {
         if (rr < nr) {
 #pragma unroll
           for (int h = 0; h < 2; ++h) {
-            const st_v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                (__attribute__((address_space(3))) st_v4s*)(xlo + (int64_t)rr * a.rsb + h * 32));
-            const st_v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                (__attribute__((address_space(3))) st_v4s*)(xhi + (int64_t)rr * a.rsb + h * 32));
-            st_v8s x8;
-            x8[0] = lo[0]; x8[1] = lo[1]; x8[2] = lo[2]; x8[3] = lo[3];
-            x8[4] = hi[0]; x8[5] = hi[1]; x8[6] = hi[2]; x8[7] = hi[3];
-            const bf16x8 xf = *reinterpret_cast<const bf16x8*>(&x8);
+            const pf_v4s lo = pf_tr_read(xlo + (int64_t)rr * a.rsb + h * 32);
+            const pf_v4s hi = pf_tr_read(xhi + (int64_t)rr * a.rsb + h * 32);
+            const bf16x8 xf = pf_join(lo, hi);
 #pragma unroll
             for (int i = 0; i < 2; ++i)
               acc[i][rr * 2 + h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(df[i], xf, acc[i][rr * 2 + h], 0, 0, 0);
@@ -269,8 +256,6 @@ extern "C" int pf_conv_stem_wrw(const void* dY, const void* X, void* dW, int dw_
   a.dY = (const bf16_t*)dY; a.slabs = workspace;
   a.dy_bytes = (int)stem_dy_bytes(imgs, a.Ho, a.Wo, ST_N);
   const size_t lds = (size_t)SW_IROWS * a.rsb + (size_t)SW_OROWS * a.Wo * ST_N * 2;
-  if (int e = pf_require_lds(reinterpret_cast<const void*>(&k_stem7x7_wrw), lds)) return e;
-  k_stem7x7_wrw<<<S, ST_THREADS, lds, (hipStream_t)stream>>>(a);
-  PF_LAUNCH_CHECK();
+  if (int e = pf_launch_lds(&k_stem7x7_wrw, S, ST_THREADS, lds, (hipStream_t)stream, a)) return e;
   return pf_wrw_reduce(workspace, S, (int64_t)ST_N * 147, dW, dw_dtype, (hipStream_t)stream);
 }

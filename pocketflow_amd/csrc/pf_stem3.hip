@@ -126,13 +126,7 @@ extern "C" int pf_conv_stem3_fwd(const void* X, const void* W, void* Y, int imgs
   a.W = (const bf16_t*)W; a.Y = (bf16_t*)Y; a.ph = pad_h; a.pw = pad_w;
   const size_t lds = (size_t)N * S3_R * 64 + (size_t)S3_IROWS * a.rsb + 16;
   if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
-  const void* fn = (N == 32) ? reinterpret_cast<const void*>(&k_stem3x3_fwd<2>) : reinterpret_cast<const void*>(&k_stem3x3_fwd<1>);
-  if (int e = pf_require_lds(fn, lds)) return e;
-  const int grid = stem_grid(a.n_items, 1024);
-  if (N == 32) k_stem3x3_fwd<2><<<grid, ST_THREADS, lds, (hipStream_t)stream>>>(a);
-  else k_stem3x3_fwd<1><<<grid, ST_THREADS, lds, (hipStream_t)stream>>>(a);
-  PF_LAUNCH_CHECK();
-  return 0;
+  return pf_launch_lds(N == 32 ? &k_stem3x3_fwd<2> : &k_stem3x3_fwd<1>, stem_grid(a.n_items, 1024), ST_THREADS, lds, (hipStream_t)stream, a);
 }
 
 // =================================================================================================================
@@ -195,14 +189,9 @@ __global__ __launch_bounds__(ST_THREADS) void k_stem3x3_wrw(Stem3WrwArgs a) {
     // ---- 32 pixels per step ----
     for (int st = 0; st < steps; ++st) {
       const unsigned char* dbase = dys + st * (4 * NB * 256);
-      const st_v4s dlo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-          (__attribute__((address_space(3))) st_v4s*)(dbase + (pg_lo * NB + nb0) * 256 + tr_off));
-      const st_v4s dhi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-          (__attribute__((address_space(3))) st_v4s*)(dbase + ((pg_lo + 2) * NB + nb0) * 256 + tr_off));
-      st_v8s d8;
-      d8[0] = dlo[0]; d8[1] = dlo[1]; d8[2] = dlo[2]; d8[3] = dlo[3];
-      d8[4] = dhi[0]; d8[5] = dhi[1]; d8[6] = dhi[2]; d8[7] = dhi[3];
-      const bf16x8 df = *reinterpret_cast<const bf16x8*>(&d8);
+      const pf_v4s dlo = pf_tr_read(dbase + (pg_lo * NB + nb0) * 256 + tr_off);
+      const pf_v4s dhi = pf_tr_read(dbase + ((pg_lo + 2) * NB + nb0) * 256 + tr_off);
+      const bf16x8 df = pf_join(dlo, dhi);
       // this lane's two X pixels of the step: lin -> (output row of the strip, ox)
       int lin = st * 32 + p_lo;
       int orow = lin >= a.Wo ? 1 : 0;
@@ -213,12 +202,9 @@ __global__ __launch_bounds__(ST_THREADS) void k_stem3x3_wrw(Stem3WrwArgs a) {
 #pragma unroll
       for (int rr = 0; rr < 2; ++rr) {
         if (rr < nr) {
-          const st_v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) st_v4s*)(xlo + (int64_t)rr * a.rsb));
-          const st_v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) st_v4s*)(xhi + (int64_t)rr * a.rsb));
-          st_v8s x8;
-          x8[0] = lo[0]; x8[1] = lo[1]; x8[2] = lo[2]; x8[3] = lo[3];
-          x8[4] = hi[0]; x8[5] = hi[1]; x8[6] = hi[2]; x8[7] = hi[3];
-          const bf16x8 xf = *reinterpret_cast<const bf16x8*>(&x8);
+          const pf_v4s lo = pf_tr_read(xlo + (int64_t)rr * a.rsb);
+          const pf_v4s hi = pf_tr_read(xhi + (int64_t)rr * a.rsb);
+          const bf16x8 xf = pf_join(lo, hi);
           acc[rr] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(df, xf, acc[rr], 0, 0, 0);
         }
       }
@@ -250,10 +236,6 @@ extern "C" int pf_conv_stem3_wrw(const void* dY, const void* X, void* dW, int dw
   a.dY = (const bf16_t*)dY; a.slabs = workspace; a.ph = pad_h; a.pw = pad_w;
   a.dy_bytes = (int)stem_dy_bytes(imgs, Ho, Wo, N);
   const size_t lds = (size_t)S3W_IROWS * a.rsb + (size_t)S3W_OROWS * Wo * N * 2 + 16;
-  const void* fn = (N == 32) ? reinterpret_cast<const void*>(&k_stem3x3_wrw<2>) : reinterpret_cast<const void*>(&k_stem3x3_wrw<1>);
-  if (int e = pf_require_lds(fn, lds)) return e;
-  if (N == 32) k_stem3x3_wrw<2><<<S, ST_THREADS, lds, (hipStream_t)stream>>>(a);
-  else k_stem3x3_wrw<1><<<S, ST_THREADS, lds, (hipStream_t)stream>>>(a);
-  PF_LAUNCH_CHECK();
+  if (int e = pf_launch_lds(N == 32 ? &k_stem3x3_wrw<2> : &k_stem3x3_wrw<1>, S, ST_THREADS, lds, (hipStream_t)stream, a)) return e;
   return pf_wrw_reduce(workspace, S, (int64_t)N * 27, dW, dw_dtype, (hipStream_t)stream);
 }

@@ -181,10 +181,7 @@ template <int STRIDE, int NB>
 static int s3x_launch_fwd(const Stem3xArgs& a, hipStream_t st) {
   constexpr int OROWS = STRIDE == 1 ? S3X_OROWS1 : S3X_OROWS2;
   const size_t lds = (size_t)(STRIDE * OROWS + 3 - STRIDE) * a.rsb;
-  if (int e = pf_require_lds(reinterpret_cast<const void*>(&k_stem3x_fwd<STRIDE, NB>), lds)) return e;
-  k_stem3x_fwd<STRIDE, NB><<<stem_grid(a.n_items, 1024), ST_THREADS, lds, st>>>(a);
-  PF_LAUNCH_CHECK();
-  return 0;
+  return pf_launch_lds(&k_stem3x_fwd<STRIDE, NB>, stem_grid(a.n_items, 1024), ST_THREADS, lds, st, a);
 }
 
 extern "C" int pf_conv_stem3x_fwd(const void* X, const void* W, void* Y, int imgs, int H, int Wd, int N, int stride, int pad_h, int pad_w,
@@ -258,18 +255,11 @@ __global__ __launch_bounds__(ST_THREADS) void k_stem3x_wrw(Stem3xWrwArgs a) {
         const int p = wave * PW + i;
         if (p < 3 * NB) {
           const int nb = p / 3, r = p - 3 * nb;
-          const st_v4s dlo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-              (__attribute__((address_space(3))) st_v4s*)(dbase + (pg_lo * NB + nb) * 256));
-          const st_v4s dhi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-              (__attribute__((address_space(3))) st_v4s*)(dbase + ((pg_lo + 2) * NB + nb) * 256));
-          const st_v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) st_v4s*)(xlo + r * a.rsb));
-          const st_v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) st_v4s*)(xhi + r * a.rsb));
-          st_v8s d8, x8;
-          d8[0] = dlo[0]; d8[1] = dlo[1]; d8[2] = dlo[2]; d8[3] = dlo[3];
-          d8[4] = dhi[0]; d8[5] = dhi[1]; d8[6] = dhi[2]; d8[7] = dhi[3];
-          x8[0] = lo[0]; x8[1] = lo[1]; x8[2] = lo[2]; x8[3] = lo[3];
-          x8[4] = hi[0]; x8[5] = hi[1]; x8[6] = hi[2]; x8[7] = hi[3];
-          acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8*>(&d8), *reinterpret_cast<const bf16x8*>(&x8), acc[i], 0, 0, 0);
+          const pf_v4s dlo = pf_tr_read(dbase + (pg_lo * NB + nb) * 256);
+          const pf_v4s dhi = pf_tr_read(dbase + ((pg_lo + 2) * NB + nb) * 256);
+          const pf_v4s lo = pf_tr_read(xlo + r * a.rsb);
+          const pf_v4s hi = pf_tr_read(xhi + r * a.rsb);
+          acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf_join(dlo, dhi), pf_join(lo, hi), acc[i], 0, 0, 0);
         }
       }
       ox0 += 32; ox1 += 32;
@@ -310,10 +300,7 @@ template <int STRIDE, int NB>
 static int s3x_launch_wrw(const Stem3xWrwArgs& a, int S, hipStream_t st) {
   const int steps = (a.orows * a.Wo + 31) >> 5;
   const size_t lds = (size_t)(STRIDE * a.orows + 3 - STRIDE) * a.rsb + (size_t)steps * NB * 1024;
-  if (int e = pf_require_lds(reinterpret_cast<const void*>(&k_stem3x_wrw<STRIDE, NB>), lds)) return e;
-  k_stem3x_wrw<STRIDE, NB><<<S, ST_THREADS, lds, st>>>(a);
-  PF_LAUNCH_CHECK();
-  return 0;
+  return pf_launch_lds(&k_stem3x_wrw<STRIDE, NB>, S, ST_THREADS, lds, st, a);
 }
 
 extern "C" int pf_conv_stem3x_wrw(const void* dY, const void* X, void* dW, int dw_dtype, float* workspace, int imgs, int H, int Wd, int N,

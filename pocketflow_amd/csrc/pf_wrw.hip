@@ -4,9 +4,8 @@
 //     dW[n][tap][c] = sum_m dY[m][n] * Q(X)[pix(m, tap)][c]          m = (img, ho, wo)
 //
 // The contraction runs over PIXELS, the slow index of both NHWC operands, so both MFMA operands are "transposed".
-// gfx950 reads a [4 pixels][16 channels] bf16 block out of LDS transposed in one instruction (ds_read_b64_tr_b16:
-// lane i of a 16-lane group supplies the i-th 8-byte piece of the block and receives column i); this kernel is
-// built around it:
+// gfx950 reads a [4 pixels][16 channels] bf16 block out of LDS transposed in one instruction (ds_read_b64_tr_b16,
+// pf_mfma.h); this kernel is built around it:
 //   * tiles go from global memory straight into LDS (global_load_lds, no staging registers, no 2-byte scatter) in a
 //     block layout [8 pixels][16 channels] = 256 contiguous bytes per block, so that the 32 lanes the LDS services
 //     together read one full 256-byte line: bank-conflict free.  The order in which pixels map to MFMA k-slots is a free
@@ -19,12 +18,9 @@
 //     pf_conv.hip (k_wrw_reduce): bit-reproducible, no float atomics.
 // The (n, k) tiles of one pixel split occupy consecutive workgroups of one XCD, so the rows they all read are fetched
 // from HBM once and shared through that XCD's L2.
-#include "pf_conv_common.h"
+#include "pf_mfma.h"
 #include "pf_buffer.h"
 #include <stdlib.h>
-
-typedef short v4s __attribute__((ext_vector_type(4)));
-typedef short v8s __attribute__((ext_vector_type(8)));
 
 // source of out-of-range rows / padding taps: the products must vanish, so these are real zeros (not "any readable bytes")
 __device__ __attribute__((aligned(16))) const uint32_t pf_wrw_zero_page[64] = {0};
@@ -152,10 +148,8 @@ __global__ __launch_bounds__(256) void k_wrw_tr(const WrwArgs a) {
     bf16x8 xf[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-          (__attribute__((address_space(3))) v4s*)(sbase + DY_BYTES + (pg_lo * 4 + j) * 256 + tr_off));
-      const v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-          (__attribute__((address_space(3))) v4s*)(sbase + DY_BYTES + ((pg_lo + 2) * 4 + j) * 256 + tr_off));
+      const pf_v4s lo = pf_tr_read(sbase + DY_BYTES + (pg_lo * 4 + j) * 256 + tr_off);
+      const pf_v4s hi = pf_tr_read(sbase + DY_BYTES + ((pg_lo + 2) * 4 + j) * 256 + tr_off);
       uint4 u;
       u.x = (uint32_t)(uint16_t)lo[0] | ((uint32_t)(uint16_t)lo[1] << 16);
       u.y = (uint32_t)(uint16_t)lo[2] | ((uint32_t)(uint16_t)lo[3] << 16);
@@ -172,14 +166,9 @@ __global__ __launch_bounds__(256) void k_wrw_tr(const WrwArgs a) {
     }
 #pragma unroll
     for (int i = 0; i < NB; ++i) {
-      const v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-          (__attribute__((address_space(3))) v4s*)(sbase + (pg_lo * NB + i) * 256 + tr_off));
-      const v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-          (__attribute__((address_space(3))) v4s*)(sbase + ((pg_lo + 2) * NB + i) * 256 + tr_off));
-      v8s d8;
-      d8[0] = lo[0]; d8[1] = lo[1]; d8[2] = lo[2]; d8[3] = lo[3];
-      d8[4] = hi[0]; d8[5] = hi[1]; d8[6] = hi[2]; d8[7] = hi[3];
-      const bf16x8 df = *reinterpret_cast<const bf16x8*>(&d8);
+      const pf_v4s lo = pf_tr_read(sbase + (pg_lo * NB + i) * 256 + tr_off);
+      const pf_v4s hi = pf_tr_read(sbase + ((pg_lo + 2) * NB + i) * 256 + tr_off);
+      const bf16x8 df = pf_join(lo, hi);
 #pragma unroll
       for (int j = 0; j < 4; ++j)
         acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(df, xf[j], acc[i][j], 0, 0, 0);
@@ -245,10 +234,7 @@ static int wrw_tr_launch_t(const WrwArgs& a, int grid, hipStream_t st) {
   const size_t ring = 4 * (size_t)3 * ((4 * NB + 16) * 256);
   const size_t red = (size_t)4 * NB * 4 * 64 * 16;
   const size_t lds = ring > red ? ring : red;
-  if (int e = pf_require_lds(reinterpret_cast<const void*>(&k_wrw_tr<BN, PRO, MAP>), lds)) return e;
-  k_wrw_tr<BN, PRO, MAP><<<grid, 256, lds, st>>>(a);
-  PF_LAUNCH_CHECK();
-  return 0;
+  return pf_launch_lds(&k_wrw_tr<BN, PRO, MAP>, grid, 256, lds, st, a);
 }
 
 // slabs: [S][N][taps*C] floats, S from pf_wrw_plan
@@ -309,21 +295,12 @@ int pf_wrw_tr_launch(const void* dY, const void* X, float* slabs, const float* s
 #endif
 
 // MFMA fragments (8 consecutive pixels of one channel each: two transposing reads, `lo` at p + off and `hi` at
-// p + off + HI) through INLINE ASM.  Reason: hipcc (ROCm 7.2) puts `s_waitcnt vmcnt(0)` in front of the first
-// __builtin_amdgcn_ds_read_tr16_b64 it meets while an LDS-DMA is pending (it treats the DMA as a store the read may alias):
-// in k_wrw2 that wait sat right behind the issue of the NEXT stage's loads, i.e. every step waited for the prefetch it had
-// just started -- no overlap of loads and matrix work at all.  The asm reads are invisible to that pass; the statement
-// carries its own lgkmcnt(0), so the results are valid when it ends.  The caller guarantees the stage has landed (own
-// counted vmcnt + barrier).
-__device__ __forceinline__ bf16x8 tr_join(const v4s& lo, const v4s& hi) {
-  v8s x8;
-  x8[0] = lo[0]; x8[1] = lo[1]; x8[2] = lo[2]; x8[3] = lo[3];
-  x8[4] = hi[0]; x8[5] = hi[1]; x8[6] = hi[2]; x8[7] = hi[3];
-  return *reinterpret_cast<const bf16x8*>(&x8);
-}
+// p + off + HI) through INLINE ASM, because the next stage's LDS-DMA is pending here (pf_mfma.h has the reason).  Unlike
+// pf_tr_issue these statements carry their own lgkmcnt(0), so the results are valid when one ends: a whole k-step's reads
+// behind one wait is this kernel's schedule.  The caller guarantees the stage has landed (own counted vmcnt + barrier).
 template <int HI>
 __device__ __forceinline__ void tr_read_frags(uint32_t p, bf16x8 (&f)[4]) {
-  v4s l0, l1, l2, l3, h0, h1, h2, h3;
+  pf_v4s l0, l1, l2, l3, h0, h1, h2, h3;
   asm volatile("ds_read_b64_tr_b16 %0, %8\n\tds_read_b64_tr_b16 %4, %8 offset:%9\n\t"
                "ds_read_b64_tr_b16 %1, %8 offset:256\n\tds_read_b64_tr_b16 %5, %8 offset:%10\n\t"
                "ds_read_b64_tr_b16 %2, %8 offset:512\n\tds_read_b64_tr_b16 %6, %8 offset:%11\n\t"
@@ -332,25 +309,25 @@ __device__ __forceinline__ void tr_read_frags(uint32_t p, bf16x8 (&f)[4]) {
                : "=&v"(l0), "=&v"(l1), "=&v"(l2), "=&v"(l3), "=&v"(h0), "=&v"(h1), "=&v"(h2), "=&v"(h3)
                : "v"(p), "n"(HI), "n"(HI + 256), "n"(HI + 512), "n"(HI + 768)
                : "memory");
-  f[0] = tr_join(l0, h0); f[1] = tr_join(l1, h1); f[2] = tr_join(l2, h2); f[3] = tr_join(l3, h3);
+  f[0] = pf_join(l0, h0); f[1] = pf_join(l1, h1); f[2] = pf_join(l2, h2); f[3] = pf_join(l3, h3);
 }
 template <int HI>
 __device__ __forceinline__ void tr_read_frags(uint32_t p, bf16x8 (&f)[2]) {
-  v4s l0, l1, h0, h1;
+  pf_v4s l0, l1, h0, h1;
   asm volatile("ds_read_b64_tr_b16 %0, %4\n\tds_read_b64_tr_b16 %2, %4 offset:%5\n\t"
                "ds_read_b64_tr_b16 %1, %4 offset:256\n\tds_read_b64_tr_b16 %3, %4 offset:%6\n\t"
                "s_waitcnt lgkmcnt(0)"
                : "=&v"(l0), "=&v"(l1), "=&v"(h0), "=&v"(h1)
                : "v"(p), "n"(HI), "n"(HI + 256)
                : "memory");
-  f[0] = tr_join(l0, h0); f[1] = tr_join(l1, h1);
+  f[0] = pf_join(l0, h0); f[1] = pf_join(l1, h1);
 }
 
 // BOTH operands' fragments behind one wait (round 4; measured with the other scheduling changes, +2.2 % per step) -- the two calls above expose
 // two LDS round trips per k-step of ~16 MFMAs
 template <int HIX, int HID>
 __device__ __forceinline__ void tr_read_frags2(uint32_t px, uint32_t pd, bf16x8 (&xf)[4], bf16x8 (&df)[4]) {
-  v4s a0, a1, a2, a3, b0, b1, b2, b3, c0, c1, c2, c3, d0, d1, d2, d3;
+  pf_v4s a0, a1, a2, a3, b0, b1, b2, b3, c0, c1, c2, c3, d0, d1, d2, d3;
   asm volatile("ds_read_b64_tr_b16 %0, %16\n\tds_read_b64_tr_b16 %4, %16 offset:%18\n\t"
                "ds_read_b64_tr_b16 %1, %16 offset:256\n\tds_read_b64_tr_b16 %5, %16 offset:%19\n\t"
                "ds_read_b64_tr_b16 %2, %16 offset:512\n\tds_read_b64_tr_b16 %6, %16 offset:%20\n\t"
@@ -365,8 +342,8 @@ __device__ __forceinline__ void tr_read_frags2(uint32_t px, uint32_t pd, bf16x8 
                : "v"(px), "v"(pd), "n"(HIX), "n"(HIX + 256), "n"(HIX + 512), "n"(HIX + 768), "n"(HID), "n"(HID + 256), "n"(HID + 512),
                  "n"(HID + 768)
                : "memory");
-  xf[0] = tr_join(a0, b0); xf[1] = tr_join(a1, b1); xf[2] = tr_join(a2, b2); xf[3] = tr_join(a3, b3);
-  df[0] = tr_join(c0, d0); df[1] = tr_join(c1, d1); df[2] = tr_join(c2, d2); df[3] = tr_join(c3, d3);
+  xf[0] = pf_join(a0, b0); xf[1] = pf_join(a1, b1); xf[2] = pf_join(a2, b2); xf[3] = pf_join(a3, b3);
+  df[0] = pf_join(c0, d0); df[1] = pf_join(c1, d1); df[2] = pf_join(c2, d2); df[3] = pf_join(c3, d3);
 }
 
 struct Wrw2Args {
@@ -553,7 +530,7 @@ __global__ __launch_bounds__(64 * (TN / WTN) * (TK / WTK)) void k_wrw2(const Wrw
   if (nsteps > 0) stage(0, 0);
   if (nsteps > 1) { stage(1, 1); wrw_wait_vm<LPS>(); } else wrw_wait_vm<0>();
   if (PRO && nsteps > 0) transform(0);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  pf_lds_wait();
   __builtin_amdgcn_s_barrier();
   int buf = 0, ibuf = 2;
 #ifdef PF_W2_TIMING
@@ -595,7 +572,7 @@ __global__ __launch_bounds__(64 * (TN / WTN) * (TK / WTK)) void k_wrw2(const Wrw
       PF_W2_STAMP(4);
       if (PRO) transform(buf);
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    pf_lds_wait();
     PF_W2_STAMP(5);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
@@ -659,10 +636,7 @@ int pf_wrw2_splits(int M, int N, int C, int taps) {
 template <int TN, int TK, int WTN, int WTK, bool PRO, int MAPM>
 static int wrw2_launch_t(const Wrw2Args& a, int grid, hipStream_t st) {
   const size_t lds = 3 * (size_t)(4 * (TN / 16) * 256 + 4 * (TK / 16) * 256) + 1024;   // three stages + the 1 KiB sink
-  if (int e = pf_require_lds(reinterpret_cast<const void*>(&k_wrw2<TN, TK, WTN, WTK, PRO, MAPM>), lds)) return e;
-  k_wrw2<TN, TK, WTN, WTK, PRO, MAPM><<<grid, 64 * (TN / WTN) * (TK / WTK), lds, st>>>(a);
-  PF_LAUNCH_CHECK();
-  return 0;
+  return pf_launch_lds(&k_wrw2<TN, TK, WTN, WTK, PRO, MAPM>, grid, 64 * (TN / WTN) * (TK / WTK), lds, st, a);
 }
 
 int pf_wrw2_launch(const void* dY, const void* X, float* slabs, const float* scale_shift, int act, const uint32_t* slot,

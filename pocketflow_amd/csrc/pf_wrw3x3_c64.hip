@@ -15,11 +15,8 @@
 //     nine taps per wavefront = 144 registers; per 32-pixel k-block a wavefront reads 4 dY and 9 X fragments
 //     for 36 MFMAs;
 //   * one float32 slab [64][576] per workgroup at the end, folded by pf_wrw_reduce in a fixed order (deterministic).
-#include "pf_conv_common.h"
+#include "pf_mfma.h"
 #include "pf_igemm.h"
-
-typedef short w3_v4s __attribute__((ext_vector_type(4)));
-typedef short w3_v8s __attribute__((ext_vector_type(8)));
 
 #define W3_W 56
 #define W3_C 64
@@ -42,20 +39,10 @@ struct Wrw3Args {
   int n_tiles;
 };
 
-template <int OFF>
-__device__ __forceinline__ void w3_tr(uint32_t p, w3_v4s& v) {
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=&v"(v) : "v"(p), "n"(OFF) : "memory");
-}
-__device__ __forceinline__ bf16x8 w3_join(const w3_v4s& lo, const w3_v4s& hi) {
-  w3_v8s x;
-  x[0] = lo[0]; x[1] = lo[1]; x[2] = lo[2]; x[3] = lo[3];
-  x[4] = hi[0]; x[5] = hi[1]; x[6] = hi[2]; x[7] = hi[3];
-  return *reinterpret_cast<const bf16x8*>(&x);
-}
-__device__ __forceinline__ void w3_wait8(w3_v4s (&v)[8]) {
+__device__ __forceinline__ void w3_wait8(pf_v4s (&v)[8]) {
   asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]) : : "memory");
 }
-__device__ __forceinline__ void w3_wait6(w3_v4s (&v)[6]) {
+__device__ __forceinline__ void w3_wait6(pf_v4s (&v)[6]) {
   asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]) : : "memory");
 }
 
@@ -64,16 +51,16 @@ __device__ __forceinline__ void w3_wait6(w3_v4s (&v)[6]) {
 // sits in the base address -- with per-wavefront immediates the four instantiations of the tile body cost 565 spilled registers.)
 template <int KB, int E>
 __device__ __forceinline__ void w3_cols(const uint32_t (&xb)[4][2], const bf16x8 (&df)[4], f32x4 (&acc)[4][9]) {
-  w3_v4s v[6];
+  pf_v4s v[6];
 #define W3_OFF(e) ((((e) / 3) * W3_WCOLS + (e) % 3) * W3_PITCH)
-  w3_tr<W3_OFF(E)>(xb[KB][0], v[0]);     w3_tr<W3_OFF(E)>(xb[KB][1], v[1]);
-  w3_tr<W3_OFF(E + 1)>(xb[KB][0], v[2]); w3_tr<W3_OFF(E + 1)>(xb[KB][1], v[3]);
-  w3_tr<W3_OFF(E + 2)>(xb[KB][0], v[4]); w3_tr<W3_OFF(E + 2)>(xb[KB][1], v[5]);
+  pf_tr_issue<W3_OFF(E)>(xb[KB][0], v[0]);     pf_tr_issue<W3_OFF(E)>(xb[KB][1], v[1]);
+  pf_tr_issue<W3_OFF(E + 1)>(xb[KB][0], v[2]); pf_tr_issue<W3_OFF(E + 1)>(xb[KB][1], v[3]);
+  pf_tr_issue<W3_OFF(E + 2)>(xb[KB][0], v[4]); pf_tr_issue<W3_OFF(E + 2)>(xb[KB][1], v[5]);
 #undef W3_OFF
   w3_wait6(v);
 #pragma unroll
   for (int e = 0; e < 3; ++e) {
-    const bf16x8 xf = w3_join(v[2 * e], v[2 * e + 1]);
+    const bf16x8 xf = pf_join(v[2 * e], v[2 * e + 1]);
 #pragma unroll
     for (int i = 0; i < 4; ++i) acc[i][E + e] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(df[i], xf, acc[i][E + e], 0, 0, 0);
   }
@@ -82,15 +69,15 @@ __device__ __forceinline__ void w3_cols(const uint32_t (&xb)[4][2], const bf16x8
 template <int KB>
 __device__ __forceinline__ void w3_kblock(uint32_t dyb, const uint32_t (&xb)[4][2], f32x4 (&acc)[4][9]) {
   // dY fragments of the four 16-channel blocks: pixel rows kb * 32 + {q * 4 + (l15 >> 2)} (lo) and + 16 (hi)
-  w3_v4s d[8];
-  w3_tr<KB * 32 * W3_PITCH + 0>(dyb, d[0]);   w3_tr<KB * 32 * W3_PITCH + 16 * W3_PITCH + 0>(dyb, d[1]);
-  w3_tr<KB * 32 * W3_PITCH + 32>(dyb, d[2]);  w3_tr<KB * 32 * W3_PITCH + 16 * W3_PITCH + 32>(dyb, d[3]);
-  w3_tr<KB * 32 * W3_PITCH + 64>(dyb, d[4]);  w3_tr<KB * 32 * W3_PITCH + 16 * W3_PITCH + 64>(dyb, d[5]);
-  w3_tr<KB * 32 * W3_PITCH + 96>(dyb, d[6]);  w3_tr<KB * 32 * W3_PITCH + 16 * W3_PITCH + 96>(dyb, d[7]);
+  pf_v4s d[8];
+  pf_tr_issue<KB * 32 * W3_PITCH + 0>(dyb, d[0]);   pf_tr_issue<KB * 32 * W3_PITCH + 16 * W3_PITCH + 0>(dyb, d[1]);
+  pf_tr_issue<KB * 32 * W3_PITCH + 32>(dyb, d[2]);  pf_tr_issue<KB * 32 * W3_PITCH + 16 * W3_PITCH + 32>(dyb, d[3]);
+  pf_tr_issue<KB * 32 * W3_PITCH + 64>(dyb, d[4]);  pf_tr_issue<KB * 32 * W3_PITCH + 16 * W3_PITCH + 64>(dyb, d[5]);
+  pf_tr_issue<KB * 32 * W3_PITCH + 96>(dyb, d[6]);  pf_tr_issue<KB * 32 * W3_PITCH + 16 * W3_PITCH + 96>(dyb, d[7]);
   w3_wait8(d);
   bf16x8 df[4];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) df[i] = w3_join(d[2 * i], d[2 * i + 1]);
+  for (int i = 0; i < 4; ++i) df[i] = pf_join(d[2 * i], d[2 * i + 1]);
   w3_cols<KB, 0>(xb, df, acc);
   w3_cols<KB, 3>(xb, df, acc);
   w3_cols<KB, 6>(xb, df, acc);
@@ -204,8 +191,5 @@ int pf_wrw3x3_c64_launch(const void* dY, const void* X, float* slabs, int imgs, 
   a.dY = (const bf16_t*)dY; a.X = (const bf16_t*)X; a.slabs = slabs;
   a.bytes = (uint32_t)((int64_t)imgs * W3_W * W3_W * W3_C * 2);
   a.n_tiles = imgs * (W3_W / 2);
-  if (int e = pf_require_lds(reinterpret_cast<const void*>(&k_wrw3x3_c64), W3_LDS)) return e;
-  k_wrw3x3_c64<<<pf_wrw3x3_c64_splits(imgs), W3_THREADS, W3_LDS, st>>>(a);
-  PF_LAUNCH_CHECK();
-  return 0;
+  return pf_launch_lds(&k_wrw3x3_c64, pf_wrw3x3_c64_splits(imgs), W3_THREADS, W3_LDS, st, a);
 }
