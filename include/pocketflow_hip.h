@@ -471,6 +471,24 @@ int pf_conv3x3n_wrw_slabs(int imgs, int H, int Wd, int C, int N);
 int pf_conv3x3n_wrw(const void* dY, const void* X, void* dW, int dw_dtype, float* workspace, int imgs, int H, int Wd, int C, int N,
                     void* stream);
 
+/* ---- 5x5 / stride 1 / 'VALID' convolutions WITH A BIAS (pf_conv5v.hip): C in {3, 32}, N in {32, 64}, the convolutions of LeNet @
+ * CIFAR-10 (nets/lenet_at_cifar10.py) ------------------------------------------------------------------------------------------------
+ * X / dX [imgs][H][Wd][C] bf16 (NHWC), W [N][5][5][C] bf16 (KRSC), Y / dY [imgs][H - 4][Wd - 4][N] bf16, bias / db [N] float32 (either
+ * may be NULL).  H >= 5, 5 <= Wd <= 64 (pf_conv5v_supported: pure host; k, stride and the pads are the layer's: 5, 1, 0, 0); imgs >= 1
+ * and both tensors below 2^31 bytes (pf_conv5v_wrw_slabs: 0 slabs = not taken).  Y, dY, dW and the workspace 16-byte aligned, and with
+ * C = 32 X, dX and W too.  The launchers return hipErrorInvalidValue for anything else; they neither allocate nor synchronise.
+ * pf_conv5v_fwd: Y = conv(X, W) + bias, the bias added in float32 before the one rounding.
+ * pf_conv5v_bwd_data (C = 32 only): dX = the full correlation of dY with Wt [C][5][5][N], Wt[c][4 - r][4 - s][n] = W[n][r][s][c].
+ * pf_conv5v_wrw: dW [N][5][5][C] in dw_dtype (PF_F32 / PF_BF16) and db[n] = sum of dY over all pixels, both deterministic (one slab
+ * per workgroup and its [N] partial sums of dY behind them, fixed-order folds); workspace (pf_conv5v_wrw_slabs(...) + 32) * N * 25 * C floats.  Activations
+ * must be finite.                                                                                                                     */
+int pf_conv5v_supported(int H, int Wd, int C, int N, int k, int stride, int pad_h, int pad_w);
+int pf_conv5v_fwd(const void* X, const void* W, const float* bias, void* Y, int imgs, int H, int Wd, int C, int N, void* stream);
+int pf_conv5v_bwd_data(const void* dY, const void* Wt, void* dX, int imgs, int H, int Wd, int C, int N, void* stream);
+int pf_conv5v_wrw_slabs(int imgs, int H, int Wd, int C, int N);
+int pf_conv5v_wrw(const void* dY, const void* X, void* dW, int dw_dtype, float* db, float* workspace, int imgs, int H, int Wd, int C,
+                  int N, void* stream);
+
 /* ---- dense layers on the matrix cores (pf_dense.hip): tf.layers.dense and MobileNet's logits, any N (1001, 10, ...) ------------------
  * X / dX [B][K] bf16, W / dW [N][K] (the store's [out][in]; dW in dw_dtype, PF_F32 / PF_BF16), Y / dY [B][N] bf16, bias / db [N]
  * float32.  K % 32 == 0, K >= 32, any N >= 1, any B >= 1, B * K * 2, N * K * 4 and B * N * 2 below 2^31 (pf_dense_supported: pure

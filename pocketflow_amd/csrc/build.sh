@@ -21,7 +21,7 @@ stale() {
 }
 OBJS=()
 PIDS=()
-for f in pf_api pf_quant pf_normalize pf_sparse pf_optim pf_loss pf_bn pf_conv pf_conv_stream pf_igemm pf_conv3x3_c64 pf_wrw3x3_c64 pf_conv3x3_narrow pf_dense pf_wrw pf_pool pf_transpose pf_stem pf_stem3 pf_stem3x pf_image pf_depthwise pf_convg pf_prox pf_im2col pf_cpr pf_conv_gather pf_conv_i8 pf_depthwise_i8 pf_act_static pf_conv_i8_q pf_depthwise_i8_q pf_bn_join; do
+for f in pf_api pf_quant pf_normalize pf_sparse pf_optim pf_loss pf_bn pf_conv pf_conv_stream pf_igemm pf_conv3x3_c64 pf_wrw3x3_c64 pf_conv3x3_narrow pf_conv5v pf_dense pf_wrw pf_pool pf_transpose pf_stem pf_stem3 pf_stem3x pf_image pf_depthwise pf_convg pf_prox pf_im2col pf_cpr pf_conv_gather pf_conv_i8 pf_depthwise_i8 pf_act_static pf_conv_i8_q pf_depthwise_i8_q pf_bn_join; do
   if stale "$f"; then
     rm -f "$f.o"
     $HIPCC $FLAGS -c "$f.hip" -o "$f.o" &

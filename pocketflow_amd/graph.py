@@ -1387,6 +1387,9 @@ OWN_DEPTHWISE = os.environ.get('PF_OWN_DEPTHWISE', '1') != '0'   # depthwise 3x3
 OWN_CONV_IM2COL = os.environ.get('PF_OWN_CONV_IM2COL', '1') != '0'   # few-channel RxS convolutions as im2col + own 1x1 kernels (0: MIOpen)
 # 3x3 / stride 1 / pad 1 with 16 | 32 channels on pf_conv3x3_narrow.hip, one launch per pass (0: im2col, for A/B runs)
 OWN_CONV3X3_NARROW = os.environ.get('PF_OWN_CONV3X3_NARROW', '1') != '0'
+# 5x5 / stride 1 / 'VALID' with 3 | 32 input and 32 | 64 output channels, bias or not, on pf_conv5v.hip: LeNet's two convolutions
+# (0: pf_convg.hip for 3 input channels, the library for 32, as before; for A/B runs)
+OWN_CONV5V = os.environ.get('PF_OWN_CONV5V', '1') != '0'
 CONVG_BF16_NARROW = os.environ.get('PF_CONVG_BF16_NARROW', '0') != '0'
 # inference-mode BN + activation applied in the epilogue of the producing convolution (teacher / evaluation of unquantised networks)
 FOLD_EVAL_BN = os.environ.get('PF_FOLD_EVAL_BN', '1') != '0'
@@ -1572,8 +1575,9 @@ def convg_ok(x: torch.Tensor, w: torch.Tensor, dense: bool = False) -> bool:
   """float32: every convolution and dense layer.  bf16: the dense layer and convolutions over images (C % 8 != 0); a bf16
   convolution with 16 / 32 / 48 ... input channels (ResNet-20 @ CIFAR-10) is MFMA-shaped work that the vector-ALU kernel runs 2x
   slower per step than MIOpen (measured, configuration C1: 33 665 vs 66 174 images/s) -- it is not offered to this kernel
-  (PF_CONVG_BF16_NARROW=1 forces it): Conv2D._route gives the 3x3 / stride 1 layers with 16 | 32 channels to pf_conv3x3_narrow.hip
-  and the other bias-free ones with C % 8 == 0 to im2col + the 1x1 kernels before this is asked; what is left goes to the library."""
+  (PF_CONVG_BF16_NARROW=1 forces it): Conv2D._route gives the 3x3 / stride 1 layers with 16 | 32 channels to pf_conv3x3_narrow.hip,
+  the 5x5 / 'VALID' layers with 32 channels (bias or not) to pf_conv5v.hip and the other bias-free ones with C % 8 == 0 to im2col +
+  the 1x1 kernels before this is asked; what is left goes to the library."""
   if not (OWN_CONV_GENERIC and isinstance(x, torch.Tensor) and x.is_cuda and x.dtype in (torch.float32, torch.bfloat16)
           and w.dtype in (torch.float32, torch.bfloat16) and x.numel() > 0):
     return False
@@ -1766,6 +1770,69 @@ class _Conv3x3Narrow(torch.autograd.Function):
       with region('conv3x3n_bwd_data', float((dy.numel() + dx.numel()) * 2)):
         hip.conv3x3n_fwd(dy, wb, dx, B, H, Wd, N, C)
     return dx, dw, (dy if ctx.needs_input_grad[2] else None), None, None
+
+
+def _run_conv5v(x, w_krsc, bias):
+  """x: logical NCHW / physical NHWC bf16; w_krsc: KRSC memory [N][5][5][C]; bias: [N] or None -- added inside the launch, in float32,
+  before the one rounding."""
+  B, C, H, Wd = x.shape
+  N = w_krsc.shape[0]
+  y = torch.empty((B, N, H - 4, Wd - 4), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+  bf = None if bias is None else bias.detach().float().contiguous()
+  with region('conv5v_fwd', float((x.numel() + w_krsc.numel() + y.numel()) * 2)):
+    hip.conv5v_fwd(x, w_krsc, bf, y, B, H, Wd, C, N)
+  return y
+
+
+class _Conv5Valid(torch.autograd.Function):
+  """y = conv2d(x, W) (+ bias) for 5x5 / stride 1 / 'VALID' with 3 | 32 input and 32 | 64 output channels (LeNet @ CIFAR-10) on
+  pf_conv5v.hip: one launch per pass.  Backward-data (32 input channels only: Conv2D._route refuses an image that asks for its
+  gradient) runs on the flipped / transposed kernel; the filter gradient is written straight into the flat gradient buffer, on the
+  side queue where one is armed, and the same launch leaves db, the sum of dy over all pixels, in float32 -- in the flat buffer the
+  bias lives in where its gradient is a view of it."""
+
+  @staticmethod
+  def forward(ctx, x, w, bias, graph, w_var):
+    ctx.save_for_backward(x, w)
+    ctx.meta = (graph, w_var, bias)
+    return _run_conv5v(x, _krsc(w, x.dtype), bias)
+
+  @staticmethod
+  def backward(ctx, dy):
+    x, w = ctx.saved_tensors
+    graph, w_var, bias = ctx.meta
+    B, C, H, Wd = x.shape
+    N = w.shape[0]
+    dy = _nhwc(dy)
+    if dy.dtype != x.dtype:
+      dy = dy.to(x.dtype)
+    dx = dw = db = None
+    want_db = bias is not None and ctx.needs_input_grad[2]
+    if ctx.needs_input_grad[1]:
+      S = hip.conv5v_wrw_slabs(B, H, Wd, C, N)
+      bview = _grad_view(bias, N) if want_db else None
+      db = bview if bview is not None else (torch.empty(N, dtype=torch.float32, device=x.device) if want_db else None)
+
+      def wrw(dwk, scratch):                     # dwk: [N][5][5][C] memory
+        hip.conv5v_wrw(dy, x, dwk, db, scratch(_wrw_floats(S, w.numel())), B, H, Wd, C, N)
+      dw = _filter_grad(graph, w, w_var, (dy, x, db), 'conv5v_wrw', float((x.numel() + dy.numel()) * 2), wrw)
+      if bview is not None:
+        db = None                                # autograd sees no gradient for the bias: it stands in the flat buffer
+      elif db is not None:
+        # db goes to autograd, which reads it on this queue: wait for the side queue where the filter launch ran there
+        side = getattr(getattr(graph, 'store', None), 'wrw_side', None)
+        if side is not None and side.forks:
+          torch.cuda.current_stream(side.device).wait_stream(side.stream)
+    elif want_db:
+      db = dy.float().sum(dim=(0, 2, 3))
+    if ctx.needs_input_grad[0]:
+      if C != 32:
+        raise RuntimeError('pf_conv5v.hip computes no image gradient')
+      wb = _bwd_data_weight(graph, w_var, w)                                              # [C][5][5][N], flipped
+      dx = torch.empty_like(x)
+      with region('conv5v_bwd_data', float((dy.numel() + w.numel() + dx.numel()) * 2)):
+        hip.conv5v_bwd_data(dy, wb, dx, B, H, Wd, C, N)
+    return dx, dw, db, None, None
 
 
 # One stem route (Conv2D._route builds it once per call): `k` names the kernel family -- 7: the ResNet stem, 7x7 / stride 2 / pad 3,
@@ -2022,7 +2089,7 @@ def dw_lazy_on(C: int, stride: int, quantised: bool, dtype) -> bool:
 ROUTE_NAME, ROUTE_X = 0, 1
 
 # the Conv2D routes that count themselves on the producer's BnSums (the table stands at BnSums.add_consumer)
-_CONV2D_COUNTED = frozenset(['conv1x1', 'igemm', 'conv3x3n', 'im2col', 'general', 'library'])
+_CONV2D_COUNTED = frozenset(['conv1x1', 'igemm', 'conv5v', 'conv3x3n', 'im2col', 'general', 'library'])
 
 
 @contextlib.contextmanager
@@ -2081,6 +2148,9 @@ class Conv2D:
       stem         any stem kernel (_stem_geom), asked BEFORE _symmetric_pads: the 3x3 kernels take the asymmetric 'SAME' pads by
                    their front pads and must not see (or pay for) a padded copy of the image; the 7x7 kernel pads both ends by 3,
                    which is what its layer hands over, so no copy is ever in question for it.
+      conv5v       5x5 / stride 1 / 'VALID' with 3 | 32 input and 32 | 64 output channels on pf_conv5v.hip, the one MFMA route that takes
+                   a bias (LeNet's two convolutions; PF_OWN_CONV5V=0: general / library).  Like conv3x3n it asks `x.is_cuda` itself;
+                   an image (3 channels) that asks for its gradient is refused, as for the 3x3 stems.
       conv3x3n     3x3 / stride 1 / pad 1 with 16 | 32 input and output channels on pf_conv3x3_narrow.hip (PF_OWN_CONV3X3_NARROW=0:
                    im2col); it asks `x.is_cuda` itself, whatever stands in for fusable_tensor.
       igemm        RxS on the implicit-GEMM kernel (cin % 64 == 0).
@@ -2119,6 +2189,8 @@ class Conv2D:
     if stem is not None:
       return 'stem', x, stem.pads, stem.out_hw, None, stem
     x, pad = _symmetric_pads(x, ph, pw)
+    if self._conv5v_ok(x, ph, pw):
+      return 'conv5v', x, pad, out_hw, None, None
     if (mfma and OWN_CONV3X3_NARROW and x.is_cuda and self.k == 3 and self.stride == 1 and ph == (1, 1) and pw == (1, 1)
         and hip.conv3x3n_supported(x.shape[2], x.shape[3], cin, cout, 1, 1, 1)
         and hip.conv3x3n_wrw_slabs(x.shape[0], x.shape[2], x.shape[3], cin, cout) > 0):     # (the slabs query: the byte limit)
@@ -2179,6 +2251,27 @@ class Conv2D:
       y = _apply_with_stats(_Conv2dIgemm, xin, w, self.stride, pad, want_stats, self.graph, getattr(x, '_pf_bn', None), self.kernel)
     else:
       y = _run_conv2d(xin, w.detach().permute(0, 2, 3, 1), self.stride, pad, want_stats, out_bn=out_bn)
+    return y if residual is None else y + residual
+
+  def _conv5v_ok(self, x, ph, pw) -> bool:
+    """pf_conv5v.hip takes this layer on `x`: 5x5 / stride 1 / no padding, bias or not, a 4-D bf16 device tensor with fusion on (the
+    float32 parity mode and plain() keep the routes they had), the shape one of the kernels' (3 | 32 -> 32 | 64 channels, width up to
+    64; the slabs query: the byte limit), and, with 3 input channels, an image that asks for no gradient (the kernels compute none)."""
+    kh, kw, cin, cout = self.kernel.ref_shape
+    if not (OWN_CONV5V and self.k == 5 and self.stride == 1 and ph == (0, 0) and pw == (0, 0) and isinstance(x, torch.Tensor)
+            and x.is_cuda and fusable_tensor(x) and x.dim() == 4 and self.graph.fuse_conv1x1 and self.kernel.tensor.dtype == x.dtype):
+      return False
+    B, C, H, Wd = x.shape
+    return (C == cin and not (cin == 3 and x.requires_grad) and hip.conv5v_supported(H, Wd, cin, cout, 5, 1, 0, 0)
+            and hip.conv5v_wrw_slabs(B, H, Wd, cin, cout) > 0)
+
+  def _call_conv5v(self, r, residual, want_stats):
+    x, w = _nhwc(r[ROUTE_X]), self.kernel.tensor
+    bias = self.bias.tensor if self.bias is not None else None
+    if _wants_grad(w, x) or (bias is not None and torch.is_grad_enabled() and bias.requires_grad):
+      y = _Conv5Valid.apply(x, w, bias, self.graph, self.kernel)
+    else:
+      y = _run_conv5v(x, _krsc(w, x.dtype), bias)
     return y if residual is None else y + residual
 
   def _call_conv3x3n(self, r, residual, want_stats):

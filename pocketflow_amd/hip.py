@@ -66,6 +66,7 @@ SYMBOLS = [
     'pf_conv3x3n_supported', 'pf_conv3x3n_fwd', 'pf_conv3x3n_wrw_slabs', 'pf_conv3x3n_wrw',
     'pf_dense_supported', 'pf_dense_splits', 'pf_dense_fwd', 'pf_dense_bwd_data', 'pf_dense_wrw',
     'pf_conv_stem3x_supported', 'pf_conv_stem3x_fwd', 'pf_conv_stem3x_wrw_slabs', 'pf_conv_stem3x_wrw',
+    'pf_conv5v_supported', 'pf_conv5v_fwd', 'pf_conv5v_bwd_data', 'pf_conv5v_wrw_slabs', 'pf_conv5v_wrw',
 ]
 
 
@@ -1129,6 +1130,39 @@ def conv3x3n_wrw(dY, X, dW, workspace, imgs: int, H: int, Wd: int, C: int, N: in
   _dev(dY)
   _check(_lib.pf_conv3x3n_wrw(_ptr(dY), _ptr(X), _ptr(dW), c_int(dtype_code(dW)), _ptr(workspace), c_int(imgs), c_int(H), c_int(Wd),
                               c_int(C), c_int(N), _stream()), 'pf_conv3x3n_wrw')
+
+
+# 5x5 / stride 1 / 'VALID' convolutions with a bias (pf_conv5v.hip): C in {3, 32}, N in {32, 64}, 5 <= Wd <= 64 -- LeNet @ CIFAR-10
+
+def conv5v_supported(H: int, Wd: int, C: int, N: int, k: int, stride: int, pad_h: int, pad_w: int) -> bool:
+  return bool(_lib.pf_conv5v_supported(c_int(H), c_int(Wd), c_int(C), c_int(N), c_int(k), c_int(stride), c_int(pad_h), c_int(pad_w)))
+
+
+def conv5v_fwd(X, W, bias, Y, imgs: int, H: int, Wd: int, C: int, N: int) -> None:
+  """Y = conv(X, W) (+ bias, float32 or None, before the one rounding).  X: NHWC memory [imgs][H][Wd][C] bf16, W: KRSC memory
+  [N][5][5][C] bf16, Y: [imgs][H - 4][Wd - 4][N] bf16."""
+  _dev(X)
+  _check(_lib.pf_conv5v_fwd(_ptr(X), _ptr(W), _ptr(bias), _ptr(Y), c_int(imgs), c_int(H), c_int(Wd), c_int(C), c_int(N), _stream()),
+         'pf_conv5v_fwd')
+
+
+def conv5v_bwd_data(dY, Wt, dX, imgs: int, H: int, Wd: int, C: int, N: int) -> None:
+  """dX [imgs][H][Wd][C] from dY [imgs][H - 4][Wd - 4][N] and the flipped / transposed kernel Wt [C][5][5][N]; C = 32 only."""
+  _dev(dY)
+  _check(_lib.pf_conv5v_bwd_data(_ptr(dY), _ptr(Wt), _ptr(dX), c_int(imgs), c_int(H), c_int(Wd), c_int(C), c_int(N), _stream()),
+         'pf_conv5v_bwd_data')
+
+
+def conv5v_wrw_slabs(imgs: int, H: int, Wd: int, C: int, N: int) -> int:
+  return int(_lib.pf_conv5v_wrw_slabs(c_int(imgs), c_int(H), c_int(Wd), c_int(C), c_int(N)))
+
+
+def conv5v_wrw(dY, X, dW, db, workspace, imgs: int, H: int, Wd: int, C: int, N: int) -> None:
+  """dW: KRSC memory [N][5][5][C] float32 / bf16 and, where `db` is not None, db[n] = sum of dY over all pixels (float32);
+  workspace: float32, wrw_workspace_floats(conv5v_wrw_slabs(...), N * 25 * C)."""
+  _dev(dY)
+  _check(_lib.pf_conv5v_wrw(_ptr(dY), _ptr(X), _ptr(dW), c_int(dtype_code(dW)), _ptr(db), _ptr(workspace), c_int(imgs), c_int(H),
+                            c_int(Wd), c_int(C), c_int(N), _stream()), 'pf_conv5v_wrw')
 
 
 # dense layers on the matrix cores (pf_dense.hip): X / dX [B][K], W / dW [N][K], Y / dY [B][N] bf16 (dW: float32 or bf16), bias / db
